@@ -7,7 +7,14 @@ A "step" is one pass of MHEnt.get_loss (ResNet-50 encoder -> 12-coupling RealNVP
 One process per GPU; images are sharded across ranks, no data-path collective
 (weak scaling).  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times exactly --steps steps in one window and prints
+the line.  --full adds everything else: the per-kernel roofline pass, the train-step
+and iteration-with-metrics legs, the Glow variant, the CPU baseline, and the median
+of --windows timed windows.  --dump-outputs DIR writes the last timed step's
+outputs (the get_loss dict of rank 0) as DIR/<name>.npy.
+
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -100,6 +107,20 @@ def timed_windows(fn, steps, windows, dist, dev):
     from mhentropy_amd import dist as mdist
     dts = [mdist.timed_region(fn, steps, dist, dev) for _ in range(max(1, windows))]
     return float(np.median(dts)), [round(d / steps * 1e3, 3) for d in dts]
+
+
+def dump_outputs(out, d, budget=64 << 20):
+    """every tensor of the step's output dict as d/<name>.npy, float32 (float64 kept); were they over `budget` bytes together, each
+    would be cut to the same share of its elements, a fixed seeded sample of the flattened array"""
+    os.makedirs(d, exist_ok=True)
+    arrs = {k: v.detach().to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+            for k, v in out.items() if torch.is_tensor(v)}
+    total = sum(a.nbytes for a in arrs.values())
+    for k, a in arrs.items():
+        if total > budget:
+            keep = np.random.default_rng(0).choice(a.size, max(1, a.size * budget // total), replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def roofline_of(times, dtype, steps_timed, step_seconds, pmc_file, n_next=3):
@@ -255,17 +276,24 @@ def main():
     ap.add_argument("--flow", default="realnvp", choices=["realnvp", "glow"],
                     help="realnvp: the flow the reference ships (configs/ho3d.yaml:39) - the measured default; glow: the 4-layer "
                          "ConditionalGlow branch (parity unpinned; its train leg runs eagerly; no CPU baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: per-kernel roofline pass, train-step and iteration-with-metrics "
+                         "legs, Glow variant, CPU baseline, median of --windows windows (the options below marked --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's get_loss dict) as DIR/<name>.npy, "
+                         "float32 (float64 kept)")
     ap.add_argument("--no-glow-variant", action="store_true",
-                    help="skip the extra forward+loss timing of the same workload with the ConditionalGlow flow (BASELINE.json's "
+                    help="--full: skip the extra forward+loss timing of the same workload with the ConditionalGlow flow (BASELINE.json's "
                          "configs name a 4-block Glow; the reference ships RealNVP, which stays the measured default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--train-steps", type=int, default=5,
-                    help="also time this many full train steps (forward + reverse + all-reduce + clip + Adam) for the metric's "
+                    help="--full: also time this many full train steps (forward + reverse + all-reduce + clip + Adam) for the metric's "
                          "'img/s train step' part; 0 skips it")
     ap.add_argument("--windows", type=int, default=3,
-                    help="timed windows of --steps (--train-steps) steps each; ms_per_step / value are the MEDIAN window's, windows_ms lists all")
+                    help="--full: timed windows of --steps (--train-steps) steps each; ms_per_step / value are the MEDIAN window's, "
+                         "windows_ms lists all (a plain run times one window)")
     ap.add_argument("--metrics-samples", type=int, default=200,
-                    help="also time the reference's whole iteration: train step + sample(N=this) + MHEntLoss metrics "
+                    help="--full: also time the reference's whole iteration: train step + sample(N=this) + MHEntLoss metrics "
                          "(hand/CrossModalHand.py:349-361); 0 skips it")
     ap.add_argument("--graph", type=int, default=1, help="replay the step from a captured HIP graph (1) or launch eagerly (0)")
     ap.add_argument("--resident-noise", type=int, default=0,
@@ -274,6 +302,8 @@ def main():
     args = ap.parse_args()
     if args.dtype is None:
         args.dtype = "bf16" if args.workload == "c2" else "f32"
+    if not args.full:
+        args.windows = 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing has touched the GPU yet in this process; the N ranks
@@ -339,15 +369,17 @@ def main():
         out = step()
         torch.cuda.synchronize()
         log(f"warm-up step {i} done")
-    # ---- per-kernel timing pass (eager, HIP events on the launch stream around every conv launch)
-    ops.KERNEL_TIMES.clear()
-    ops.TIMING = True
-    for _ in range(min(args.steps, 3)):
-        step()
-    torch.cuda.synchronize()
-    ops.TIMING = False
-    fwd_times = list(ops.KERNEL_TIMES)
-    ops.KERNEL_TIMES.clear()
+    # ---- per-kernel timing pass (--full; eager, HIP events on the launch stream around every conv launch)
+    fwd_times = []
+    if args.full:
+        ops.KERNEL_TIMES.clear()
+        ops.TIMING = True
+        for _ in range(min(args.steps, 3)):
+            step()
+        torch.cuda.synchronize()
+        ops.TIMING = False
+        fwd_times = list(ops.KERNEL_TIMES)
+        ops.KERNEL_TIMES.clear()
     # ---- the timed region: exactly `steps` steps, replayed from one captured HIP graph (launch-bound inner
     # loop: ~250 launches per step) or launched eagerly with --graph 0
     last = {}
@@ -373,11 +405,14 @@ def main():
     loss_out = {k: v.clone() for k, v in out.items()}
     log(f"timed region: {dt * 1e3 / args.steps:.2f} ms/step (windows {windows_ms})")
     assert torch.isfinite(loss_out["log_p"]).all(), "non-finite loss"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(loss_out, args.dump_outputs)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
-    # ---- second part of BASELINE.json's metric: img/s of a full train step (hand/CrossModalHand.py:455-470) on the
-    # same model, inputs and hypotheses; every rank takes part (gradient all-reduce over RCCL when N > 1)
+    # ---- second part of BASELINE.json's metric (--full): img/s of a full train step (hand/CrossModalHand.py:455-470) on
+    # the same model, inputs and hypotheses; every rank takes part (gradient all-reduce over RCCL when N > 1)
     train = None
-    if args.train_steps > 0:
+    if args.full and args.train_steps > 0:
         del last, run
         if args.graph:
             del graph
@@ -387,9 +422,9 @@ def main():
             log(f"train-step leg failed: {type(e).__name__}: {e}")
             train = {"error": f"{type(e).__name__}: {e}"[:300]}
 
-    # ---- the same forward+loss workload with the Glow branch (parity unpinned), reported beside the headline, N=1 only
+    # ---- the same forward+loss workload with the Glow branch (parity unpinned), reported beside the headline, N=1 and --full only
     glow_variant = None
-    if args.flow == "realnvp" and world == 1 and not args.no_glow_variant:
+    if args.full and args.flow == "realnvp" and world == 1 and not args.no_glow_variant:
         try:
             del model
             torch.cuda.empty_cache()
@@ -457,9 +492,9 @@ def main():
         # roofline that binds its launches IN AGGREGATE - bf16 MFMA (2.5 PFLOP/s dense) when sum(flops)/peak exceeds
         # sum(algorithmic bytes)/8 TB/s, HBM otherwise (the plain 1x1 layers at 64-512 input channels move 128-512 B per
         # pixel for 64-512 MACs per byte pair: HBM-bound on this chip).  Timed live: HIP events on the launch stream around
-        # every launch (ops.TIMING), eager pass.
-        roof = roofline_of(fwd_times, args.dtype, min(args.steps, 3), dt / args.steps, PMC_TRAFFIC)
-        cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(cfg, sd, args.seed)      # rank 0 at N=1 only
+        # every launch (ops.TIMING), eager pass.  Both this and the CPU baseline run with --full only.
+        roof = roofline_of(fwd_times, args.dtype, min(args.steps, 3), dt / args.steps, PMC_TRAFFIC) if args.full else None
+        cpu = None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(cfg, sd, args.seed)      # rank 0 at N=1 only
         line = {
             "metric": "hypotheses/sec (BxK) fwd+loss, 256x256",
             "value": round(world * B * K * args.steps / dt, 1), "unit": "hypotheses/s",
@@ -472,7 +507,8 @@ def main():
                        "launch": "hip-graph replay" if args.graph else "eager",
                        "base_noise": "resident tensor" if args.resident_noise else "drawn on the device inside the step (Philox4x32-10, mhe_randn_f32)",
                        "img_per_s": round(world * B * args.steps / dt, 1),
-                       "timing": f"median of {max(1, args.windows)} windows of {args.steps} steps, each bracketed by barrier + synchronize",
+                       "timing": (f"median of {args.windows} windows of {args.steps} steps, each" if args.windows > 1 else
+                                  f"one window of {args.steps} steps,") + " bracketed by barrier + synchronize",
                        "switches_set": __import__("mhentropy_amd.switches", fromlist=["x"]).non_default(),     # {} = the product path (mhentropy_amd/switches.py)
                        "ranks": world, "rccl_ranks": (world if (dist is not None and dist.get_backend() == "nccl") else 0),
                        "backend": (None if dist is None else "rccl (torch backend 'nccl')" if dist.get_backend() == "nccl" else dist.get_backend()),

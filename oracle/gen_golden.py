@@ -438,8 +438,45 @@ def gen_ho3d():
         np.savez_compressed(os.path.join(GOLD, f"ho3d_{ci}.npz"), **out)
 
 
+def gen_index_tables():
+    """the MANO index tables, read by name out of the reference's source text (hand/manopth/manolayer.py:197-199,228,251,260,
+    hand/utils.py:15, hand/ManoLayer.py:112-118), so that the tests pin them without a reference tree"""
+    import re
+    print("[index tables]")
+    ml = open(os.path.join(REF, "manopth", "manolayer.py")).read()
+    ut = open(os.path.join(REF, "utils.py")).read()
+    wl = open(os.path.join(REF, "ManoLayer.py")).read()
+
+    def ints(src, pat):
+        return np.array([int(v) for v in re.search(pat, src).group(1).split(",")], np.int64)
+    out = {name: ints(ml, rf"{name}\s*=\s*\[([^\]]*)\]") for name in ("lev1_idxs", "lev2_idxs", "lev3_idxs", "reorder_idxs")}
+    out["tip_verts_right"] = ints(ml, r"side == 'right':\s*tips = th_verts\[:, \[([^\]]*)\]\]")
+    out["joint_reorder"] = ints(ml, r"th_jtr = th_jtr\[:, \[([^\]]*)\]\]")
+    out["freihand2rhd"] = ints(ut, r"FreiHand2RHD_skeidx\s*=\s*\[([^\]]*)\]")
+    tips = dict((int(k), int(v)) for k, v in re.findall(r"(\d+): \[(\d+)\]", re.search(r"kpId2vertices = \{([^}]*)\}", wl).group(1)))
+    out["wrapper_tip_keys"], out["wrapper_tip_verts"] = np.array(sorted(tips), np.int64), np.array([tips[k] for k in sorted(tips)], np.int64)
+    np.savez_compressed(os.path.join(GOLD, "mano_index_tables.npz"), **out)
+
+
+def gen_config_values():
+    """the values of hand/configs/ho3d.yaml that MHEnt's construction and the training schedule read (section -> key -> value)"""
+    import json
+    import yaml
+    print("[config values]")
+    cfg = yaml.safe_load(open(os.path.join(REF, "configs", "ho3d.yaml")))
+    keys = {"dataset": ("dataset_name", "image_size", "jointN", "pe"),
+            "network": ("enc_type", "input", "num_latent", "nums_latent", "backbone", "conditional_p", "feat_dim", "acts", "deterministic",
+                        "h_dims", "num_steps", "regressor", "rot_prior", "w_reg_th", "w_prior_2d", "w_reg_ds", "b_2d", "entropy", "mode"),
+            "training": ("batch_size", "lr", "milestones", "criterion", "test_samples")}
+    with open(os.path.join(GOLD, "ho3d_config_values.json"), "w") as fh:
+        json.dump({s: {k: cfg[s][k] for k in ks} for s, ks in keys.items()}, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
+    gen_index_tables()
+    gen_config_values()
     tables = synth.mano_tables(0)
     _install_placeholders(tables)
     sys.path.insert(0, REF)

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import ROOT, load_golden
 from mhentropy_amd import _lib, mano_pack, synth
 from oracle import mano_ref
 
@@ -63,22 +63,17 @@ def test_index_tables_are_the_references():
     assert _c_array(src, "kWrapTipVert") == [mano_ref.WRAPPER_TIP_VERTS[k] for k in (4, 8, 12, 16, 20)]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/hand"), reason="the reference tree only exists in the build container")
 def test_index_tables_against_the_reference_source_text():
-    """the same tables parsed straight out of the reference's source text (reading it is study, nothing is imported):
-    hand/manopth/manolayer.py:197-199,228,251,260, hand/utils.py:15, hand/ManoLayer.py:112-127"""
-    ml = open("/root/reference/hand/manopth/manolayer.py").read()
-    lists = [[int(v) for v in m.split(",")] for m in re.findall(r"\[((?:\s*\d+\s*,)+\s*\d+\s*)\]", ml)]
-    assert [1, 4, 7, 10, 13] in lists and [2, 5, 8, 11, 14] in lists and [3, 6, 9, 12, 15] in lists
-    assert [0, 1, 6, 11, 2, 7, 12, 3, 8, 13, 4, 9, 14, 5, 10, 15] in lists                   # reorder_idxs
-    assert list(mano_ref.TIP_VERTS_RIGHT) in lists                                            # [745, 317, 444, 556, 673]
-    assert list(mano_ref.JOINT_REORDER) in lists
-    ut = open("/root/reference/hand/utils.py").read()
-    m = re.search(r"FreiHand2RHD_skeidx\s*=\s*\[([^\]]*)\]", ut)
-    assert [int(v) for v in m.group(1).split(",")] == list(mano_ref.FREIHAND2RHD)
-    wl = open("/root/reference/hand/ManoLayer.py").read()
-    for k, v in mano_ref.WRAPPER_TIP_VERTS.items():
-        assert re.search(rf"\b{v}\b", wl), (k, v)
+    """the same tables as parsed out of the reference's source text by oracle/gen_golden.py (tests/golden/mano_index_tables.npz):
+    hand/manopth/manolayer.py:197-199,228,251,260, hand/utils.py:15, hand/ManoLayer.py:112-118"""
+    g = load_golden("mano_index_tables")
+    assert g["lev1_idxs"].tolist() == [1, 4, 7, 10, 13] and g["lev2_idxs"].tolist() == [2, 5, 8, 11, 14]
+    assert g["lev3_idxs"].tolist() == [3, 6, 9, 12, 15]
+    assert g["reorder_idxs"].tolist() == [0, 1, 6, 11, 2, 7, 12, 3, 8, 13, 4, 9, 14, 5, 10, 15]
+    assert g["tip_verts_right"].tolist() == list(mano_ref.TIP_VERTS_RIGHT)                   # [745, 317, 444, 556, 673]
+    assert g["joint_reorder"].tolist() == list(mano_ref.JOINT_REORDER)
+    assert g["freihand2rhd"].tolist() == list(mano_ref.FREIHAND2RHD)
+    assert dict(zip(g["wrapper_tip_keys"].tolist(), g["wrapper_tip_verts"].tolist())) == mano_ref.WRAPPER_TIP_VERTS
 
 
 def test_flow_pack_roundtrip():

@@ -25,14 +25,14 @@ python tools/pmc_traffic.py $O/pmc_fetch_train $O/pmc_write_train $O/train_pmc_t
 cp $O/train_pmc_traffic.json profiles/r04_train_pmc_traffic.json
 # the headline line last: it reads profiles/r04_pmc_traffic.json for roofline.traffic, which must come from these very sources
 cp $O/pmc_traffic.json profiles/r04_pmc_traffic.json
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -2 $O/bench.err
 python tools/pmc_mfma.py $O/pmc_mfma $O/pmc_mfma.json
 python tools/pmc_mfma.py $O/pmc_mfma_train $O/pmc_mfma_train.json
 python tools/trace_stats.py $O/train_tr $O/train_kernel_stats.csv step:adam_kernel:5 > $O/train_stats.txt; tail -1 $O/train_stats.txt
 # the forward's kernels PER TIMED STEP (a step ends with its single elbo_reduce launch): nothing of the model's construction in it
 python tools/trace_stats.py $O/stats $O/step_kernel_stats.csv step:elbo_reduce_kernel:5 > $O/step_stats.txt; tail -1 $O/step_stats.txt
-timeout -k 10 300 python bench.py --workload c1 --no-glow-variant > $O/bench_c1.json 2> $O/bench_c1.err || true
+timeout -k 10 300 python bench.py --workload c1 --no-glow-variant --full > $O/bench_c1.json 2> $O/bench_c1.err || true
 find $O -name "*counter_collection.csv" -size +4M -delete; find $O -name "*kernel_trace.csv" -size +4M -delete
 du -sh $O
 echo "cp $O/bench.json profiles/r04_bench_c2_bf16.json; cp $O/stats/s_kernel_stats.csv profiles/r04_c2_bf16_kernel_stats.csv; cp $O/pmc_traffic.json profiles/r04_pmc_traffic.json; cp $O/pmc_mfma.json profiles/r04_pmc_mfma.json; cp $O/pmc_mfma_train.json profiles/r04_pmc_mfma_train.json; cp $O/train_kernel_stats.csv profiles/r04_train_kernel_stats.csv; cp $O/step_kernel_stats.csv profiles/r04_c2_bf16_step_kernel_stats.csv; cp $O/bench_c1.json profiles/r04_bench_c1_f32.json; cp $O/train_pmc_traffic.json profiles/r04_train_pmc_traffic.json"
