@@ -37,6 +37,8 @@ extern "C" {
 enum { MHE_ACT_NONE = 0, MHE_ACT_RELU = 1 };
 enum { MHE_F32 = 0, MHE_BF16 = 1 };
 enum { MHE_FLOW_FORWARD = 0, MHE_FLOW_INVERSE = 1 };
+/* likelihoods of the MANO loss pass (the reference's get_loss `mods`, hand/network.py:620-643): a bit set */
+enum { MHE_MODS_UV = 1, MHE_MODS_XYZ = 2 };
 
 /* library ---------------------------------------------------------------- */
 /* MHE_ABI_VERSION changes whenever a struct layout or an existing signature changes (new entry points alone do not bump it).
@@ -198,6 +200,20 @@ int mhe_mano_joints_f32(const float *th45, const float *det, const float *crop_u
                         float *z, float *xyz, float *uv, float *terms, float *log_p, float *norms,
                         float *joints_mm, int R, int B, float laplace_b, float th45_alpha, int inv_norm, float image_size,
                         void *stream);
+/* mhe_mano_joints_f32 with the likelihoods chosen by `mods` (MHE_MODS_UV | MHE_MODS_XYZ): the reference's 3D-supervised
+ * get_loss(mods=['xyz', 'uv']) (hand/CrossModalHand.py:354, hand/network.py:393,398-400,620-662).  MHE_MODS_XYZ adds the
+ * visibility-masked Laplace of the 63 normalised joint coordinates (root 12, bone 11) against pose3d with constant
+ * b = laplace_b_3d (the reference's 0.03, independent of laplace_b); joint k of image b is weighted by vis[b][k] == 1.
+ *   pose3d [B,63]  target joints (may be NULL when MHE_MODS_XYZ is off); crop_uv may be NULL when MHE_MODS_UV is off
+ *   terms  [R,5] = log p(uv|z), log p(xyz|z), log p(th3), log p(th45), log p(bt), 0 for a modality that is off;
+ *   log_p  [R]   ((uv + xyz) + th3 + th45) + bt, the reference's order.  Other outputs as in mhe_mano_joints_f32.
+ * MHE_ERR_ARG when mods is empty or has unknown bits, when an enabled modality lacks its target or has b <= 0.  The
+ * one-hypothesis-per-wave A/B kernel (MHE_MANO_FOUR=0) evaluates MHE_MODS_UV only. */
+int mhe_mano_joints_mods_f32(const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
+                             const float *tables,
+                             float *z, float *xyz, float *uv, float *terms, float *log_p, float *norms,
+                             float *joints_mm, int R, int B, int mods, float laplace_b, float laplace_b_3d, float th45_alpha,
+                             int inv_norm, float image_size, void *stream);
 
 /* Full 778-vertex linear-blend skinning for MHEnt.sample
  * (hand/manopth/manolayer.py:181-246, hand/network.py:480): verts [R,778,3]
@@ -429,6 +445,12 @@ int mhe_topk_gather_f32(const float *score, const float *rows, int *idx_out, flo
 int mhe_mano_joints_bwd_f32(const float *th45, const float *det, const float *crop_uv, const float *vis,
                             const float *tables, const float *g_log_p, float *g_th45, float *g_det_rows,
                             int R, int B, float laplace_b, float th45_alpha, float row_weight, void *stream);
+/* Reverse of mhe_mano_joints_mods_f32's log_p (arguments as there and in mhe_mano_joints_bwd_f32).  The 3D term's adjoint
+ * reaches all three components of the normalised joints; the root's coordinates are identically 0 and take none. */
+int mhe_mano_joints_mods_bwd_f32(const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
+                                 const float *tables, const float *g_log_p, float *g_th45, float *g_det_rows,
+                                 int R, int B, int mods, float laplace_b, float laplace_b_3d, float th45_alpha, float row_weight,
+                                 void *stream);
 /* out[b*out_stride + c] (+)= sum_n rows[(n*B + b)][c] : the adjoint of `.repeat(N,1)` (hand/network.py:734,747);
  * out_stride <= 0 means C (dense). */
 int mhe_sum_over_hypotheses_f32(const float *rows, float *out, int N, int B, int C, int accumulate, long out_stride,

@@ -12,6 +12,9 @@
 
 namespace mhe { namespace mano {
 
+// NTERMS = 4: terms [R,4] = (uv, th3, th45, bt) of mhe_mano_joints_f32; 5: [R,5] = (uv, xyz = 0, th3, th45, bt) of
+// mhe_mano_joints_mods_f32 with mods = uv (this A/B kernel evaluates the 2D likelihood only)
+template <int NTERMS>
 __global__ __launch_bounds__(256) void mano_joints_kernel(
     const float *__restrict__ th45_g, const float *__restrict__ det_g, const float *__restrict__ crop_uv,
     const float *__restrict__ vis, const float *__restrict__ tables,
@@ -73,8 +76,13 @@ __global__ __launch_bounds__(256) void mano_joints_kernel(
             const float lp_3 = -5.f * v3 * v3;
             if (lane == 0) {
                 if (terms_o) {
-                    float4 t4 = make_float4(lp_uv, lp_3, lp_45, lp_bt);
-                    reinterpret_cast<float4 *>(terms_o)[r] = t4;
+                    if constexpr (NTERMS == 4) {
+                        float4 t4 = make_float4(lp_uv, lp_3, lp_45, lp_bt);
+                        reinterpret_cast<float4 *>(terms_o)[r] = t4;
+                    } else {
+                        float *t = terms_o + (size_t)r * 5;
+                        t[0] = lp_uv; t[1] = 0.f; t[2] = lp_3; t[3] = lp_45; t[4] = lp_bt;
+                    }
                 }
                 if (logp_o) logp_o[r] = ((lp_uv + lp_3) + lp_45) + lp_bt;
             }
@@ -100,12 +108,17 @@ __device__ __forceinline__ float group_sum16(float v) {
     return v;
 }
 
+// MODS: the likelihoods evaluated (MODS_UV: 2D joints against crop_uv, MODS_XYZ: normalised 3D joints against pose3d,
+// hand/network.py:620-643).  NTERMS = 4: terms [R,4] = (uv, th3, th45, bt) of mhe_mano_joints_f32 (MODS_UV only);
+// 5: [R,5] = (uv, xyz, th3, th45, bt) of mhe_mano_joints_mods_f32, 0 for a modality that is off.
+template <int MODS, int NTERMS>
 __global__ __launch_bounds__(256) void mano_joints16_kernel(
     const float *__restrict__ th45_g, const float *__restrict__ det_g, const float *__restrict__ crop_uv,
-    const float *__restrict__ vis, const float *__restrict__ tables,
+    const float *__restrict__ vis, const float *__restrict__ pose3d, const float *__restrict__ tables,
     float *__restrict__ z_o, float *__restrict__ xyz_o, float *__restrict__ uv_o, float *__restrict__ terms_o,
     float *__restrict__ logp_o, float *__restrict__ norms_o, float *__restrict__ jmm_o, float *__restrict__ ws_o,
-    int R, int B, float lap_b, float th45_alpha, int inv_norm, float image_size) {
+    int R, int B, float lap_b, float lap_b3, float th45_alpha, int inv_norm, float image_size) {
+    static_assert(MODS >= 1 && MODS <= 3 && (NTERMS == 5 || (NTERMS == 4 && MODS == MODS_UV)), "mano_joints16_kernel instantiation");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *tb = smem;
     for (int i = threadIdx.x; i < JOINT_FLOATS / 4; i += 256)
@@ -114,6 +127,7 @@ __global__ __launch_bounds__(256) void mano_joints16_kernel(
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, grp = lane >> 4, sub = lane & 15;
     float *sc = smem + JOINT_FLOATS + (wave * 4 + grp) * SCRATCH16;
     const float log2b = logf(2.f * lap_b);
+    const float log2b3 = (MODS & MODS_XYZ) ? logf(2.f * lap_b3) : 0.f;
     const int nrow4 = (R + 3) / 4;                       // row quads; a wave takes quad qd -> rows 4 qd + grp
 
     for (int qd = blockIdx.x * 4 + wave; qd < nrow4; qd += gridDim.x * 4) {
@@ -299,11 +313,28 @@ __global__ __launch_bounds__(256) void mano_joints16_kernel(
                 float uv = s_cam * sc[S16_XYZ + 3 * (u >> 1) + (u & 1)] + sc[S16_DET + 14 + (u & 1)];
                 if (inv_norm) uv = (uv + 1.f) / 2.f * image_size;
                 if (live && uv_o) uv_o[(size_t)r * 42 + u] = uv;
-                if (terms_o || logp_o) {
+                if ((MODS & MODS_UV) && (terms_o || logp_o)) {
                     const float y = crop_uv[b * 42 + u];
                     const float w = vis[b * 21 + (u >> 1)];
                     const float e = -(fmaxf(fabsf(y - uv) - 1e-4f, 0.f) + 1e-4f) / lap_b - log2b;
                     lt += (w == 1.f) ? e : 0.f;
+                }
+            }
+        }
+        // visibility-masked Laplace over the 63 normalised joint coordinates, constant b (hand/network.py:393,398-400,620-643); the
+        // root's coordinates are exactly 0, so they add a constant
+        float lx = 0.f;
+        if constexpr ((MODS & MODS_XYZ) != 0) {
+            if (terms_o || logp_o) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int u = sub + 16 * i;
+                    if (u < 63) {
+                        const float y = pose3d[b * 63 + u];
+                        const float w = vis[b * 21 + u / 3];
+                        const float e = -(fmaxf(fabsf(y - sc[S16_XYZ + u]) - 1e-4f, 0.f) + 1e-4f) / lap_b3 - log2b3;
+                        lx += (w == 1.f) ? e : 0.f;
+                    }
                 }
             }
         }
@@ -341,9 +372,22 @@ __global__ __launch_bounds__(256) void mano_joints16_kernel(
             const float r3 = sqrtf(t0 * t0 + t1 * t1 + t2 * t2);
             const float v3 = fmaxf(r3 / 3.14159265358979323846f - 1.f, 0.f);
             const float lp_3 = -5.f * v3 * v3;
-            if (live && sub == 0) {
-                if (terms_o) reinterpret_cast<float4 *>(terms_o)[r] = make_float4(lp_uv, lp_3, lp_45, lp_bt);
-                if (logp_o) logp_o[r] = ((lp_uv + lp_3) + lp_45) + lp_bt;
+            if constexpr (NTERMS == 4) {
+                if (live && sub == 0) {
+                    if (terms_o) reinterpret_cast<float4 *>(terms_o)[r] = make_float4(lp_uv, lp_3, lp_45, lp_bt);
+                    if (logp_o) logp_o[r] = ((lp_uv + lp_3) + lp_45) + lp_bt;
+                }
+            } else {
+                // the reference sums the dict in insertion order: uv, xyz, then the priors (hand/network.py:620-662)
+                const float lp_xyz = (MODS & MODS_XYZ) ? group_sum16(lx) : 0.f;
+                const float lp_y = MODS == MODS_UV ? lp_uv : (MODS == MODS_XYZ ? lp_xyz : lp_uv + lp_xyz);
+                if (live && sub == 0) {
+                    if (terms_o) {
+                        float *t = terms_o + (size_t)r * 5;
+                        t[0] = lp_uv; t[1] = lp_xyz; t[2] = lp_3; t[3] = lp_45; t[4] = lp_bt;
+                    }
+                    if (logp_o) logp_o[r] = ((lp_y + lp_3) + lp_45) + lp_bt;
+                }
             }
         }
         wave_sync();                                     // the next quad's inputs overwrite the scratch
@@ -501,29 +545,47 @@ using namespace mhe;
 
 extern "C" size_t mhe_mano_table_floats(void) { return mano::TOTAL_FLOATS; }
 
-static int joints_launch(const float *th45, const float *det, const float *crop_uv, const float *vis,
+template <int MODS, int NTERMS>
+static int launch16(const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d, const float *tables,
+                    float *z, float *xyz, float *uv, float *terms, float *log_p, float *norms, float *joints_mm, float *ws_rows, int R, int B,
+                    float laplace_b, float laplace_b_3d, float th45_alpha, int inv_norm, float image_size, void *stream) {
+    const int quads = (R + 3) / 4, wgs = (quads + 3) / 4;
+    const int blocks = wgs < 512 ? wgs : 512;            // two workgroups per CU (67 KiB of LDS each), every wave walks its share of the row quads
+    const size_t lds = (mano::JOINT_FLOATS + 16 * mano::SCRATCH16) * sizeof(float);
+    hipLaunchKernelGGL((mano::mano_joints16_kernel<MODS, NTERMS>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, th45, det, crop_uv,
+                       vis, pose3d, tables, z, xyz, uv, terms, log_p, norms, joints_mm, ws_rows, R, B, laplace_b, laplace_b_3d, th45_alpha,
+                       inv_norm, image_size);
+    return check_launch("mano_joints16_kernel");
+}
+
+// mods: MHE_MODS_* bit set; nterms: width of a terms row (4: mhe_mano_joints_f32 / mhe_mano_decode_f32, 5: mhe_mano_joints_mods_f32)
+static int joints_launch(const char *who, const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
                          const float *tables, float *z, float *xyz, float *uv, float *terms, float *log_p,
-                         float *norms, float *joints_mm, float *ws_rows, int R, int B, float laplace_b, float th45_alpha,
-                         int inv_norm, float image_size, void *stream) {
-    MHE_REQUIRE(th45 && det && tables, "mhe_mano_joints_f32: null input");
-    MHE_REQUIRE(R > 0 && B > 0 && R % B == 0, "mhe_mano_joints_f32: R=%d must be a positive multiple of B=%d", R, B);
-    MHE_REQUIRE(!(terms || log_p) || (crop_uv && vis), "mhe_mano_joints_f32: likelihood outputs need crop_uv and vis");
-    MHE_REQUIRE(laplace_b > 0.f, "mhe_mano_joints_f32: laplace_b must be > 0");
+                         float *norms, float *joints_mm, float *ws_rows, int R, int B, int mods, int nterms, float laplace_b,
+                         float laplace_b_3d, float th45_alpha, int inv_norm, float image_size, void *stream) {
+    const bool lik = terms || log_p, m_uv = mods & MHE_MODS_UV, m_xyz = mods & MHE_MODS_XYZ;
+    MHE_REQUIRE(th45 && det && tables, "%s: null input", who);
+    MHE_REQUIRE(R > 0 && B > 0 && R % B == 0, "%s: R=%d must be a positive multiple of B=%d", who, R, B);
+    MHE_REQUIRE(!(lik && m_uv) || (crop_uv && vis), "%s: likelihood outputs need crop_uv and vis", who);
+    MHE_REQUIRE(!(lik && m_xyz) || (pose3d && vis), "%s: the xyz likelihood needs pose3d and vis", who);
+    MHE_REQUIRE(!m_uv || laplace_b > 0.f, "%s: laplace_b must be > 0", who);
+    MHE_REQUIRE(!m_xyz || laplace_b_3d > 0.f, "%s: laplace_b_3d must be > 0", who);
     static const int four = getenv("MHE_MANO_FOUR") ? atoi(getenv("MHE_MANO_FOUR")) : 1;      // 0: the one-hypothesis-per-wave kernel (A/B runs)
     if (four) {
-        const int quads = (R + 3) / 4, wgs = (quads + 3) / 4;
-        const int blocks = wgs < 512 ? wgs : 512;            // two workgroups per CU (67 KiB of LDS each), every wave walks its share of the row quads
-        const size_t lds = (mano::JOINT_FLOATS + 16 * mano::SCRATCH16) * sizeof(float);
-        hipLaunchKernelGGL(mano::mano_joints16_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, th45, det, crop_uv,
-                           vis, tables, z, xyz, uv, terms, log_p, norms, joints_mm, ws_rows, R, B, laplace_b, th45_alpha, inv_norm, image_size);
-        return check_launch("mano_joints16_kernel");
+        if (nterms == 4) return launch16<mano::MODS_UV, 4>(th45, det, crop_uv, vis, pose3d, tables, z, xyz, uv, terms, log_p, norms, joints_mm,
+                                                           ws_rows, R, B, laplace_b, laplace_b_3d, th45_alpha, inv_norm, image_size, stream);
+        auto fn = mods == MHE_MODS_UV ? launch16<mano::MODS_UV, 5> : (mods == MHE_MODS_XYZ ? launch16<mano::MODS_XYZ, 5>
+                                                                                            : launch16<mano::MODS_UV | mano::MODS_XYZ, 5>);
+        return fn(th45, det, crop_uv, vis, pose3d, tables, z, xyz, uv, terms, log_p, norms, joints_mm, ws_rows, R, B, laplace_b, laplace_b_3d,
+                  th45_alpha, inv_norm, image_size, stream);
     }
     MHE_REQUIRE(!ws_rows, "mhe_mano_decode_f32 runs on the four-hypotheses-per-wave kernel (MHE_MANO_FOUR=1)");
+    MHE_REQUIRE(!m_xyz, "%s: the one-hypothesis-per-wave kernel (MHE_MANO_FOUR=0) evaluates the uv likelihood only", who);
     const int blocks = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
     const size_t lds = (mano::JOINT_FLOATS + 4 * mano::SCRATCH) * sizeof(float);
-    hipLaunchKernelGGL(mano::mano_joints_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, th45, det, crop_uv,
-                       vis, tables, z, xyz, uv, terms, log_p, norms, joints_mm, R, B, laplace_b, th45_alpha, inv_norm,
-                       image_size);
+    hipLaunchKernelGGL((nterms == 4 ? mano::mano_joints_kernel<4> : mano::mano_joints_kernel<5>), dim3(blocks), dim3(256), lds,
+                       (hipStream_t)stream, th45, det, crop_uv, vis, tables, z, xyz, uv, terms, log_p, norms, joints_mm, R, B, laplace_b,
+                       th45_alpha, inv_norm, image_size);
     return check_launch("mano_joints_kernel");
 }
 
@@ -535,8 +597,21 @@ extern "C" int mhe_mano_joints_f32(const float *th45, const float *det, const fl
                                    const float *tables, float *z, float *xyz, float *uv, float *terms, float *log_p,
                                    float *norms, float *joints_mm, int R, int B, float laplace_b, float th45_alpha,
                                    int inv_norm, float image_size, void *stream) {
-    return joints_launch(th45, det, crop_uv, vis, tables, z, xyz, uv, terms, log_p, norms, joints_mm, nullptr, R, B, laplace_b, th45_alpha,
-                         inv_norm, image_size, stream);
+    return joints_launch("mhe_mano_joints_f32", th45, det, crop_uv, vis, nullptr, tables, z, xyz, uv, terms, log_p, norms, joints_mm, nullptr,
+                         R, B, MHE_MODS_UV, 4, laplace_b, 0.f, th45_alpha, inv_norm, image_size, stream);
+}
+
+// the same pass with the likelihoods chosen by `mods` (hand/network.py:620-643; the reference's 3D-supervised mode, mods = ['xyz', 'uv'])
+extern "C" int mhe_mano_joints_mods_f32(const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
+                                        const float *tables, float *z, float *xyz, float *uv, float *terms, float *log_p,
+                                        float *norms, float *joints_mm, int R, int B, int mods, float laplace_b, float laplace_b_3d,
+                                        float th45_alpha, int inv_norm, float image_size, void *stream) {
+    MHE_REQUIRE(mods >= 1 && mods <= (MHE_MODS_UV | MHE_MODS_XYZ), "mhe_mano_joints_mods_f32: mods=%d must be a non-empty set of MHE_MODS_UV | MHE_MODS_XYZ", mods);
+    MHE_REQUIRE(!(mods & MHE_MODS_XYZ) || pose3d, "mhe_mano_joints_mods_f32: mods has MHE_MODS_XYZ but pose3d is null");
+    MHE_REQUIRE(!(mods & MHE_MODS_UV) || crop_uv, "mhe_mano_joints_mods_f32: mods has MHE_MODS_UV but crop_uv is null");
+    MHE_REQUIRE(vis, "mhe_mano_joints_mods_f32: null vis");
+    return joints_launch("mhe_mano_joints_mods_f32", th45, det, crop_uv, vis, pose3d, tables, z, xyz, uv, terms, log_p, norms, joints_mm,
+                         nullptr, R, B, mods, 5, laplace_b, laplace_b_3d, th45_alpha, inv_norm, image_size, stream);
 }
 
 extern "C" size_t mhe_mano_verts_workspace_floats(int R) { return R > 0 ? mhe_mano_skin_split_floats() + (size_t)R * mano::WS_STRIDE : 0; }
@@ -567,8 +642,8 @@ extern "C" int mhe_mano_decode_f32(const float *th45, const float *det, const fl
                                    float th45_alpha, int inv_norm, float image_size, int mm_mode, void *stream) {
     MHE_REQUIRE(verts && workspace, "mhe_mano_decode_f32: null pointer");
     float *rows = workspace + mhe_mano_skin_split_floats();
-    if (int rc = joints_launch(th45, det, crop_uv, vis, tables, z, xyz, uv, terms, log_p, norms, joints_mm, rows, R, B, laplace_b, th45_alpha,
-                               inv_norm, image_size, stream))
+    if (int rc = joints_launch("mhe_mano_decode_f32", th45, det, crop_uv, vis, nullptr, tables, z, xyz, uv, terms, log_p, norms, joints_mm, rows,
+                               R, B, MHE_MODS_UV, 4, laplace_b, 0.f, th45_alpha, inv_norm, image_size, stream))
         return rc;
     return mhe_mano_skin_mfma(rows, tables, workspace, verts, R, mm_mode, (hipStream_t)stream);
 }

@@ -25,10 +25,13 @@ constexpr int A_TIPV = 640;    // [5][3]    posed tip vertices (rest frame)
 constexpr int A_POSE = 656;    // [48]      axis-angles
 constexpr int A_SCRATCH = 704;
 
+// MODS: the likelihoods in log_p (MODS_UV and / or MODS_XYZ, as in mano_joints16_kernel)
+template <int MODS>
 __global__ __launch_bounds__(256) void mano_joints_bwd_kernel(
     const float *__restrict__ th45_g, const float *__restrict__ det_g, const float *__restrict__ crop_uv,
-    const float *__restrict__ vis, const float *__restrict__ tables, const float *__restrict__ g_logp,
-    float *__restrict__ g_th45_o, float *__restrict__ g_det_o, int R, int B, float lap_b, float th45_alpha, float row_w) {
+    const float *__restrict__ vis, const float *__restrict__ pose3d, const float *__restrict__ tables, const float *__restrict__ g_logp,
+    float *__restrict__ g_th45_o, float *__restrict__ g_det_o, int R, int B, float lap_b, float lap_b3, float th45_alpha, float row_w) {
+    static_assert(MODS >= 1 && MODS <= 3, "mano_joints_bwd_kernel instantiation");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *tb = smem;
     for (int i = threadIdx.x; i < JOINT_FLOATS / 4; i += 256)
@@ -52,7 +55,7 @@ __global__ __launch_bounds__(256) void mano_joints_bwd_kernel(
         const int lu = lane < 42 ? lane : 41;
         const float uv = s_cam * __shfl(o.xyz, 3 * (lu >> 1) + (lu & 1), 64) + t_cam;
         float a_uv = 0.f;
-        if (lane < 42) {
+        if ((MODS & MODS_UV) && lane < 42) {
             const float d = uv - crop_uv[b * 42 + lane];
             if (vis[b * 21 + (lane >> 1)] == 1.f && fabsf(d) > 1e-4f) a_uv = (d > 0.f ? -g : g) / lap_b;
         }
@@ -60,7 +63,15 @@ __global__ __launch_bounds__(256) void mano_joints_bwd_kernel(
         const float a_t0 = wave_sum((lane & 1) ? 0.f : a_uv);
         const float a_t1 = wave_sum((lane & 1) ? a_uv : 0.f);
         const float a_uv_j = __shfl(a_uv, 2 * k21 + (c3 < 2 ? c3 : 0), 64);
-        const float a_xyz = (lane < 63 && c3 < 2) ? s_cam * a_uv_j : 0.f;
+        float a_xyz = (lane < 63 && c3 < 2) ? s_cam * a_uv_j : 0.f;
+        if constexpr ((MODS & MODS_XYZ) != 0) {
+            // ---- Laplace on the normalised joints (hand/network.py:620-643).  The root's normalised coordinates are identically 0:
+            // their terms are constant and take no adjoint (the Sc cancellation below would only leave round-off of it)
+            if (lane < 63 && k21 != kRootIdx) {
+                const float d = o.xyz - pose3d[b * 63 + lane];
+                if (vis[b * 21 + k21] == 1.f && fabsf(d) > 1e-4f) a_xyz += (d > 0.f ? -g : g) / lap_b3;
+            }
+        }
 
         // ---- xyz = (J - J_root) / |J_norm - J_root|
         const float L = o.bone;
@@ -255,17 +266,38 @@ __global__ __launch_bounds__(256) void sum_over_hypotheses_kernel(const float *_
 
 using namespace mhe;
 
+static int joints_bwd_launch(const char *who, const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
+                             const float *tables, const float *g_log_p, float *g_th45, float *g_det_rows, int R, int B, int mods,
+                             float laplace_b, float laplace_b_3d, float th45_alpha, float row_weight, void *stream) {
+    MHE_REQUIRE(th45 && det && vis && tables && g_log_p && g_th45 && g_det_rows, "%s: null pointer", who);
+    MHE_REQUIRE(mods >= 1 && mods <= (MHE_MODS_UV | MHE_MODS_XYZ), "%s: mods=%d must be a non-empty set of MHE_MODS_UV | MHE_MODS_XYZ", who, mods);
+    MHE_REQUIRE(!(mods & MHE_MODS_UV) || crop_uv, "%s: mods has MHE_MODS_UV but crop_uv is null", who);
+    MHE_REQUIRE(!(mods & MHE_MODS_XYZ) || pose3d, "%s: mods has MHE_MODS_XYZ but pose3d is null", who);
+    MHE_REQUIRE(R > 0 && B > 0 && R % B == 0, "%s: R=%d must be a positive multiple of B=%d", who, R, B);
+    MHE_REQUIRE(!(mods & MHE_MODS_UV) || laplace_b > 0.f, "%s: laplace_b must be > 0", who);
+    MHE_REQUIRE(!(mods & MHE_MODS_XYZ) || laplace_b_3d > 0.f, "%s: laplace_b_3d must be > 0", who);
+    const int blocks = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
+    const size_t lds = (mano::JOINT_FLOATS + 4 * (mano::SCRATCH + mano::A_SCRATCH)) * sizeof(float);
+    auto kern = mods == MHE_MODS_UV ? mano::mano_joints_bwd_kernel<mano::MODS_UV>
+                                    : (mods == MHE_MODS_XYZ ? mano::mano_joints_bwd_kernel<mano::MODS_XYZ>
+                                                            : mano::mano_joints_bwd_kernel<mano::MODS_UV | mano::MODS_XYZ>);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, (hipStream_t)stream, th45, det, crop_uv, vis, pose3d, tables, g_log_p, g_th45,
+                       g_det_rows, R, B, laplace_b, laplace_b_3d, th45_alpha, row_weight);
+    return check_launch("mano_joints_bwd_kernel");
+}
+
 extern "C" int mhe_mano_joints_bwd_f32(const float *th45, const float *det, const float *crop_uv, const float *vis,
                                        const float *tables, const float *g_log_p, float *g_th45, float *g_det_rows,
                                        int R, int B, float laplace_b, float th45_alpha, float row_weight, void *stream) {
-    MHE_REQUIRE(th45 && det && crop_uv && vis && tables && g_log_p && g_th45 && g_det_rows, "mhe_mano_joints_bwd_f32: null pointer");
-    MHE_REQUIRE(R > 0 && B > 0 && R % B == 0, "mhe_mano_joints_bwd_f32: R=%d must be a positive multiple of B=%d", R, B);
-    MHE_REQUIRE(laplace_b > 0.f, "mhe_mano_joints_bwd_f32: laplace_b must be > 0");
-    const int blocks = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
-    const size_t lds = (mano::JOINT_FLOATS + 4 * (mano::SCRATCH + mano::A_SCRATCH)) * sizeof(float);
-    hipLaunchKernelGGL(mano::mano_joints_bwd_kernel, dim3(blocks), dim3(256), lds, (hipStream_t)stream, th45, det, crop_uv,
-                       vis, tables, g_log_p, g_th45, g_det_rows, R, B, laplace_b, th45_alpha, row_weight);
-    return check_launch("mano_joints_bwd_kernel");
+    return joints_bwd_launch("mhe_mano_joints_bwd_f32", th45, det, crop_uv, vis, nullptr, tables, g_log_p, g_th45, g_det_rows, R, B,
+                             MHE_MODS_UV, laplace_b, 0.f, th45_alpha, row_weight, stream);
+}
+
+extern "C" int mhe_mano_joints_mods_bwd_f32(const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
+                                            const float *tables, const float *g_log_p, float *g_th45, float *g_det_rows, int R, int B,
+                                            int mods, float laplace_b, float laplace_b_3d, float th45_alpha, float row_weight, void *stream) {
+    return joints_bwd_launch("mhe_mano_joints_mods_bwd_f32", th45, det, crop_uv, vis, pose3d, tables, g_log_p, g_th45, g_det_rows, R, B,
+                             mods, laplace_b, laplace_b_3d, th45_alpha, row_weight, stream);
 }
 
 extern "C" int mhe_sum_over_hypotheses_f32(const float *rows, float *out, int N, int B, int C, int accumulate, long out_stride,

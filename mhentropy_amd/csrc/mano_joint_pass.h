@@ -15,6 +15,8 @@ static __device__ constexpr int kFreihand2Rhd[21] = {0, 4, 3, 2, 1, 8, 7, 6, 5, 
 constexpr int kCenterPre = 4;     // kJointReorder[center_idx = 9]   (manolayer.py:262-266)
 constexpr int kRootIdx = 12;      // hand/network.py:477
 constexpr int kNormIdx = 11;      // hand/network.py:478
+// likelihoods a loss-pass kernel evaluates (template argument; the `mods` bit set of mhe_mano_joints_mods_f32)
+constexpr int MODS_UV = MHE_MODS_UV, MODS_XYZ = MHE_MODS_XYZ;
 
 // per-wave LDS scratch (floats)
 constexpr int S_POSE = 0;      // [48]

@@ -105,6 +105,7 @@ class MHEnt(nn.Module):
         feat_dim = 512
         self.det_head = nn.Sequential(nn.Linear(feat_dim, feat_dim), nn.ReLU(inplace=True), nn.Linear(feat_dim, 16))
         self.b_2d = float(special_cfg["data_prior_cfg"]["b_2d"])                   # network.py:392
+        self.b_3d = 0.03                        # network.py:393 (constant, independent of b_2d)
         prior_cfg = special_cfg["prior_cfg"]
         if prior_cfg.get("p_theta45_pth"):
             raise NotImplementedError("VAE4Pose prior is undefined in the reference (network.py:423)")
@@ -146,16 +147,18 @@ class MHEnt(nn.Module):
 
     # ---- reference surface ------------------------------------------------------
     def _reverse_kld(self, y, x, mods=None, return_dict=True, N=None, noise=None):
-        """reference hand/network.py:760-831."""
-        if mods is not None and list(mods) != ["uv"]:
-            raise NotImplementedError("only the weakly supervised 'uv' likelihood of the shipped config is built")
+        """reference hand/network.py:760-831.  mods: ['uv'] (None; weak supervision), ['xyz'] or ['xyz', 'uv'] (3D supervision,
+        hand/CrossModalHand.py:354: adds the Laplace likelihood of the normalised joints against y['pose3d'], network.py:620-643)."""
+        bits = ops.mods_bits(mods)
+        if bits & ops.MODS_XYZ and "pose3d" not in y:
+            raise ValueError("get_loss(mods=[..., 'xyz']) needs the 3D target y['pose3d'] (B, 63)")
         N = N or self.loss_N
         tr = getattr(self, "_trainer", None)
         if tr is not None and self.training and torch.is_grad_enabled():
             # a train.TrainStep is attached: the loss dict comes out as ONE autograd node whose backward is the
             # hand-written reverse pass, so the reference's `total_loss.backward()` works unchanged
             from .train import differentiable_get_loss
-            return differentiable_get_loss(tr, x, y, N=N, noise=noise)
+            return differentiable_get_loss(tr, x, y, N=N, noise=noise, mods=bits)
         _, feat, _ = self.feat_extractor(x)
         B = feat.shape[0]
         if isinstance(self.q_z_giv_i, ConditionalGlow):      # entropy from the sampling pass itself (network.py:781-783,798-799)
@@ -167,8 +170,14 @@ class MHEnt(nn.Module):
             z0 = self._noise(N * B, 1.0, noise, feat.device)
             th45 = self.q_z_giv_i.forward_p(z0, cond=feat)
             log_q = self.q_z_giv_i.log_prob(th45, logvar=feat) if self.entropy else None       # network.py:801
-        o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(), y["crop_uv"].contiguous(),
-                            y["vis"].contiguous(), self.b_2d, self.th45_ref_alpha, want=("log_p", "norms"))
+        if bits == ops.MODS_UV:
+            o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(), y["crop_uv"].contiguous(),
+                                y["vis"].contiguous(), self.b_2d, self.th45_ref_alpha, want=("log_p", "norms"))
+        else:
+            o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(),
+                                y["crop_uv"].contiguous() if bits & ops.MODS_UV else None, y["vis"].contiguous(), self.b_2d,
+                                self.th45_ref_alpha, want=("log_p", "norms"), pose3d=y["pose3d"].contiguous().float(), mods=bits,
+                                laplace_b_3d=self.b_3d)
         q_log_p, h, log_p = ops.elbo_reduce(o["log_p"], log_q, N, B)
         out = {"th_norm": o["norms"][:, 0], "bt_norm": o["norms"][:, 1], "q_log_p_z_giv_y": q_log_p}
         if self.entropy:

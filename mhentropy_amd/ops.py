@@ -316,19 +316,53 @@ def flow_couplings_frag(x_in, cond, w0F, w1F, w2F, w_net_stride, bias2, mask, B,
     return out, sum_s, logp
 
 
+MODS_UV, MODS_XYZ = 1, 2           # MHE_MODS_* of include/mhe.h
+
+
+def mods_bits(mods):
+    """the reference's get_loss `mods` (hand/network.py:620-643; None means ['uv']) -> the MHE_MODS_* bit set.  'uv' and 'xyz' in any
+    order; anything else (the render mods 'm' / 'depth', the dead chamfer / p_ys branches) is not built"""
+    if mods is None:
+        return MODS_UV
+    names = [mods] if isinstance(mods, str) else list(mods)
+    bits = 0
+    for m in names:
+        if m not in ("uv", "xyz"):
+            raise NotImplementedError(f"mods={names!r}: only the 'uv' and 'xyz' likelihoods are built (hand/network.py:620-643)")
+        bits |= MODS_UV if m == "uv" else MODS_XYZ
+    if not bits or len(names) != len(set(names)):
+        raise NotImplementedError(f"mods={names!r}: expected ['uv'], ['xyz'] or ['xyz', 'uv']")
+    return bits
+
+
 def mano_joints(th45, det, tables, crop_uv=None, vis=None, laplace_b=0.03, th45_alpha=50.0, inv_norm=False,
-                image_size=256.0, want=("z", "xyz", "uv", "terms", "log_p", "norms")):
+                image_size=256.0, want=("z", "xyz", "uv", "terms", "log_p", "norms"), pose3d=None, mods=None, laplace_b_3d=0.03):
     """want may also include "joints_mm", and "verts" (the full mesh, normalised like xyz) or "mesh_mm" (ManoLayer's mesh in mm): the mesh
-    of the same hypotheses through mhe_mano_decode_f32 - the joint pass leaves the skinning operands, no second pose pass."""
+    of the same hypotheses through mhe_mano_decode_f32 - the joint pass leaves the skinning operands, no second pose pass.
+    mods (None, or a MHE_MODS_* bit set / the reference's list of names): the likelihoods in terms / log_p through
+    mhe_mano_joints_mods_f32 - terms is then [R,5] = (uv, xyz, th3, th45, bt); 'xyz' needs pose3d [B,63] (Laplace with b = laplace_b_3d)."""
     R, B = th45.shape[0], det.shape[0]
     dev = th45.device
     _chk(th45, torch.float32, "mano.th45", (R, 45)); _chk(det, torch.float32, "mano.det", (B, 16))
     _chk(tables, torch.float32, "mano.tables")
     if crop_uv is not None:
-        _chk(crop_uv, torch.float32, "mano.crop_uv", (B, 42)); _chk(vis, torch.float32, "mano.vis", (B, 21))
-    shapes = {"z": (R, 61), "xyz": (R, 63), "uv": (R, 42), "terms": (R, 4), "log_p": (R,), "norms": (R, 2),
+        _chk(crop_uv, torch.float32, "mano.crop_uv", (B, 42))
+    if vis is not None:
+        _chk(vis, torch.float32, "mano.vis", (B, 21))
+    if pose3d is not None:
+        _chk(pose3d, torch.float32, "mano.pose3d", (B, 63))
+    bits = None if mods is None else (int(mods) if isinstance(mods, int) else mods_bits(mods))
+    shapes = {"z": (R, 61), "xyz": (R, 63), "uv": (R, 42), "terms": (R, 4 if bits is None else 5), "log_p": (R,), "norms": (R, 2),
               "joints_mm": (R, 63)}
     o = {k: (torch.empty(shapes[k], device=dev, dtype=torch.float32) if k in want else None) for k in shapes}
+    if bits is not None:
+        if "verts" in want or "mesh_mm" in want:
+            raise ValueError("mano_joints: the mesh outputs come from the uv-only pass (mods=None)")
+        check(_lib.lib().mhe_mano_joints_mods_f32(_ptr(th45), _ptr(det), _ptr(crop_uv), _ptr(vis), _ptr(pose3d), _ptr(tables),
+                                                  _ptr(o["z"]), _ptr(o["xyz"]), _ptr(o["uv"]), _ptr(o["terms"]), _ptr(o["log_p"]),
+                                                  _ptr(o["norms"]), _ptr(o["joints_mm"]), R, B, bits, float(laplace_b), float(laplace_b_3d),
+                                                  float(th45_alpha), int(inv_norm), float(image_size), _stream()), "mhe_mano_joints_mods_f32")
+        return o
     if "verts" in want or "mesh_mm" in want:
         if "verts" in want and "mesh_mm" in want:
             raise ValueError("mano_joints: 'verts' or 'mesh_mm', one mesh per call")
@@ -348,17 +382,29 @@ def mano_joints(th45, det, tables, crop_uv=None, vis=None, laplace_b=0.03, th45_
     return o
 
 
-def mano_joints_bwd(th45, det, tables, crop_uv, vis, g_log_p, N, laplace_b=0.03, th45_alpha=50.0):
-    """reverse of mano_joints' log_p: (d/d th45 [R,45], d/d det [B,16]) for d loss/d log_p[n*B+b] = g_log_p[b]/N"""
+def mano_joints_bwd(th45, det, tables, crop_uv, vis, g_log_p, N, laplace_b=0.03, th45_alpha=50.0, pose3d=None, mods=None,
+                    laplace_b_3d=0.03):
+    """reverse of mano_joints' log_p: (d/d th45 [R,45], d/d det [B,16]) for d loss/d log_p[n*B+b] = g_log_p[b]/N;
+    mods / pose3d / laplace_b_3d as in mano_joints (crop_uv may be None when 'uv' is off)"""
     R, B = th45.shape[0], det.shape[0]
     _chk(th45, torch.float32, "mano_bwd.th45", (R, 45)); _chk(det, torch.float32, "mano_bwd.det", (B, 16))
-    _chk(crop_uv, torch.float32, "mano_bwd.crop_uv", (B, 42)); _chk(vis, torch.float32, "mano_bwd.vis", (B, 21))
+    if crop_uv is not None or mods is None:
+        _chk(crop_uv, torch.float32, "mano_bwd.crop_uv", (B, 42))
+    _chk(vis, torch.float32, "mano_bwd.vis", (B, 21))
+    if pose3d is not None:
+        _chk(pose3d, torch.float32, "mano_bwd.pose3d", (B, 63))
     _chk(g_log_p, torch.float32, "mano_bwd.g_log_p", (B,))
     g_th45 = torch.empty(R, 45, device=th45.device, dtype=torch.float32)
     g_rows = torch.empty(R, 16, device=th45.device, dtype=torch.float32)
-    check(_lib.lib().mhe_mano_joints_bwd_f32(_ptr(th45), _ptr(det), _ptr(crop_uv), _ptr(vis), _ptr(tables), _ptr(g_log_p),
-                                             _ptr(g_th45), _ptr(g_rows), R, B, float(laplace_b), float(th45_alpha), 1.0 / N,
-                                             _stream()), "mhe_mano_joints_bwd_f32")
+    if mods is None:
+        check(_lib.lib().mhe_mano_joints_bwd_f32(_ptr(th45), _ptr(det), _ptr(crop_uv), _ptr(vis), _ptr(tables), _ptr(g_log_p),
+                                                 _ptr(g_th45), _ptr(g_rows), R, B, float(laplace_b), float(th45_alpha), 1.0 / N,
+                                                 _stream()), "mhe_mano_joints_bwd_f32")
+    else:
+        bits = int(mods) if isinstance(mods, int) else mods_bits(mods)
+        check(_lib.lib().mhe_mano_joints_mods_bwd_f32(_ptr(th45), _ptr(det), _ptr(crop_uv), _ptr(vis), _ptr(pose3d), _ptr(tables),
+                                                      _ptr(g_log_p), _ptr(g_th45), _ptr(g_rows), R, B, bits, float(laplace_b),
+                                                      float(laplace_b_3d), float(th45_alpha), 1.0 / N, _stream()), "mhe_mano_joints_mods_bwd_f32")
     return g_th45, sum_over_hypotheses(g_rows, N, B)
 
 

@@ -5,6 +5,7 @@ on synthetic batches (no dataset ships with this repository; the HO3D pipeline i
 
     python -m mhentropy_amd.run --backbone resnet50 --batch 256 --hyps 64 --dtype bf16 --epochs 1 --iters 20
     python -m torch.distributed.run --nproc-per-node 8 -m mhentropy_amd.run ...      # one process per GPU, RCCL
+    python -m mhentropy_amd.run --mods uv,xyz ...        # 3D-supervised training (hand/CrossModalHand.py:354, mods = ['xyz', 'uv'])
 """
 import argparse
 import json
@@ -45,7 +46,13 @@ def main(argv=None):
                     help="feed the step from DECODED synthetic HO3D samples through the GPU input pipeline (ho3d_dataloader.HO3DBatchPipeline: "
                          "crop, augmentation, visibility, compute_st; hand/dataloader/ho3d_dataloader.py:272-459) instead of ready-made batches; "
                          "image size is then 256")
+    ap.add_argument("--mods", default="uv",
+                    help="likelihoods of the loss, comma-separated (hand/CrossModalHand.py:354): uv (weak supervision, the reference's default), "
+                         "uv,xyz or xyz (3D supervision: adds the Laplace likelihood of the normalised joints against the batch's pose3d)")
     args = ap.parse_args(argv)
+    from . import ops
+    mods = [m.strip() for m in args.mods.split(",") if m.strip()]
+    ops.mods_bits(mods)                               # NotImplementedError for anything but uv / xyz, before any work
     cfg = None
     if args.cfg:
         cfg = harness.load_config(args.cfg)
@@ -58,7 +65,6 @@ def main(argv=None):
         raise SystemExit("mhentropy_amd.run needs a HIP device (there is no CPU path)")
     torch.cuda.set_device(local_rank if world > 1 else 0)
     torch.manual_seed(args.seed)                      # same initial weights on every rank
-    from . import ops
     ops.rng_state(torch.device("cuda", torch.cuda.current_device()), seed=args.seed + 7919 * rank)      # the device generator of the base noise
     cd = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     if cfg is not None:
@@ -104,12 +110,12 @@ def main(argv=None):
             model.training_step_start(step)
             if args.graph and not args.test_samples:
                 from .train import GraphedStep
-                yk = {k: y[k].contiguous() for k in ("crop_uv", "vis")}          # what the loss consumes
+                yk = {k: y[k].contiguous() for k in ("crop_uv", "vis") + (("pose3d",) if "xyz" in mods else ())}     # what the loss consumes
                 if graphed is None or graphed_lr != trainer.lr:
                     # (re-)capture: GraphedStep's warm-up pass is one real step on this batch - it IS this iteration (replaying the
                     # same batch as well would apply two optimizer steps to it and advance Adam's count and the BatchNorm buffers twice)
                     sx, sy = x.clone(), {k: v.clone() for k, v in yk.items()}
-                    graphed, graphed_lr = GraphedStep(trainer, sx, sy, N=args.hyps), trainer.lr
+                    graphed, graphed_lr = GraphedStep(trainer, sx, sy, N=args.hyps, mods=mods), trainer.lr
                     out = graphed.warm_out
                 else:
                     sx.copy_(x)
@@ -117,7 +123,7 @@ def main(argv=None):
                         sy[k].copy_(v)
                     out = graphed.replay()
             else:
-                out = trainer.step(x, y, N=args.hyps, test_samples=args.test_samples)
+                out = trainer.step(x, y, N=args.hyps, test_samples=args.test_samples, mods=mods)
             with torch.no_grad():
                 total, losses, metrics = criterion(dict(out), y)
             meters["loss"].update(float(total))

@@ -1168,12 +1168,16 @@ class TrainStep:
         return Gc
 
     # ------------------------------------------------------------------ the step
-    def forward(self, x, y, noise=None, N=None, trunk_out=None):
+    def forward(self, x, y, noise=None, N=None, trunk_out=None, mods=None):
         """forward of MHEnt.get_loss (hand/network.py:760-831) keeping what the reverse pass needs.  Returns the get_loss dict.
         trunk_out (B, feat_dim) f32 (testing aid): stands in for the ResNet trunk's output, whose forward and reverse
-        passes are then skipped - the reference's golden gradients are pinned from the trunk feature on."""
+        passes are then skipped - the reference's golden gradients are pinned from the trunk feature on.
+        mods: get_loss's likelihoods (None = ['uv']; ['xyz'] / ['xyz', 'uv'] read y['pose3d'], hand/CrossModalHand.py:354)."""
         m = self.model
         N = N or m.loss_N
+        bits = ops.mods_bits(mods) if not isinstance(mods, int) else mods
+        if bits & ops.MODS_XYZ and "pose3d" not in y:
+            raise ValueError("TrainStep.forward(mods=[..., 'xyz']) needs the 3D target y['pose3d'] (B, 63)")
         B = x.shape[0] if trunk_out is None else trunk_out.shape[0]
         self.sync()           # someone else (torch.optim, load_state_dict) may have written the parameters
         f = self._trunk_forward(x.contiguous()) if trunk_out is None else trunk_out.contiguous()
@@ -1186,7 +1190,7 @@ class TrainStep:
             hs = HypothesisShards(self.dist, N)
             feat_own, feat = feat, hs.gather_rows(feat)                       # (world*B, 512): every image's conditioning feature
             feat_b = None
-            y = {"crop_uv": hs.gather_rows(y["crop_uv"]), "vis": hs.gather_rows(y["vis"])}
+            y = {k: hs.gather_rows(y[k]) for k in ("crop_uv", "vis") + (("pose3d",) if bits & ops.MODS_XYZ else ())}
             if noise is not None:
                 noise = hs.gather_hypothesis_rows(noise.reshape(N * B, 45), B)
             lo, hi = hs.hypotheses()
@@ -1232,8 +1236,13 @@ class TrainStep:
                 self._need_fallback()
                 th45, _, log_q = ops.flow_couplings(z0, cond, self.f_stream, self.f_b2, fl.mask, B, h, ops.FLOW_FORWARD)
         blob = m.mano_dec.table_blob()
-        cu, vis = y["crop_uv"].contiguous(), y["vis"].contiguous()
-        o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=("log_p", "norms"))
+        cu, vis = y["crop_uv"].contiguous() if bits & ops.MODS_UV else None, y["vis"].contiguous()
+        p3 = y["pose3d"].contiguous().float() if bits & ops.MODS_XYZ else None
+        if bits == ops.MODS_UV:
+            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=("log_p", "norms"))
+        else:
+            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=("log_p", "norms"), pose3d=p3, mods=bits,
+                                laplace_b_3d=m.b_3d)
         q_log_p, hq, log_p = ops.elbo_reduce(o["log_p"], log_q if m.entropy else None, N, B)
         if hs is not None:
             # means over the local hypotheses -> sums -> all-reduce -> means over all K; each rank reports its own images
@@ -1247,7 +1256,7 @@ class TrainStep:
         if m.entropy:
             out["h_q_z_giv_i"] = hq
         self.tape = {"f": f, "feat": feat, "feat_b": feat_b, "hd": hd, "det": det, "cond": cond, "th45": th45, "blob": blob, "cu": cu, "vis": vis,
-                     "N": N, "B": B, "trunk": trunk_out is None, "hs": hs, "B_own": B_own, "N_all": N_all, "feat_own": feat_own}
+                     "p3": p3, "mods": bits, "N": N, "B": B, "trunk": trunk_out is None, "hs": hs, "B_own": B_own, "N_all": N_all, "feat_own": feat_own}
         return out
 
     def backward(self, g_log_p=None):
@@ -1265,7 +1274,7 @@ class TrainStep:
             g_logp.copy_(hs.gather_rows(g_log_p.reshape(B_own).contiguous()))
         else:
             g_logp.copy_(g_log_p.reshape(B))
-        g45, gdet_rows = self._mano_bwd(th45, det, t["blob"], t["cu"], t["vis"], g_logp, N_all)
+        g45, gdet_rows = self._mano_bwd(th45, det, t["blob"], t["cu"], t["vis"], g_logp, N_all, t["p3"], t["mods"])
         if self.glow is not None:
             g_feat = self.glow.backward(g45, g_logp if m.entropy else None, N, B)
         else:
@@ -1322,9 +1331,9 @@ class TrainStep:
             self.G.mul_(1.0 / self.world)
             self._G_averaged = True        # optimizer_step() must not divide by world a second time
 
-    def forward_backward(self, x, y, noise=None, N=None, trunk_out=None):
+    def forward_backward(self, x, y, noise=None, N=None, trunk_out=None, mods=None):
         """forward + reverse pass of total = mean_b(-log_p[b]); fills self.G.  Returns the get_loss dict + 'total'."""
-        out = self.forward(x, y, noise=noise, N=N, trunk_out=trunk_out)
+        out = self.forward(x, y, noise=noise, N=N, trunk_out=trunk_out, mods=mods)
         self.backward()
         out["total"] = -out["log_p"].mean()
         return out
@@ -1338,13 +1347,19 @@ class TrainStep:
         self.model._trainer = self
         return self
 
-    def _mano_bwd(self, th45, det, blob, cu, vis, g_logp, N):
+    def _mano_bwd(self, th45, det, blob, cu, vis, g_logp, N, p3=None, mods=ops.MODS_UV):
         R, B = th45.shape[0], det.shape[0]
         g45 = self._buf("g45", (R, 45)); rows = self._buf("gdet_rows", (R, 16))
         from . import _lib
-        ops.check(_lib.lib().mhe_mano_joints_bwd_f32(ops._ptr(th45), ops._ptr(det), ops._ptr(cu), ops._ptr(vis), ops._ptr(blob), ops._ptr(g_logp),
-                                                     ops._ptr(g45), ops._ptr(rows), R, B, float(self.model.b_2d), float(self.model.th45_ref_alpha),
-                                                     1.0 / N, ops._stream()), "mhe_mano_joints_bwd_f32")
+        if mods == ops.MODS_UV:
+            ops.check(_lib.lib().mhe_mano_joints_bwd_f32(ops._ptr(th45), ops._ptr(det), ops._ptr(cu), ops._ptr(vis), ops._ptr(blob), ops._ptr(g_logp),
+                                                         ops._ptr(g45), ops._ptr(rows), R, B, float(self.model.b_2d), float(self.model.th45_ref_alpha),
+                                                         1.0 / N, ops._stream()), "mhe_mano_joints_bwd_f32")
+        else:
+            ops.check(_lib.lib().mhe_mano_joints_mods_bwd_f32(ops._ptr(th45), ops._ptr(det), ops._ptr(cu), ops._ptr(vis), ops._ptr(p3), ops._ptr(blob),
+                                                              ops._ptr(g_logp), ops._ptr(g45), ops._ptr(rows), R, B, int(mods), float(self.model.b_2d),
+                                                              float(self.model.b_3d), float(self.model.th45_ref_alpha), 1.0 / N, ops._stream()),
+                      "mhe_mano_joints_mods_bwd_f32")
         return g45, rows
 
     def optimizer_step(self):
@@ -1377,14 +1392,14 @@ class TrainStep:
         torch._foreach_lerp_([u.bn.running_var for u in units], var, BN_MOMENTUM)
         torch._foreach_add_([u.bn.num_batches_tracked for u in units], 1)
 
-    def step(self, x, y, noise=None, N=None, test_samples=0, temp=0.8, double_bn_update=True):
+    def step(self, x, y, noise=None, N=None, test_samples=0, temp=0.8, double_bn_update=True, mods=None):
         """one iteration of the reference's training loop (hand/CrossModalHand.py:353-361,455-470).  test_samples > 0
         adds its per-iteration metrics pass `sample(N=[n,n], temp=0.8, mods={uv,xyz,verts})` to the returned dict,
         from the conditioning feature of THIS forward.  The reference runs the encoder a second time on the same
         batch in train mode for it: same feature, but the BatchNorm running statistics advance twice per iteration -
         double_bn_update=True (default) reproduces that on the buffers, so checkpoints / eval-mode results match a
-        reference-trained model."""
-        out = self.forward_backward(x, y, noise=noise, N=N)
+        reference-trained model.  mods: get_loss's likelihoods, as in forward()."""
+        out = self.forward_backward(x, y, noise=noise, N=N, mods=mods)
         if test_samples:
             if double_bn_update and self.tape["trunk"]:
                 self.second_bn_update()
@@ -1401,17 +1416,18 @@ class GraphedStep:
     (RCCL, async_op: it runs on the communicator's stream under the next graph's kernels), the next graph starts; the last
     graph (norm, clip, Adam, operand re-pack) is launched after the waits.  Six graphs and four collectives per step."""
 
-    def __init__(self, ts, x, y, noise=None, N=None, test_samples=0, criterion=None):
+    def __init__(self, ts, x, y, noise=None, N=None, test_samples=0, criterion=None, mods=None):
         """test_samples / criterion: the reference's whole iteration (hand/CrossModalHand.py:349-361,452-470) in the graph - the
         metrics pass sample(N=[n,n], temp=0.8) from this forward's feature and `criterion(out, y)` (MHEntLoss: 14 metrics);
-        self.out then carries 'criterion' = (total, losses, metrics)"""
+        self.out then carries 'criterion' = (total, losses, metrics).  mods: get_loss's likelihoods (TrainStep.forward); with 'xyz'
+        the graphs read y['pose3d'] - a new target is copied into that static tensor like the rest of the batch"""
         if ts.shard_hypotheses:
             raise NotImplementedError("GraphedStep: the hypothesis-sharded forward has collectives inside the forward pass")
         self.ts, self.graphs, self.actions = ts, [], []
         _step = ts.step
 
         def step(x, y, noise=None, N=None):
-            out = _step(x, y, noise=noise, N=N, test_samples=test_samples)
+            out = _step(x, y, noise=noise, N=N, test_samples=test_samples, mods=mods)
             if criterion is not None:
                 with torch.no_grad():
                     out["criterion"] = criterion(dict(out), y)
@@ -1468,8 +1484,8 @@ class GraphedStep:
 class _LossFn(torch.autograd.Function):
     """MHEnt.get_loss as one autograd node: forward = TrainStep.forward, backward = TrainStep.backward(d loss / d log_p)."""
     @staticmethod
-    def forward(ctx, trainer, x, y, N, noise, *params):
-        out = trainer.forward(x, y, noise=noise, N=N)
+    def forward(ctx, trainer, x, y, N, noise, mods, *params):
+        out = trainer.forward(x, y, noise=noise, N=N, mods=mods)
         ctx.trainer, ctx.keys = trainer, list(out)
         vals = tuple(out[k] for k in ctx.keys)
         ctx.mark_non_differentiable(*[v for k, v in zip(ctx.keys, vals) if k != "log_p"])
@@ -1480,11 +1496,11 @@ class _LossFn(torch.autograd.Function):
         tr = ctx.trainer
         g = grads[ctx.keys.index("log_p")]
         tr.backward(None if g is None else g.contiguous().float())
-        return (None, None, None, None, None) + tuple(tr.grad_of(p) for p in tr._params)
+        return (None, None, None, None, None, None) + tuple(tr.grad_of(p) for p in tr._params)
 
 
-def differentiable_get_loss(trainer, x, y, N=None, noise=None):
-    vals = _LossFn.apply(trainer, x, y, N, noise, *trainer._params)
+def differentiable_get_loss(trainer, x, y, N=None, noise=None, mods=None):
+    vals = _LossFn.apply(trainer, x, y, N, noise, mods, *trainer._params)
     return dict(zip(_LossFn_keys(trainer), vals))
 
 
