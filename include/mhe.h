@@ -430,6 +430,26 @@ int mhe_nchw_to_nhwc_pad(const float *x_nchw, void *y, int B, int C, int Cp, int
 int mhe_metrics_f32(const float *xyz, const float *uv, const float *pose3d, const float *scale,
                     const float *crop_uv, const float *vis, float *out, int N, int B, void *stream);
 
+/* the aligned evaluation (MHEntLoss with `aligned`, hand/criteria.py:62-68,93-96,141): as mhe_metrics_f32, but the 3D error rows
+ * (sample, vis, vis_mean, invis) are taken of xyz_err [N,B,63] and the 3D spread rows (sample_std, vis_std, invis_std) of
+ * xyz_spread [N,B,63] - the Procrustes-aligned and the unaligned joints.  With xyz_err == xyz_spread the values are mhe_metrics_f32's.
+ * Every pointer must be device memory; out must not overlap an input (MHE_ERR_ARG otherwise). */
+int mhe_metrics_split_f32(const float *xyz_err, const float *xyz_spread, const float *uv, const float *pose3d, const float *scale,
+                          const float *crop_uv, const float *vis, float *out, int N, int B, void *stream);
+
+/* Procrustes alignment with scale (hand/utils.py:502-525 align_w_scale, scipy.linalg.orthogonal_procrustes) of every hypothesis
+ * row pred [N,B,P*3] (sample-major, P points x 3 coordinates, any length unit) to its image's target [B,P*3], 0 < P <= 1024:
+ *   t1 = mean(A), s1 = |A - t1|_F + 1e-8, A0 = (A - t1) / s1;   t2, s2, B0 likewise of the row;
+ *   A0^T B0 = U S V^T, R = U V^T (no determinant correction: det R = -1 is kept), s = trace(S);
+ *   out [N,B,P*3] = (B0 R^T) * s * s1 + t1   (the target's unit).
+ * R [N,B,9] (row-major 3x3) and s [N,B] (dimensionless) are written when non-NULL.  M = A0^T B0 is accumulated from centred rows in
+ * f32, the polar factor is taken in f64; M = 0 (e.g. an all-zero target) gives s = 0 and out = t1.  ws: a workspace of
+ * mhe_procrustes_workspace_floats(B, P) floats (the target statistics, computed once per image).  Every pointer must be device
+ * memory; out, R, s and ws must not overlap one another or the inputs (MHE_ERR_ARG otherwise). */
+size_t mhe_procrustes_workspace_floats(int B, int P);
+int mhe_procrustes_align_f32(const float *pred, const float *target, float *out, float *R, float *s, float *ws, size_t ws_floats,
+                             int N, int B, int P, void *stream);
+
 /* Top-Q hypothesis selection of MHEnt.sample (hand/network.py:866-871): per image b keep the Q rows of
  * highest score[n*B+b] in descending order and gather them: idx_out [Q,B] (hypothesis index n),
  * rows_out [Q*B, D] sample-major.  rows [N*B, D] is the flow sample th45. */

@@ -170,6 +170,9 @@ SIGNATURES = {
     "mhe_lbs_skin_mfma_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "mhe_topk_gather_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "mhe_metrics_f32": (_i, [_p] * 7 + [_i, _i, _p]),
+    "mhe_metrics_split_f32": (_i, [_p] * 8 + [_i, _i, _p]),
+    "mhe_procrustes_workspace_floats": (_sz, [_i, _i]),
+    "mhe_procrustes_align_f32": (_i, [_p] * 6 + [_sz, _i, _i, _i, _p]),
 }
 
 _lib = None

@@ -31,6 +31,22 @@ static inline int check_launch(const char *what) {
         }                                      \
     } while (0)
 
+// argument checks of entry points that must refuse, not fault on, memory the GPU cannot use (host pointers) or aliased buffers
+static inline bool on_device(const void *p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();               // an unregistered host pointer: clear the error the query left behind
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+// byte ranges [a, a + na) and [b, b + nb) do not overlap (a NULL pointer overlaps nothing)
+static inline bool disjoint(const void *a, size_t na, const void *b, size_t nb) {
+    if (!a || !b) return true;
+    const char *x = static_cast<const char *>(a), *y = static_cast<const char *>(b);
+    return x + na <= y || y + nb <= x;
+}
+
 // wave-local ordering of LDS traffic: all 64 lanes run in lockstep and one
 // wave's DS operations complete in order, so only the compiler needs fencing.
 __device__ __forceinline__ void wave_sync() {

@@ -25,9 +25,12 @@ constexpr int CH = 256;                 // hypotheses per chunk: 256 x 63 floats
 constexpr int LDS_FLOATS = CH * K * 3 + CH * K + 4 * 64 * 2 + 4 * 64 + 64 * 4;
 
 // out[14][B]: for sup in (3d, 2d): sample, sample_std, vis, vis_std, vis_mean, invis, invis_std
-template <int D>
+// SPLIT: the error rows (sample, vis, vis_mean, invis) read `coord`, the spread rows (*_std) read `coord_sp` - the aligned evaluation
+// (criteria.py:63-68,141: errors of the Procrustes-aligned joints, spread of the unaligned ones).  SPLIT = false is the one-array form.
+template <int D, bool SPLIT = false>
 __device__ __forceinline__ void one_sup(float *lds, const float *__restrict__ coord, const float *gt_b, float cscale, float escale, int N, int B,
-                                        int b, const float *w, const float *nvis, const float *nvalid, float *__restrict__ out) {
+                                        int b, const float *w, const float *nvis, const float *nvalid, float *__restrict__ out,
+                                        const float *__restrict__ coord_sp = nullptr) {
     constexpr int KD = K * D;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     float *buf = lds;                               // [CH][KD] coordinates
@@ -67,6 +70,13 @@ __device__ __forceinline__ void one_sup(float *lds, const float *__restrict__ co
             }
         }
         __syncthreads();
+        if (SPLIT) {                                // (b) sums the spread rows: those of the other array
+            for (int i = tid; i < cn * KD; i += 256) {
+                const int n = i / KD, j = i - n * KD;
+                buf[n * KD + j] = coord_sp[((size_t)(n0 + n) * B + b) * KD + j];
+            }
+            __syncthreads();
+        }
         if (lane < KD) for (int n = wave; n < cn; n += 4) csum += buf[n * KD + lane] * cscale;          // (b)
         if (lane < K) for (int n = wave; n < cn; n += 4) esum += eb[n * K + lane];
     }
@@ -91,7 +101,7 @@ __device__ __forceinline__ void one_sup(float *lds, const float *__restrict__ co
                 __syncthreads();
                 for (int i = tid; i < cn * KD; i += 256) {
                     const int n = i / KD, j = i - n * KD;
-                    buf[n * KD + j] = coord[((size_t)(n0 + n) * B + b) * KD + j];
+                    buf[n * KD + j] = (SPLIT ? coord_sp : coord)[((size_t)(n0 + n) * B + b) * KD + j];
                 }
                 __syncthreads();
             }
@@ -137,10 +147,12 @@ __device__ __forceinline__ void one_sup(float *lds, const float *__restrict__ co
     __syncthreads();
 }
 
+// SPLIT: xyz_sp carries the joints of the 3D spread rows (one_sup)
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void metrics_kernel(const float *__restrict__ xyz, const float *__restrict__ uv,
                                                       const float *__restrict__ pose3d, const float *__restrict__ scale,
                                                       const float *__restrict__ crop_uv, const float *__restrict__ vis,
-                                                      float *__restrict__ out, int N, int B) {
+                                                      float *__restrict__ out, int N, int B, const float *__restrict__ xyz_sp) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ float wk[3 * K], gt[K * 3], hdr[8];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
@@ -168,7 +180,7 @@ __global__ __launch_bounds__(256) void metrics_kernel(const float *__restrict__ 
     __syncthreads();
     const float nvis[3] = {hdr[0], hdr[1], hdr[2]}, nvalid[3] = {hdr[3], hdr[4], hdr[5]};
     const float sc = scale[b];
-    one_sup<3>(lds, xyz, gt, sc, sc, N, B, b, wk, nvis, nvalid, out);
+    one_sup<3, SPLIT>(lds, xyz, gt, sc, sc, N, B, b, wk, nvis, nvalid, out, xyz_sp);
     // 2D ground truth in pixels: (crop_uv + 1) / 2 * 256   (criteria.py:96)
     if (tid < K * 2) gt[tid] = (crop_uv[(size_t)b * K * 2 + tid] + 1.f) / 2.f * 256.f;
     __syncthreads();
@@ -183,14 +195,35 @@ extern "C" int mhe_metrics_f32(const float *xyz, const float *uv, const float *p
                                const float *crop_uv, const float *vis, float *out, int N, int B, void *stream) {
     MHE_REQUIRE(xyz && uv && pose3d && scale && crop_uv && vis && out && N > 0 && B > 0, "mhe_metrics_f32: bad arguments");
     static const bool set = [] {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(metrics::metrics_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(metrics::metrics_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   metrics::LDS_FLOATS * (int)sizeof(float));
         return true;
     }();
     (void)set;
-    hipLaunchKernelGGL(metrics::metrics_kernel, dim3(B), dim3(256), metrics::LDS_FLOATS * sizeof(float), (hipStream_t)stream, xyz, uv, pose3d,
-                       scale, crop_uv, vis, out, N, B);
+    hipLaunchKernelGGL(metrics::metrics_kernel<false>, dim3(B), dim3(256), metrics::LDS_FLOATS * sizeof(float), (hipStream_t)stream, xyz, uv, pose3d,
+                       scale, crop_uv, vis, out, N, B, nullptr);
     return check_launch("metrics_kernel");
+}
+
+extern "C" int mhe_metrics_split_f32(const float *xyz_err, const float *xyz_spread, const float *uv, const float *pose3d, const float *scale,
+                                     const float *crop_uv, const float *vis, float *out, int N, int B, void *stream) {
+    MHE_REQUIRE(xyz_err && xyz_spread && uv && pose3d && scale && crop_uv && vis && out && N > 0 && B > 0, "mhe_metrics_split_f32: bad arguments");
+    MHE_REQUIRE(on_device(xyz_err) && on_device(xyz_spread) && on_device(uv) && on_device(pose3d) && on_device(scale) && on_device(crop_uv) &&
+                on_device(vis) && on_device(out), "mhe_metrics_split_f32: every pointer must be device memory");
+    const size_t f = sizeof(float), no = (size_t)14 * B * f, nx = (size_t)N * B * 63 * f;
+    MHE_REQUIRE(disjoint(out, no, xyz_err, nx) && disjoint(out, no, xyz_spread, nx) && disjoint(out, no, uv, (size_t)N * B * 42 * f) &&
+                disjoint(out, no, pose3d, (size_t)B * 63 * f) && disjoint(out, no, scale, (size_t)B * f) &&
+                disjoint(out, no, crop_uv, (size_t)B * 42 * f) && disjoint(out, no, vis, (size_t)B * 21 * f),
+                "mhe_metrics_split_f32: out must not overlap an input");
+    static const bool set = [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(metrics::metrics_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  metrics::LDS_FLOATS * (int)sizeof(float));
+        return true;
+    }();
+    (void)set;
+    hipLaunchKernelGGL(metrics::metrics_kernel<true>, dim3(B), dim3(256), metrics::LDS_FLOATS * sizeof(float), (hipStream_t)stream, xyz_err, uv,
+                       pose3d, scale, crop_uv, vis, out, N, B, xyz_spread);
+    return check_launch("metrics_kernel<split>");
 }
 
 // ---------------------------------------------------------------------------

@@ -469,6 +469,49 @@ def metrics(xyz, uv, pose3d, scale, crop_uv, vis):
     return out
 
 
+def metrics_split(xyz_err, xyz_spread, uv, pose3d, scale, crop_uv, vis):
+    """metrics() with the 3D error rows taken of xyz_err and the 3D spread rows of xyz_spread (both [N,B,63]): the aligned
+    evaluation passes the Procrustes-aligned and the unaligned joints (include/mhe.h, mhe_metrics_split_f32)"""
+    N, B = xyz_err.shape[:2]
+    _chk(xyz_err, torch.float32, "metrics_split.xyz_err", (N, B, 63)); _chk(xyz_spread, torch.float32, "metrics_split.xyz_spread", (N, B, 63))
+    _chk(uv, torch.float32, "metrics_split.uv", (N, B, 42))
+    _chk(pose3d, torch.float32, "metrics_split.pose3d", (B, 63)); _chk(scale, torch.float32, "metrics_split.scale", (B,))
+    _chk(crop_uv, torch.float32, "metrics_split.crop_uv", (B, 42)); _chk(vis, torch.float32, "metrics_split.vis", (B, 21))
+    out = torch.empty(14, B, device=xyz_err.device, dtype=torch.float32)
+    check(_lib.lib().mhe_metrics_split_f32(_ptr(xyz_err), _ptr(xyz_spread), _ptr(uv), _ptr(pose3d), _ptr(scale), _ptr(crop_uv), _ptr(vis),
+                                           _ptr(out), N, B, _stream()), "mhe_metrics_split_f32")
+    return out
+
+
+def procrustes_align(pred, target, want_transform=False):
+    """Procrustes alignment with scale of every hypothesis to its image's target (hand/utils.py:502-525 align_w_scale, without the
+    determinant correction that scipy's orthogonal_procrustes also leaves out).  pred [N,B,...] and target [B,...] hold P*3
+    coordinates per row (joints [N,B,63], meshes [N,B,2334] or [N,B,778,3]); returns a new tensor shaped like pred, in the
+    target's unit.  want_transform: also return R [N,B,3,3] and s [N,B] of each row (M = A0^T B0 = U S V^T, R = U V^T, s = tr S)."""
+    if not isinstance(pred, torch.Tensor) or pred.dim() < 3:
+        raise _lib.MheError("procrustes_align.pred: expected an [N,B,...] tensor")
+    N, B = pred.shape[:2]
+    F = pred[0, 0].numel()
+    if F % 3 or F == 0:
+        raise _lib.MheError(f"procrustes_align.pred: {F} coordinates per row is not P x 3")
+    _chk(pred, torch.float32, "procrustes_align.pred")
+    _chk(target, torch.float32, "procrustes_align.target")
+    if target.dim() < 1 or target.shape[0] != B or target[0].numel() != F:
+        raise _lib.MheError(f"procrustes_align.target: expected [B={B}, ...] with {F} coordinates per image, got {tuple(target.shape)}")
+    if target.device != pred.device:
+        raise _lib.MheError("procrustes_align: pred and target are on different devices")
+    P = F // 3
+    L = _lib.lib()
+    out = torch.empty_like(pred)
+    nws = L.mhe_procrustes_workspace_floats(B, P)
+    ws = torch.empty(nws, device=pred.device, dtype=torch.float32)
+    R = torch.empty(N, B, 3, 3, device=pred.device, dtype=torch.float32) if want_transform else None
+    s = torch.empty(N, B, device=pred.device, dtype=torch.float32) if want_transform else None
+    check(L.mhe_procrustes_align_f32(_ptr(pred), _ptr(target), _ptr(out), _ptr(R), _ptr(s), _ptr(ws), nws, N, B, P, _stream()),
+          "mhe_procrustes_align_f32")
+    return (out, R, s) if want_transform else out
+
+
 def conv2d_nhwc(x, w, KH, KW, stride, pad, in_scale=None, in_shift=None, relu_in=False, out_scale=None,
                 out_shift=None, residual=None, relu_out=False, stats=None, out=None, mask=None, bn=None, tile=0, res_half=False, xcat=None,
                 mask_bits=None):

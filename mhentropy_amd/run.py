@@ -46,6 +46,9 @@ def main(argv=None):
                     help="feed the step from DECODED synthetic HO3D samples through the GPU input pipeline (ho3d_dataloader.HO3DBatchPipeline: "
                          "crop, augmentation, visibility, compute_st; hand/dataloader/ho3d_dataloader.py:272-459) instead of ready-made batches; "
                          "image size is then 256")
+    ap.add_argument("--aligned", action="store_true",
+                    help="report Procrustes-aligned 3D metrics (MHEntLoss(aligned=True), the reference's criteria.py:62-87): joints aligned to "
+                         "pose3d, meshes to the target's verts where the batch carries them (--input-pipeline)")
     ap.add_argument("--mods", default="uv",
                     help="likelihoods of the loss, comma-separated (hand/CrossModalHand.py:354): uv (weak supervision, the reference's default), "
                          "uv,xyz or xyz (3D supervision: adds the Laplace likelihood of the normalised joints against the batch's pose3d)")
@@ -83,7 +86,7 @@ def main(argv=None):
             ops.rng_set_state(torch.device("cuda", torch.cuda.current_device()), ck["mhe_rng_state"])
     scalars = harness.ScalarLog(args.scalars) if (args.scalars and rank == 0) else None
     trainer = TrainStep(model, lr=args.lr, max_norm=1.0, dist=dist)
-    criterion = MHEntLoss()
+    criterion = MHEntLoss(aligned=args.aligned)
     meters = {"loss": harness.AverageMeter(), "epe3d": harness.AverageMeter(), "epe2d": harness.AverageMeter()}
     step, log = 0, []
     graphed, graphed_lr, sx, sy = None, None, None, None
