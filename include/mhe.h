@@ -822,6 +822,31 @@ int mhe_glow_affine_f64(const void *param_ptrs, int layers, int features, float 
 int mhe_glow_reparam_bwd_f64(const void *g_ainv_ptrs, const void *g_cinv_ptrs, const float *g_log_p, int n_log_p, float q_sign, int layers,
                              int features, const double *workspace, const void *grad_ptrs, void *stream);
 
+/* The same re-parameterisation for a WIDE flow variable (csrc/glow_affine_wide.hip; 2 <= features <= 256, the 144-D body pose): the float64
+ * working set lives in a global workspace of mhe_glow_affine_wide_workspace_doubles(layers, features) doubles (it does not fit in LDS), phases
+ * are separate launches with many workgroups per layer.  param_ptrs as for mhe_glow_affine_f64, eps (LULinear's) in float64; outputs f32 zero-padded to Dp = ceil64(features):
+ * A, A^-1, (A^-1)^T [layers][Dp][Dp], c, c^-1 [layers][Dp], const_parts [layers].  The reverse takes dL/dA^-1 [layers][Dp][Dp], dL/dc^-1
+ * [layers][Dp] and dL/dlog q of every row (g_log_q [n_log_q], may be NULL with n_log_q = 0; S = their sum), reads the workspace of the forward
+ * call (and overwrites its scratch part) and writes float64 gradients, mhe_glow_affine_wide_grad_doubles(layers, features) in all: per layer
+ * [log_scale D | shift D | lower_entries D(D-1)/2 | upper_entries D(D-1)/2 | unconstrained_upper_diag D | bias D]. */
+size_t mhe_glow_affine_wide_workspace_doubles(int layers, int features);
+size_t mhe_glow_affine_wide_grad_doubles(int layers, int features);
+int mhe_glow_affine_wide_f64(const void *param_ptrs, int layers, int features, double eps, float *A, float *c, float *Ainv, float *AinvT,
+                             float *cinv, float *const_parts, double *workspace, void *stream);
+int mhe_glow_affine_wide_bwd_f64(const float *g_ainv, const float *g_cinv, const float *g_log_q, long n_log_q, int layers, int features,
+                                 double *workspace, double *grads, void *stream);
+/* Reverse of the INVERSE coupling (mhe_glow_coupling_f32 with inverse = 1) at row pitches ld (variable) / ldp (parameter rows), multiples of
+ * 64 up to 256, 2 n_transform <= ldp: g_v [R][ld], g_params [R][ldp] = [d shift | d unconstrained scale | 0]; g_log_q [R] = dL/dlog q per row
+ * (NULL: none).  Formulas: csrc/glow.hip. */
+int mhe_glow_coupling_inv_bwd_wide_f32(const float *v, const float *params, const float *g_y, const float *g_log_q, float *g_v,
+                                       float *g_params, long R, int dim, int first, int n_transform, int ld, int ldp, void *stream);
+/* out[g * out_stride + c] (+)= sum_{n < N} rows[(g N + n) C + c]: per-image sums of batch-major rows (r = b N + n), in n order */
+int mhe_sum_row_blocks_f32(const float *rows, float *out, int groups, int N, int C, long out_stride, int accumulate, void *stream);
+/* Reverse of the posed joints of mhe_lbs_pose_f32 (csrc/body.hip; one wavefront per hypothesis, J <= 32, any tree with parents[j] < j):
+ * g_joints [R,J,3] -> g_rotmats [R,J,3,3], g_betas [R,nb] (through j_template + j_shapedirs beta).  Follow with mhe_rot6d_to_rotmat_bwd_f32. */
+int mhe_lbs_pose_bwd_f32(const float *rotmats, const float *betas, const float *j_template, const float *j_shapedirs, const int *parents,
+                         const float *g_joints, float *g_rotmats, float *g_betas, int R, int J, int nb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,12 @@ SIGNATURES = {
     "mhe_glow_affine_workspace_doubles": (_sz, [_i, _i]),
     "mhe_glow_affine_f64": (_i, [_p, _i, _i, _f] + [_p] * 7 + [_p]),
     "mhe_glow_reparam_bwd_f64": (_i, [_p, _p, _p, _i, _f, _i, _i, _p, _p, _p]),
+    "mhe_glow_affine_wide_workspace_doubles": (_sz, [_i, _i]),
+    "mhe_glow_affine_wide_grad_doubles": (_sz, [_i, _i]),
+    "mhe_glow_affine_wide_f64": (_i, [_p, _i, _i, _d] + [_p] * 7 + [_p]),
+    "mhe_glow_affine_wide_bwd_f64": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p]),
+    "mhe_glow_coupling_inv_bwd_wide_f32": (_i, [_p] * 6 + [_l, _i, _i, _i, _i, _i, _p]),
+    "mhe_sum_row_blocks_f32": (_i, [_p, _p, _i, _i, _i, _l, _i, _p]),
     "mhe_mano_regress_joints_f32": (_i, [_p, _p, _p, _i, _p]),
     "mhe_elbo_reduce_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),
     "mhe_conv2d_nhwc": (_i, [C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
@@ -163,6 +169,7 @@ SIGNATURES = {
     "mhe_rot6d_to_rotmat_bwd_f32": (_i, [_p, _p, _p, _l, _p]),
     "mhe_lbs_workspace_floats": (_sz, [_i, _i, _i]),
     "mhe_lbs_pose_f32": (_i, [_p] * 7 + [_i, _i, _i, _p]),
+    "mhe_lbs_pose_bwd_f32": (_i, [_p] * 8 + [_i, _i, _i, _p]),
     "mhe_lbs_skin_f32": (_i, [_p] * 6 + [_i, _i, _i, _i, _i, _f, _p]),
     "mhe_lbs_split_floats": (_sz, [_i, _i, _i]),
     "mhe_lbs_split_tables_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),

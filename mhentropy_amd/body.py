@@ -136,7 +136,23 @@ class BodyFlowHead(nn.Module):
 
     def forward(self, feats, num_samples, betas=None, noise=None, hyp_slice=None, want_verts=True):
         """feats (B,F) -> pose6d (B,K,6J), log_prob (B,K), vertices (B,K,NV,3), joints (B,K,J,3); hyp_slice = (lo, hi) decodes only
-        hypotheses lo..hi-1 of every image (the hypothesis-sharded form)"""
+        hypotheses lo..hi-1 of every image (the hypothesis-sharded form).
+
+        Differentiable when grad is enabled and `feats` or `betas` require grad, or the head is in train mode with flow parameters that require
+        grad (one autograd node, _HeadFn, whose backward is the hand-written reverse pass; an eval-mode call on plain inputs stays the
+        inference pass and returns plain tensors): log_prob, pose6d and joints carry gradients to every flow parameter, feats and betas.
+        Refused there (NotImplementedError): a non-zero gradient on vertices, compute_dtype bfloat16, dropout p > 0 in train mode."""
+        params = [p for p in self.flow.parameters()]
+        if torch.is_grad_enabled() and ((self.training and any(p.requires_grad for p in params)) or feats.requires_grad
+                                        or (betas is not None and betas.requires_grad)):
+            if noise is None:
+                noise = ops.randn(feats.shape[0] * num_samples, self.flow.features, feats.device).view(feats.shape[0], num_samples, self.flow.features)
+            lo, hi = hyp_slice if hyp_slice is not None else (0, num_samples)
+            vals = _HeadFn.apply(self, feats, betas, noise, num_samples, lo, hi, want_verts, *params)
+            res = {"pose6d": vals[0], "log_prob": vals[1], "joints": vals[2]}
+            if want_verts:
+                res["vertices"] = vals[3]
+            return res
         B = feats.shape[0]
         pose, logp, _ = self.flow.sample_and_log_prob(num_samples, noise=noise, context=feats)
         lo, hi = hyp_slice if hyp_slice is not None else (0, num_samples)
@@ -148,3 +164,62 @@ class BodyFlowHead(nn.Module):
         if want_verts:
             res["vertices"] = out["vertices"].view(B, hi - lo, self.body.NV, 3)
         return res
+
+
+def lbs_pose_bwd(layer, rotmats, betas, g_joints):
+    """reverse of BodyLayer's posed joints: g_joints (R,J,3) -> (g_rotmats (R,J,3,3), g_betas (R,nb)) (mhe_lbs_pose_bwd_f32)"""
+    R = rotmats.shape[0]
+    ops._chk(rotmats, torch.float32, "lbs_bwd.rotmats", (R, layer.J, 3, 3)); ops._chk(betas, torch.float32, "lbs_bwd.betas", (R, layer.nb))
+    ops._chk(g_joints, torch.float32, "lbs_bwd.g_joints", (R, layer.J, 3))
+    g_rot, g_bt = torch.empty_like(rotmats), torch.empty_like(betas)
+    ops.check(_lib.lib().mhe_lbs_pose_bwd_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(layer._jt), ops._ptr(layer._jsd), ops._ptr(layer.parents),
+                                              ops._ptr(g_joints), ops._ptr(g_rot), ops._ptr(g_bt), R, layer.J, layer.nb, ops._stream()), "mhe_lbs_pose_bwd_f32")
+    return g_rot, g_bt
+
+
+class _HeadFn(torch.autograd.Function):
+    """BodyFlowHead.forward as one autograd node: forward = the f32 sampling pass with a tape (glow_grad.sample_with_tape, bit-identical to the
+    no-grad pass) + the body decode; backward = joints -> rotations -> 6D poses (mhe_lbs_pose_bwd_f32, mhe_rot6d_to_rotmat_bwd_f32) added to
+    dL/dpose6d on the slice's rows, then the flow's reverse pass (glow_grad.backward).  Vertices are returned but have no reverse pass."""
+    @staticmethod
+    def forward(ctx, head, feats, betas, noise, K, lo, hi, want_verts, *params):
+        from . import glow_grad
+        B, D, nb, J = feats.shape[0], head.flow.features, head.body.nb, head.body.J
+        x, lp, tape = glow_grad.sample_with_tape(head.flow, noise.reshape(B * K, D).contiguous(), feats.contiguous(), K)
+        pose = x.view(B, K, D)
+        p = pose[:, lo:hi].reshape(B * (hi - lo), D).contiguous()
+        bt = betas.contiguous() if betas is not None else torch.zeros(B, nb, device=feats.device)
+        bt = bt[:, None, :].expand(B, hi - lo, nb).reshape(B * (hi - lo), nb).contiguous()
+        out = head.body(bt, pose6d=p, want_verts=want_verts)
+        ctx.head, ctx.tape, ctx.shape, ctx.has_betas = head, tape, (B, K, lo, hi), betas is not None
+        ctx.save_for_backward(p, out["rotmats"], bt)
+        ctx.set_materialize_grads(False)
+        joints = out["joints"].view(B, hi - lo, J, 3)
+        verts = out["vertices"].view(B, hi - lo, head.body.NV, 3) if want_verts else None
+        return (pose, lp.view(B, K), joints) + ((verts,) if want_verts else ())
+
+    @staticmethod
+    def backward(ctx, g_pose, g_lp, g_joints, *g_verts):
+        from . import glow_grad
+        if g_verts and g_verts[0] is not None and bool(g_verts[0].ne(0).any()):
+            raise NotImplementedError("BodyFlowHead: no reverse pass through the vertex skinning - a loss on 'vertices' cannot be differentiated "
+                                      "(use 'joints' / 'pose6d')")
+        head, (B, K, lo, hi) = ctx.head, ctx.shape
+        p, rotmats, bt = ctx.saved_tensors
+        D, nb, J = head.flow.features, head.body.nb, head.body.J
+        gx = torch.zeros(B, K, D, device=p.device) if g_pose is None else g_pose.float().contiguous().clone()
+        g_betas = None
+        if g_joints is not None:
+            n = hi - lo
+            g_rot, g_bt = lbs_pose_bwd(head.body, rotmats, bt, g_joints.float().reshape(B * n, J, 3).contiguous())
+            g6 = rot6d_to_rotmat_bwd(p.view(B * n, J, 6), g_rot)
+            gx[:, lo:hi] += g6.view(B, n, D)
+            if ctx.has_betas and ctx.needs_input_grad[2]:
+                g_betas = ops.sum_row_blocks(g_bt, B, n)
+        elif ctx.has_betas and ctx.needs_input_grad[2]:
+            g_betas = torch.zeros(B, nb, device=p.device)
+        glp = None if g_lp is None else g_lp.float().reshape(B * K).contiguous()
+        grads, g_feats = glow_grad.backward(head.flow, ctx.tape, gx.view(B * K, D), glp)
+        ctx.tape = None
+        params = list(head.flow.parameters())
+        return (None, g_feats if ctx.needs_input_grad[1] else None, g_betas, None, None, None, None, None) + tuple(grads.get(q) for q in params)

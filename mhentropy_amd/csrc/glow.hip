@@ -108,6 +108,45 @@ __global__ __launch_bounds__(256) void coupling_inv_bwd_kernel(const float *__re
     g_v[r * 64 + lane] = lane < dim ? gv : 0.f;
 }
 
+// ... the same for a wide flow variable (the 144-D body pose): row pitches ld (variable) / ldp (parameter rows), multiples of 64 up to 256, and
+// dL/dlog q given PER ROW (g_logq[r], the rows' own log-probability gradient; NULL: none).  g_prm [R, ldp] = [d shift (T) | d us (T) | 0].
+__global__ __launch_bounds__(256) void coupling_inv_bwd_wide_kernel(const float *__restrict__ v, const float *__restrict__ prm,
+                                                                    const float *__restrict__ g_y, const float *__restrict__ g_logq,
+                                                                    float *__restrict__ g_v, float *__restrict__ g_prm, long R, int dim, int first,
+                                                                    int T, int ld, int ldp) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const float a_q = g_logq ? g_logq[r] : 0.f;
+    for (int c = 2 * T + lane; c < ldp; c += 64) g_prm[r * ldp + c] = 0.f;
+    for (int c = lane; c < ld; c += 64) {
+        const float gy = c < dim ? g_y[r * ld + c] : 0.f;
+        float gv = gy;
+        const int j = (c - first) >> 1;
+        if (c < dim && c >= first && ((c - first) & 1) == 0 && j < T) {
+            const float shift = prm[r * ldp + j], us = prm[r * ldp + T + j];
+            const float sig = 1.f / (1.f + expf(-(us + 2.f))), scale = sig + 1e-3f;
+            gv = gy / scale;
+            g_prm[r * ldp + j] = -gv;
+            g_prm[r * ldp + T + j] = (-gv * (v[r * ld + c] - shift) / scale + a_q / scale) * sig * (1.f - sig);
+        }
+        g_v[r * ld + c] = c < dim ? gv : 0.f;
+    }
+}
+
+// out[g * out_stride + c] (+)= sum_{n < N} rows[(g N + n) C + c]: per-image sums of batch-major rows (r = b N + n), summed in n order
+__global__ __launch_bounds__(256) void sum_row_blocks_kernel(const float *__restrict__ rows, float *__restrict__ out, int G, int N, int C,
+                                                             long out_stride, int accumulate) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)G * C) return;
+    const int g = (int)(i / C), c = (int)(i % C);
+    const float *p = rows + (size_t)g * N * C + c;
+    float a = 0.f;
+    for (int n = 0; n < N; ++n) a += p[(size_t)n * C];
+    float *o = out + (size_t)g * out_stride + c;
+    *o = accumulate ? *o + a : a;
+}
+
 // residual block tail reverse: H_out = H_in + T3 * sigmoid(gate[image]):  g_t3 = g_h * s,  g_gate_rows = g_h * T3 * s (1 - s)
 template <typename TT>       // storage type of t3 and g_t3 (operands of the bf16 products in performance mode); g_gate stays f32
 __global__ __launch_bounds__(256) void glu_bwd_kernel(const float *__restrict__ g_h, const TT *__restrict__ t3,
@@ -317,6 +356,27 @@ extern "C" int mhe_glow_coupling_inv_bwd_f32(const float *v, const float *params
     hipLaunchKernelGGL(glow::coupling_inv_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, v, params, g_y, g_log_p,
                        q_weight, g_v, g_params, R, B, dim, first, n_transform);
     return check_launch("coupling_inv_bwd_kernel");
+}
+
+extern "C" int mhe_glow_coupling_inv_bwd_wide_f32(const float *v, const float *params, const float *g_y, const float *g_log_q, float *g_v,
+                                                  float *g_params, long R, int dim, int first, int n_transform, int ld, int ldp, void *stream) {
+    MHE_REQUIRE(R > 0 && dim > 0 && ld % 64 == 0 && ld >= dim && ld <= 256 && ldp % 64 == 0 && ldp <= 256 && (first == 0 || first == 1) &&
+                    n_transform > 0 && first + 2 * (n_transform - 1) < dim && 2 * n_transform <= ldp && R <= (1l << 40) / ld,
+                "mhe_glow_coupling_inv_bwd_wide_f32: bad arguments (R=%ld dim=%d first=%d T=%d ld=%d ldp=%d)", R, dim, first, n_transform, ld, ldp);
+    MHE_REQUIRE(on_device(v) && on_device(params) && on_device(g_y) && on_device(g_v) && on_device(g_params) && (!g_log_q || on_device(g_log_q)),
+                "mhe_glow_coupling_inv_bwd_wide_f32: every buffer must be device memory");
+    hipLaunchKernelGGL(glow::coupling_inv_bwd_wide_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, v, params, g_y, g_log_q,
+                       g_v, g_params, R, dim, first, n_transform, ld, ldp);
+    return check_launch("coupling_inv_bwd_wide_kernel");
+}
+
+extern "C" int mhe_sum_row_blocks_f32(const float *rows, float *out, int groups, int N, int C, long out_stride, int accumulate, void *stream) {
+    MHE_REQUIRE(groups > 0 && N > 0 && C > 0 && out_stride >= C && (long)groups * C < (1l << 31), "mhe_sum_row_blocks_f32: bad arguments");
+    MHE_REQUIRE(on_device(rows) && on_device(out), "mhe_sum_row_blocks_f32: every buffer must be device memory");
+    const long n = (long)groups * C;
+    hipLaunchKernelGGL(glow::sum_row_blocks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, out, groups, N, C,
+                       out_stride, accumulate);
+    return check_launch("sum_row_blocks_kernel");
 }
 
 extern "C" int mhe_glow_glu_bwd_f32(const float *g_h, const void *t3, const float *gate, long gate_stride, void *g_t3, float *g_gate_rows,

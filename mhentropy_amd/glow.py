@@ -49,21 +49,6 @@ class _LULinear(nn.Module):
         self.bias = nn.Parameter(torch.zeros(features))
 
 
-    def weight_and_diag(self):
-        """W = L U and U's diagonal in float64 on the host (the wide body flow, features > 64; the hand flow builds them on the device)"""
-        D = self.features
-        lower = torch.zeros(D, D, dtype=torch.float64)
-        li = np.tril_indices(D, k=-1)
-        lower[li[0], li[1]] = self.lower_entries.detach().double().cpu()
-        lower[range(D), range(D)] = 1.0
-        upper = torch.zeros(D, D, dtype=torch.float64)
-        ui = np.triu_indices(D, k=1)
-        upper[ui[0], ui[1]] = self.upper_entries.detach().double().cpu()
-        diag = F.softplus(self.unconstrained_upper_diag.detach().double().cpu()) + self.eps
-        upper[range(D), range(D)] = diag
-        return lower @ upper, diag
-
-
 class _ResidualBlock(nn.Module):
     def __init__(self, features, context_features, dropout_probability):
         super().__init__()
@@ -162,29 +147,14 @@ class ConditionalGlow(nn.Module):
         if D <= 64:
             # ActNorm + LU of every layer as one 45x45 affine map and its inverse: one launch, float64 on the device (no host round trip)
             aff = ops.glow_affine(self.small_param_table(), self.num_layers, D, T[1].eps)
-            pk = {"layers": [], "const_parts": aff["const_parts"], "aff": aff}
         else:
-            # the wide body flow (144-D pose, padded to 192 columns): float64 on the host, once per parameter version
-            pk = {"layers": [], "aff": None}
-            parts = []
+            # the wide body flow (144-D pose, padded to 192 columns): float64 on the device with a global workspace (csrc/glow_affine_wide.hip)
+            aff = ops.glow_affine_wide(self.small_param_table(), self.num_layers, D, T[1].eps)
+        pk = {"layers": [], "const_parts": aff["const_parts"], "aff": aff}
         wctx, bctx = [], []
         for l in range(self.num_layers):
             cp = T[3 * l + 2]
-            if D <= 64:
-                d = {"A": aff["A"][l], "c": aff["c"][l], "Ainv": aff["Ainv"][l], "cinv": aff["cinv"][l]}
-            else:
-                an, lu = T[3 * l], T[3 * l + 1]
-                W, diag = lu.weight_and_diag()
-                sc = torch.exp(an.log_scale.detach().double().cpu())
-                A = W * sc[None, :]                                          # x -> W (s*x + shift) + b
-                c = W @ an.shift.detach().double().cpu() + lu.bias.detach().double().cpu()
-                Ainv = torch.linalg.inv(A)
-                Dp = self.Dp
-                pad = lambda M, v: (F.pad(M, (0, Dp - D, 0, Dp - D)).float().to(dev).contiguous(), F.pad(v, (0, Dp - D)).float().to(dev).contiguous())
-                d = {}
-                d["A"], d["c"] = pad(A, c)
-                d["Ainv"], d["cinv"] = pad(Ainv, -(Ainv @ c))
-                parts.append(float(an.log_scale.detach().double().sum().cpu() + torch.log(diag).sum()))
+            d = {"A": aff["A"][l], "c": aff["c"][l], "Ainv": aff["Ainv"][l], "cinv": aff["cinv"][l]}
             net = cp.transform_net
             idf = cp.identity_features
             w0 = net.initial_layer.weight.detach()
@@ -205,8 +175,6 @@ class ConditionalGlow(nn.Module):
             bf = torch.zeros(Pp, device=dev); bf[:2 * nt] = net.final_layer.bias.detach()
             d["wf"], d["bf"], d["T"], d["first"] = wf.contiguous(), bf.contiguous(), nt, 1 - (l % 2)      # (the alternating mask: odd columns first)
             pk["layers"].append(d)
-        if D > 64:
-            pk["const_parts"] = torch.tensor(parts, dtype=torch.float32, device=dev)
         pk["wctx"], pk["bctx"] = torch.cat(wctx).contiguous(), torch.cat(bctx).contiguous()
         if H == 512 and self.num_blocks == 2 and D <= 48:
             # the one-launch kernel's operands (csrc/glow_fwd.hip): bf16 copies in MFMA fragment order, the final layer's rows at the flow

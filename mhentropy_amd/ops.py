@@ -1618,6 +1618,59 @@ def glow_reparam_bwd(g_ainv_ptrs, g_cinv_ptrs, g_logp, layers, features, ws, gra
                                               layers, features, _ptr(ws), _ptr(grad_ptrs), _stream()), "mhe_glow_reparam_bwd_f64")
 
 
+def glow_affine_wide(ptr_table, layers, features, eps, out=None):
+    """glow_affine for a wide flow variable (2 <= features <= 256; the 144-D body pose): the same dict with [L, Dp, Dp] / [L, Dp] outputs,
+    Dp = ceil64(features), and the float64 workspace the reverse reads: mhe_glow_affine_wide_f64"""
+    dev, Dp = ptr_table.device, (features + 63) // 64 * 64
+    if out is None:
+        out = {k: torch.empty(layers, Dp, Dp, device=dev) for k in ("A", "Ainv", "AinvT")}
+        out.update({k: torch.empty(layers, Dp, device=dev) for k in ("c", "cinv")})
+        out["const_parts"] = torch.empty(layers, device=dev)
+        out["ws"] = torch.empty(int(_lib.lib().mhe_glow_affine_wide_workspace_doubles(layers, features)), device=dev, dtype=torch.float64)
+    check(_lib.lib().mhe_glow_affine_wide_f64(_ptr(ptr_table), layers, features, float(eps), _ptr(out["A"]), _ptr(out["c"]), _ptr(out["Ainv"]),
+                                              _ptr(out["AinvT"]), _ptr(out["cinv"]), _ptr(out["const_parts"]), _ptr(out["ws"]), _stream()),
+          "mhe_glow_affine_wide_f64")
+    return out
+
+
+def glow_affine_wide_bwd(g_ainv, g_cinv, g_logq, layers, features, ws):
+    """float64 gradients [layers, 4 D + D (D - 1)] of every layer's (log_scale, shift, lower, upper, unconstrained diag, bias) from dL/dA^-1
+    [L, Dp, Dp], dL/dc^-1 [L, Dp] and dL/dlog q per row (or None): mhe_glow_affine_wide_bwd_f64"""
+    Dp = (features + 63) // 64 * 64
+    _chk(g_ainv, torch.float32, "affine_wide_bwd.g_ainv", (layers, Dp, Dp)); _chk(g_cinv, torch.float32, "affine_wide_bwd.g_cinv", (layers, Dp))
+    if g_logq is not None:
+        _chk(g_logq, torch.float32, "affine_wide_bwd.g_logq")
+    L = _lib.lib()
+    out = torch.empty(layers, int(L.mhe_glow_affine_wide_grad_doubles(layers, features)) // layers, device=g_ainv.device, dtype=torch.float64)
+    check(L.mhe_glow_affine_wide_bwd_f64(_ptr(g_ainv), _ptr(g_cinv), _ptr(g_logq), 0 if g_logq is None else g_logq.numel(), layers, features,
+                                         _ptr(ws), _ptr(out), _stream()), "mhe_glow_affine_wide_bwd_f64")
+    return out
+
+
+def glow_coupling_inv_bwd_wide(v, prm, g_y, g_logq, dim, first, n_transform):
+    """reverse of the inverse coupling at the pitches of v [R, ld] and prm [R, ldp]: (g_v [R, ld], g_prm [R, ldp])"""
+    R, ld = v.shape
+    ldp = prm.shape[1]
+    _chk(v, torch.float32, "coupling_bwd.v"); _chk(prm, torch.float32, "coupling_bwd.prm", (R, ldp)); _chk(g_y, torch.float32, "coupling_bwd.g_y", (R, ld))
+    if g_logq is not None:
+        _chk(g_logq, torch.float32, "coupling_bwd.g_logq", (R,))
+    g_v, g_prm = torch.empty_like(v), torch.empty_like(prm)
+    check(_lib.lib().mhe_glow_coupling_inv_bwd_wide_f32(_ptr(v), _ptr(prm), _ptr(g_y), _ptr(g_logq), _ptr(g_v), _ptr(g_prm), R, dim, first, n_transform,
+                                                        ld, ldp, _stream()), "mhe_glow_coupling_inv_bwd_wide_f32")
+    return g_v, g_prm
+
+
+def sum_row_blocks(rows, groups, N, out=None, out_stride=0, accumulate=False):
+    """out[g] (+)= sum_n rows[g*N + n] (per-image sums of batch-major rows); `out` may be a view into a wider [groups, out_stride] matrix"""
+    Cc = rows.shape[1]
+    _chk(rows, torch.float32, "sum_row_blocks.rows", (groups * N, Cc))
+    if out is None:
+        out = torch.empty(groups, Cc, device=rows.device, dtype=torch.float32)
+    check(_lib.lib().mhe_sum_row_blocks_f32(_ptr(rows), C.c_void_p(out.data_ptr()), groups, N, Cc, int(out_stride or Cc), int(accumulate), _stream()),
+          "mhe_sum_row_blocks_f32")
+    return out
+
+
 def glow_finish(z_padded, v_padded, logdet, R, dim, inverse, const_parts, want_out=True):
     """(out [R,dim] | None, log_prob [R]) with the log-determinant constant summed from the device-resident per-layer parts"""
     out = torch.empty(R, dim, device=z_padded.device) if want_out else None

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Body-model path (SURVEY.md section 8 row f1 / config C4 per GPU: B=128 images x K=128 hypotheses of a 144-D 6D pose): time of the
 Glow sampling pass, the 6D -> R conversion and the SMPL-sized linear-blend skinning (24 joints, 6,890 vertices), whole and for a
-1/8 hypothesis slice (what one rank of a hypothesis-sharded 8-GPU job decodes).  Synthetic tables; parity unpinned at this size."""
+1/8 hypothesis slice (what one rank of a hypothesis-sharded 8-GPU job decodes).  Synthetic tables; parity unpinned at this size.
+TRAIN=1 adds the train leg: forward + backward of the head in f32 (log_prob[:, 1:].mean() + a joint loss, joints only) next to the f32
+forward-only time of the same call under no_grad."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -44,3 +46,21 @@ vb = R * 6890 * 12
 print(f"B={B} K={K} R={R}: glow sample+log_prob {ms_flow:.2f} ms | rot6d {ms_rot * 1e3:.0f} us | LBS 6,890 verts {ms_lbs:.2f} ms "
       f"({vb / ms_lbs / 1e6:.0f} GB/s of vertices written, {R * 6890 * 3 * (10 + 207 + 96 + 4) / ms_lbs / 1e9:.1f} TFMA/s) | joints only {ms_joints * 1e3:.0f} us")
 print(f"whole head {ms_all:.2f} ms = {R / ms_all * 1e3:.3e} hypotheses/s ; decoding a 1/8 hypothesis slice {ms_slice:.2f} ms")
+
+
+if os.environ.get("TRAIN", "0") == "1":
+    head.flow.compute_dtype = torch.float32
+    head.train()                                   # (dropout p = 0: train mode only switches the differentiable pass on)
+    target = torch.randn(B, K, 24, 3, device="cuda") * 0.3
+
+    def step():
+        for p_ in head.flow.parameters():
+            p_.grad = None
+        out = head(feats, K, betas=betas, noise=noise, want_verts=False)
+        (out["log_prob"][:, 1:].mean() + (out["joints"] - target).abs().mean()).backward()
+
+    with torch.no_grad():
+        ms_fwd32 = t(lambda: head(feats, K, betas=betas, noise=noise, want_verts=False))
+    ms_train = t(step, n=3)
+    print(f"train leg (f32, joints only) B={B} K={K}: forward {ms_fwd32:.2f} ms | forward + backward {ms_train:.2f} ms "
+          f"({ms_train / ms_fwd32:.2f}x the forward)")
