@@ -846,6 +846,24 @@ int mhe_sum_row_blocks_f32(const float *rows, float *out, int groups, int N, int
  * g_joints [R,J,3] -> g_rotmats [R,J,3,3], g_betas [R,nb] (through j_template + j_shapedirs beta).  Follow with mhe_rot6d_to_rotmat_bwd_f32. */
 int mhe_lbs_pose_bwd_f32(const float *rotmats, const float *betas, const float *j_template, const float *j_shapedirs, const int *parents,
                          const float *g_joints, float *g_rotmats, float *g_betas, int R, int J, int nb, void *stream);
+/* Reverse of the vertex skinning (csrc/lbs_skin_bwd.hip; exact-f32 matrix-core reductions over the vertices, no atomics: bit-reproducible).
+ * The tables are made once per model: `tables` = mhe_lbs_bwd_tables_floats(J, nb, VP) floats, filled by mhe_lbs_bwd_tables_f32 from the vertex-fastest
+ * v_shapedirs / v_posedirs / v_weights of mhe_lbs_skin_f32 (coefficient-fastest copies).  mhe_lbs_skin_bwd_f32 takes the workspace rows of
+ * mhe_lbs_pose_f32 (no further workspace), the same vertex tables, and g_verts [R,NV,3] = dL/dverts of verts = scale * skin; it writes
+ * g_transforms [R,J,12] (the workspace's transform layout), g_posemap [R,9(J-1)] and g_betas [R,nb] (the blend-shape term only).
+ * 1 < J <= 32, 0 < nb <= 64, VP >= NV a multiple of 32, any R and NV. */
+size_t mhe_lbs_bwd_tables_floats(int J, int nb, int VP);
+int mhe_lbs_bwd_tables_f32(const float *v_shapedirs, const float *v_posedirs, const float *v_weights, float *tables, int J, int nb, int NV, int VP,
+                           void *stream);
+int mhe_lbs_skin_bwd_f32(const float *workspace, const float *v_template, const float *v_shapedirs, const float *v_posedirs, const float *v_weights,
+                         const float *tables, const float *g_verts, float *g_transforms, float *g_posemap, float *g_betas, int R, int J, int nb, int NV,
+                         int VP, float scale, void *stream);
+/* Reverse of the pose pass from the skinning transforms (csrc/body.hip; one wavefront per hypothesis): g_transforms [R,J,12], g_posemap [R,9(J-1)]
+ * and g_joints [R,J,3] (NULL: none) -> g_rotmats [R,J,3,3], g_betas [R,nb] = g_betas_in (NULL: zero; may equal g_betas) + the rest-joint term.
+ * With g_transforms and g_posemap zero it equals mhe_lbs_pose_bwd_f32.  Follow with mhe_rot6d_to_rotmat_bwd_f32. */
+int mhe_lbs_transforms_bwd_f32(const float *rotmats, const float *betas, const float *j_template, const float *j_shapedirs, const int *parents,
+                               const float *g_joints, const float *g_transforms, const float *g_posemap, const float *g_betas_in, float *g_rotmats,
+                               float *g_betas, int R, int J, int nb, void *stream);
 
 #ifdef __cplusplus
 }

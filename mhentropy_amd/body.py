@@ -96,6 +96,18 @@ class BodyLayer(nn.Module):
             self._split, self._split_key = sp, key
         return self._split
 
+    def _bwd_tables(self, dev):
+        """coefficient-fastest copies of the blend-shape and weight tables for the skinning reverse (mhe_lbs_bwd_tables_f32, 19 MB for SMPL), made
+        on first use per device like _split_tables"""
+        key = (dev.type, dev.index, self._vt.data_ptr())
+        if getattr(self, "_bwd_key", None) != key:
+            L = _lib.lib()
+            tb = torch.empty(L.mhe_lbs_bwd_tables_floats(self.J, self.nb, self.VP), device=dev, dtype=torch.float32)
+            ops.check(L.mhe_lbs_bwd_tables_f32(ops._ptr(self._vsd), ops._ptr(self._vpd), ops._ptr(self._vw), ops._ptr(tb), self.J, self.nb, self.NV,
+                                               self.VP, ops._stream()), "mhe_lbs_bwd_tables_f32")
+            self._bwd_tab, self._bwd_key = tb, key
+        return self._bwd_tab
+
     def forward(self, betas, rotmats=None, pose6d=None, scale=1.0, want_verts=True):
         """betas (R,nb); rotmats (R,J,3,3) or pose6d (R,6J) -> {'vertices' (R,NV,3), 'joints' (R,J,3), 'rotmats'}"""
         if rotmats is None:
@@ -134,21 +146,24 @@ class BodyFlowHead(nn.Module):
         self.flow = ConditionalGlow(6 * self.body.J, hidden, num_layers, num_blocks, context_features=context_features,
                                     dropout_probability=0.0)
 
-    def forward(self, feats, num_samples, betas=None, noise=None, hyp_slice=None, want_verts=True):
+    def forward(self, feats, num_samples, betas=None, noise=None, hyp_slice=None, want_verts=True, verts_grad=False):
         """feats (B,F) -> pose6d (B,K,6J), log_prob (B,K), vertices (B,K,NV,3), joints (B,K,J,3); hyp_slice = (lo, hi) decodes only
         hypotheses lo..hi-1 of every image (the hypothesis-sharded form).
 
         Differentiable when grad is enabled and `feats` or `betas` require grad, or the head is in train mode with flow parameters that require
         grad (one autograd node, _HeadFn, whose backward is the hand-written reverse pass; an eval-mode call on plain inputs stays the
-        inference pass and returns plain tensors): log_prob, pose6d and joints carry gradients to every flow parameter, feats and betas.
-        Refused there (NotImplementedError): a non-zero gradient on vertices, compute_dtype bfloat16, dropout p > 0 in train mode."""
+        inference pass and returns plain tensors): log_prob, pose6d and joints carry gradients to every flow parameter, feats and betas; with
+        verts_grad=True so do vertices (the skinning reverse, lbs_bwd).  Refused there (NotImplementedError): a non-zero gradient on vertices
+        without verts_grad=True, compute_dtype bfloat16, dropout p > 0 in train mode.  verts_grad changes nothing on the inference pass."""
+        if verts_grad and not want_verts:
+            raise ValueError("BodyFlowHead: verts_grad=True needs want_verts=True")
         params = [p for p in self.flow.parameters()]
         if torch.is_grad_enabled() and ((self.training and any(p.requires_grad for p in params)) or feats.requires_grad
                                         or (betas is not None and betas.requires_grad)):
             if noise is None:
                 noise = ops.randn(feats.shape[0] * num_samples, self.flow.features, feats.device).view(feats.shape[0], num_samples, self.flow.features)
             lo, hi = hyp_slice if hyp_slice is not None else (0, num_samples)
-            vals = _HeadFn.apply(self, feats, betas, noise, num_samples, lo, hi, want_verts, *params)
+            vals = _HeadFn.apply(self, feats, betas, noise, num_samples, lo, hi, want_verts, bool(verts_grad), *params)
             res = {"pose6d": vals[0], "log_prob": vals[1], "joints": vals[2]}
             if want_verts:
                 res["vertices"] = vals[3]
@@ -177,12 +192,39 @@ def lbs_pose_bwd(layer, rotmats, betas, g_joints):
     return g_rot, g_bt
 
 
+def lbs_bwd(layer, rotmats, betas, g_verts, g_joints=None, scale=1.0):
+    """reverse of BodyLayer's vertices and posed joints: g_verts (R,NV,3) = dL/dvertices of `layer(betas, rotmats=rotmats, scale=scale)`,
+    g_joints (R,J,3) or None -> (g_rotmats (R,J,3,3), g_betas (R,nb)).  The pose pass is run again for its workspace rows; the skinning reverse
+    (mhe_lbs_skin_bwd_f32, exact-f32 matrix-core reductions over the vertices) then the pose chain's (mhe_lbs_transforms_bwd_f32)."""
+    R, J, nb = rotmats.shape[0], layer.J, layer.nb
+    ops._chk(rotmats, torch.float32, "lbs_bwd.rotmats", (R, J, 3, 3)); ops._chk(betas, torch.float32, "lbs_bwd.betas", (R, nb))
+    ops._chk(g_verts, torch.float32, "lbs_bwd.g_verts", (R, layer.NV, 3))
+    if g_joints is not None:
+        ops._chk(g_joints, torch.float32, "lbs_bwd.g_joints", (R, J, 3))
+    L, dev = _lib.lib(), rotmats.device
+    ws = torch.empty(L.mhe_lbs_workspace_floats(R, J, nb), device=dev, dtype=torch.float32)
+    ops.check(L.mhe_lbs_pose_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(layer._jt), ops._ptr(layer._jsd), ops._ptr(layer.parents), ops._ptr(ws),
+                                 None, R, J, nb, ops._stream()), "mhe_lbs_pose_f32")
+    g_tf = torch.empty(R, J, 12, device=dev, dtype=torch.float32)
+    g_pm = torch.empty(R, 9 * (J - 1), device=dev, dtype=torch.float32)
+    g_bt = torch.empty_like(betas)
+    ops.check(L.mhe_lbs_skin_bwd_f32(ops._ptr(ws), ops._ptr(layer._vt), ops._ptr(layer._vsd), ops._ptr(layer._vpd), ops._ptr(layer._vw),
+                                     ops._ptr(layer._bwd_tables(dev)), ops._ptr(g_verts), ops._ptr(g_tf), ops._ptr(g_pm), ops._ptr(g_bt), R, J, nb,
+                                     layer.NV, layer.VP, float(scale), ops._stream()), "mhe_lbs_skin_bwd_f32")
+    g_rot = torch.empty_like(rotmats)
+    ops.check(L.mhe_lbs_transforms_bwd_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(layer._jt), ops._ptr(layer._jsd), ops._ptr(layer.parents),
+                                           ops._ptr(g_joints), ops._ptr(g_tf), ops._ptr(g_pm), ops._ptr(g_bt), ops._ptr(g_rot), ops._ptr(g_bt), R, J, nb,
+                                           ops._stream()), "mhe_lbs_transforms_bwd_f32")
+    return g_rot, g_bt
+
+
 class _HeadFn(torch.autograd.Function):
     """BodyFlowHead.forward as one autograd node: forward = the f32 sampling pass with a tape (glow_grad.sample_with_tape, bit-identical to the
     no-grad pass) + the body decode; backward = joints -> rotations -> 6D poses (mhe_lbs_pose_bwd_f32, mhe_rot6d_to_rotmat_bwd_f32) added to
-    dL/dpose6d on the slice's rows, then the flow's reverse pass (glow_grad.backward).  Vertices are returned but have no reverse pass."""
+    dL/dpose6d on the slice's rows, then the flow's reverse pass (glow_grad.backward).  With verts_grad, a vertex gradient takes lbs_bwd (the
+    skinning reverse together with the joints'); without one the route is the joints-only one whatever verts_grad says."""
     @staticmethod
-    def forward(ctx, head, feats, betas, noise, K, lo, hi, want_verts, *params):
+    def forward(ctx, head, feats, betas, noise, K, lo, hi, want_verts, verts_grad, *params):
         from . import glow_grad
         B, D, nb, J = feats.shape[0], head.flow.features, head.body.nb, head.body.J
         x, lp, tape = glow_grad.sample_with_tape(head.flow, noise.reshape(B * K, D).contiguous(), feats.contiguous(), K)
@@ -191,7 +233,7 @@ class _HeadFn(torch.autograd.Function):
         bt = betas.contiguous() if betas is not None else torch.zeros(B, nb, device=feats.device)
         bt = bt[:, None, :].expand(B, hi - lo, nb).reshape(B * (hi - lo), nb).contiguous()
         out = head.body(bt, pose6d=p, want_verts=want_verts)
-        ctx.head, ctx.tape, ctx.shape, ctx.has_betas = head, tape, (B, K, lo, hi), betas is not None
+        ctx.head, ctx.tape, ctx.shape, ctx.has_betas, ctx.verts_grad = head, tape, (B, K, lo, hi), betas is not None, verts_grad
         ctx.save_for_backward(p, out["rotmats"], bt)
         ctx.set_materialize_grads(False)
         joints = out["joints"].view(B, hi - lo, J, 3)
@@ -201,17 +243,22 @@ class _HeadFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_pose, g_lp, g_joints, *g_verts):
         from . import glow_grad
-        if g_verts and g_verts[0] is not None and bool(g_verts[0].ne(0).any()):
-            raise NotImplementedError("BodyFlowHead: no reverse pass through the vertex skinning - a loss on 'vertices' cannot be differentiated "
-                                      "(use 'joints' / 'pose6d')")
+        gv = g_verts[0] if g_verts and g_verts[0] is not None and bool(g_verts[0].ne(0).any()) else None
+        if gv is not None and not ctx.verts_grad:
+            raise NotImplementedError("BodyFlowHead: no reverse pass through the vertex skinning by default - a loss on 'vertices' cannot be "
+                                      "differentiated (use 'joints' / 'pose6d', or pass verts_grad=True)")
         head, (B, K, lo, hi) = ctx.head, ctx.shape
         p, rotmats, bt = ctx.saved_tensors
         D, nb, J = head.flow.features, head.body.nb, head.body.J
         gx = torch.zeros(B, K, D, device=p.device) if g_pose is None else g_pose.float().contiguous().clone()
         g_betas = None
-        if g_joints is not None:
+        if g_joints is not None or gv is not None:
             n = hi - lo
-            g_rot, g_bt = lbs_pose_bwd(head.body, rotmats, bt, g_joints.float().reshape(B * n, J, 3).contiguous())
+            gj = None if g_joints is None else g_joints.float().reshape(B * n, J, 3).contiguous()
+            if gv is None:
+                g_rot, g_bt = lbs_pose_bwd(head.body, rotmats, bt, gj)
+            else:
+                g_rot, g_bt = lbs_bwd(head.body, rotmats, bt, gv.float().reshape(B * n, head.body.NV, 3).contiguous(), gj)
             g6 = rot6d_to_rotmat_bwd(p.view(B * n, J, 6), g_rot)
             gx[:, lo:hi] += g6.view(B, n, D)
             if ctx.has_betas and ctx.needs_input_grad[2]:
@@ -222,4 +269,4 @@ class _HeadFn(torch.autograd.Function):
         grads, g_feats = glow_grad.backward(head.flow, ctx.tape, gx.view(B * K, D), glp)
         ctx.tape = None
         params = list(head.flow.parameters())
-        return (None, g_feats if ctx.needs_input_grad[1] else None, g_betas, None, None, None, None, None) + tuple(grads.get(q) for q in params)
+        return (None, g_feats if ctx.needs_input_grad[1] else None, g_betas, None, None, None, None, None, None) + tuple(grads.get(q) for q in params)

@@ -229,6 +229,75 @@ __global__ __launch_bounds__(256) void lbs_pose_bwd_kernel(const float *__restri
     }
 }
 
+// Reverse of the whole pose pass (one wavefront per hypothesis): the gradients of the skinning transforms A_j = [Rw_j | a_j], a_j = t_j - Rw_j J_j
+// (g_transforms [J][12], the workspace layout), of the pose map p = R_j - I (g_posemap [9(J-1)]) and optionally of the posed joints seed
+//   gRw_j = gA_j[:, :3] - g_a_j J_j^T,  gt_j = g_joints_j + g_a_j,  gJ_j = -Rw_j^T g_a_j
+// then the child -> parent walk of lbs_pose_bwd_kernel, with g_R_j += g_posemap[block j - 1]; g_beta = g_betas_in + j_shapedirs^T gJ.
+// g_betas_in may be g_betas (each lane reads its element before writing it).
+__global__ __launch_bounds__(256) void lbs_transforms_bwd_kernel(const float *__restrict__ rot, const float *__restrict__ betas,
+                                                                 const float *__restrict__ jt, const float *__restrict__ jsd,
+                                                                 const int *__restrict__ parents, const float *__restrict__ g_joints,
+                                                                 const float *__restrict__ g_tf, const float *__restrict__ g_pm, const float *g_betas_in,
+                                                                 float *__restrict__ g_rot, float *g_betas, int R, int J, int nb) {
+    __shared__ float sW[4][MAXJ * 9], sJ[4][MAXJ * 3], sGW[4][MAXJ * 9], sGT[4][MAXJ * 3], sGJ[4][MAXJ * 3];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float *W = sW[wave], *Jr = sJ[wave], *GW = sGW[wave], *GT = sGT[wave], *GJ = sGJ[wave];
+    for (int r = blockIdx.x * 4 + wave; r < R; r += gridDim.x * 4) {
+        const float *Rr = rot + (size_t)r * J * 9, *bt = betas + (size_t)r * nb, *ga = g_tf + (size_t)r * J * 12, *gp = g_pm + (size_t)r * 9 * (J - 1);
+        for (int e = lane; e < 3 * J; e += 64) {
+            float v = jt[e];
+            for (int k = 0; k < nb; ++k) v = fmaf(jsd[e * nb + k], bt[k], v);
+            Jr[e] = v;
+        }
+        if (lane < 9) W[lane] = Rr[lane];
+        wave_sync();
+        for (int j = 1; j < J; ++j) {                     // world rotations
+            const int p = parents[j];
+            if (lane < 9) {
+                const int a = lane / 3, b = lane % 3;
+                W[9 * j + lane] = W[9 * p + 3 * a] * Rr[9 * j + b] + W[9 * p + 3 * a + 1] * Rr[9 * j + 3 + b] + W[9 * p + 3 * a + 2] * Rr[9 * j + 6 + b];
+            }
+            wave_sync();
+        }
+        for (int e = lane; e < 9 * J; e += 64) {
+            const int j = e / 9, k = e % 9;
+            GW[e] = ga[j * 12 + k] - ga[j * 12 + 9 + k / 3] * Jr[3 * j + k % 3];
+        }
+        for (int e = lane; e < 3 * J; e += 64) {
+            const int j = e / 3, c = e % 3;
+            const float *g = ga + j * 12 + 9, *Wj = W + 9 * j;
+            GT[e] = (g_joints ? g_joints[(size_t)r * 3 * J + e] : 0.f) + g[c];
+            GJ[e] = -(Wj[c] * g[0] + Wj[3 + c] * g[1] + Wj[6 + c] * g[2]);
+        }
+        wave_sync();
+        for (int j = J - 1; j >= 1; --j) {
+            const int p = parents[j];
+            const float *Wp = W + 9 * p, *gw = GW + 9 * j, *gt = GT + 3 * j, *Rj = Rr + 9 * j;
+            if (lane < 9) {
+                const int a = lane / 3, b = lane % 3;
+                g_rot[(size_t)r * J * 9 + 9 * j + lane] = Wp[a] * gw[b] + Wp[3 + a] * gw[3 + b] + Wp[6 + a] * gw[6 + b] + gp[9 * (j - 1) + lane];
+                GW[9 * p + lane] += gw[3 * a] * Rj[3 * b] + gw[3 * a + 1] * Rj[3 * b + 1] + gw[3 * a + 2] * Rj[3 * b + 2] + gt[a] * (Jr[3 * j + b] - Jr[3 * p + b]);
+            } else if (lane < 12) {
+                const int c = lane - 9;
+                const float u = Wp[c] * gt[0] + Wp[3 + c] * gt[1] + Wp[6 + c] * gt[2];
+                GJ[3 * j + c] += u;
+                GJ[3 * p + c] -= u;
+                GT[3 * p + c] += gt[c];
+            }
+            wave_sync();
+        }
+        if (lane < 9) g_rot[(size_t)r * J * 9 + lane] = GW[lane];
+        else if (lane < 12) GJ[lane - 9] += GT[lane - 9];
+        wave_sync();
+        if (lane < nb) {
+            float a = g_betas_in ? g_betas_in[(size_t)r * nb + lane] : 0.f;
+            for (int e = 0; e < 3 * J; ++e) a = fmaf(jsd[e * nb + lane], GJ[e], a);
+            g_betas[(size_t)r * nb + lane] = a;
+        }
+        wave_sync();
+    }
+}
+
 template <int HB>
 __global__ __launch_bounds__(256) void lbs_skin_kernel(const float *__restrict__ ws, const float *__restrict__ Vt, const float *__restrict__ Vsd,
                                                        const float *__restrict__ Vpd, const float *__restrict__ Vw, float *__restrict__ verts_o,
@@ -327,6 +396,21 @@ extern "C" int mhe_lbs_pose_bwd_f32(const float *rotmats, const float *betas, co
     hipLaunchKernelGGL(body::lbs_pose_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rotmats, betas, j_template, j_shapedirs, parents,
                        g_joints, g_rotmats, g_betas, R, J, nb);
     return check_launch("lbs_pose_bwd_kernel");
+}
+
+extern "C" int mhe_lbs_transforms_bwd_f32(const float *rotmats, const float *betas, const float *j_template, const float *j_shapedirs,
+                                          const int *parents, const float *g_joints, const float *g_transforms, const float *g_posemap,
+                                          const float *g_betas_in, float *g_rotmats, float *g_betas, int R, int J, int nb, void *stream) {
+    MHE_REQUIRE(rotmats && betas && j_template && j_shapedirs && parents && g_transforms && g_posemap && g_rotmats && g_betas,
+                "mhe_lbs_transforms_bwd_f32: null pointer");
+    MHE_REQUIRE(R > 0 && J > 1 && J <= body::MAXJ && nb > 0 && nb <= 64, "mhe_lbs_transforms_bwd_f32: R=%d J=%d nb=%d", R, J, nb);
+    MHE_REQUIRE(on_device(rotmats) && on_device(betas) && on_device(j_template) && on_device(j_shapedirs) && on_device(parents) &&
+                    (!g_joints || on_device(g_joints)) && on_device(g_transforms) && on_device(g_posemap) && (!g_betas_in || on_device(g_betas_in)) &&
+                    on_device(g_rotmats) && on_device(g_betas), "mhe_lbs_transforms_bwd_f32: every buffer must be device memory");
+    const int blocks = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
+    hipLaunchKernelGGL(body::lbs_transforms_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, rotmats, betas, j_template, j_shapedirs,
+                       parents, g_joints, g_transforms, g_posemap, g_betas_in, g_rotmats, g_betas, R, J, nb);
+    return check_launch("lbs_transforms_bwd_kernel");
 }
 
 extern "C" int mhe_lbs_skin_f32(const float *workspace, const float *v_template, const float *v_shapedirs, const float *v_posedirs,

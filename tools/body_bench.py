@@ -3,7 +3,8 @@
 Glow sampling pass, the 6D -> R conversion and the SMPL-sized linear-blend skinning (24 joints, 6,890 vertices), whole and for a
 1/8 hypothesis slice (what one rank of a hypothesis-sharded 8-GPU job decodes).  Synthetic tables; parity unpinned at this size.
 TRAIN=1 adds the train leg: forward + backward of the head in f32 (log_prob[:, 1:].mean() + a joint loss, joints only) next to the f32
-forward-only time of the same call under no_grad."""
+forward-only time of the same call under no_grad.  VERTS=1 (with TRAIN=1) adds the vertex-loss leg: log_prob[:, 1:].mean() + |vertices - target|.mean()
+with verts_grad=True, and the time of the skinning reverse alone (body.lbs_bwd) next to the forward skinning."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -64,3 +65,22 @@ if os.environ.get("TRAIN", "0") == "1":
     ms_train = t(step, n=3)
     print(f"train leg (f32, joints only) B={B} K={K}: forward {ms_fwd32:.2f} ms | forward + backward {ms_train:.2f} ms "
           f"({ms_train / ms_fwd32:.2f}x the forward)")
+
+    if os.environ.get("VERTS", "0") == "1":
+        tv = torch.randn(B, K, 6890, 3, device="cuda") * 0.3
+
+        def vstep():
+            for p_ in head.flow.parameters():
+                p_.grad = None
+            out = head(feats, K, betas=betas, noise=noise, verts_grad=True)
+            (out["log_prob"][:, 1:].mean() + (out["vertices"] - tv).abs().mean()).backward()
+
+        with torch.no_grad():
+            ms_fwdv = t(lambda: head(feats, K, betas=betas, noise=noise))
+        ms_vtrain = t(vstep, n=3)
+        gv = torch.randn(R, 6890, 3, device="cuda")
+        ms_bwd = t(lambda: body.lbs_bwd(head.body, rm, bt, gv))
+        ms_skin = t(lambda: head.body(bt, rotmats=rm))
+        print(f"train leg (f32, vertex loss) B={B} K={K}: forward {ms_fwdv:.2f} ms | forward + backward {ms_vtrain:.2f} ms "
+              f"({ms_vtrain / ms_fwdv:.2f}x the forward; joints only {ms_train:.2f} ms) | skinning reverse (lbs_bwd: pose pass + "
+              f"both reductions + chain) {ms_bwd:.2f} ms vs forward LBS {ms_skin:.2f} ms ({ms_bwd / ms_skin:.2f}x)")
