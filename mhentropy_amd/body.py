@@ -218,16 +218,76 @@ def lbs_bwd(layer, rotmats, betas, g_verts, g_joints=None, scale=1.0):
     return g_rot, g_bt
 
 
+def _flow_sample_with_tape(g, noise_rows, context, N):
+    """the flow's f32 sampling pass on batch-major rows (r = b N + n) with its tape: ConditionalGlow._run, the no-grad pass's own code ->
+    (x (B N, D), log_prob (B N,), tape)"""
+    if g.compute_dtype != torch.float32:
+        raise NotImplementedError("the Glow reverse pass runs in f32 parity mode: compute_dtype must be torch.float32 under grad")
+    if g.training and g.p_drop > 0.0:
+        raise NotImplementedError("the wide Glow reverse pass has no dropout: build the flow with dropout_probability=0 or call eval()")
+    ops._chk(noise_rows, torch.float32, "glow.noise", (noise_rows.shape[0], g.features))
+    pk = g._packed()
+    aff = pk["aff"]         # the wide float64 affine maps + workspace (the pack holds them above 64 features)
+    if not ("ws" in aff and aff["A"].shape[-1] == g.Dp and aff["ws"].numel() == _lib.lib().mhe_glow_affine_wide_workspace_doubles(g.num_layers, g.features)):
+        aff = ops.glow_affine_wide(g.small_param_table(), g.num_layers, g.features, g._transform._transforms[1].eps)
+    tape = {"aff": aff, "context": context, "sample_major": False}
+    x, lp = g._run(noise_rows, context, True, N, context.shape[0], pk=pk, tape=tape)
+    return x, lp, tape
+
+
+def _flow_backward(g, tp, g_x, g_logq):
+    """the flow's reverse pass over that tape: ConditionalGlow._reverse into fresh gradients, then the context weights' gradient from the
+    per-image rows, dL/dcontext and the ActNorm / LU gradients from dA^-1, dc^-1 and sum dL/dlog q in float64 (mhe_glow_affine_wide_bwd_f64).
+    g_x (B N, D) = dL/dx (or None), g_logq (B N,) = dL/dlog_prob (or None) -> ({parameter: gradient}, dL/dcontext (B, F)).  The noise is an
+    input, not differentiated."""
+    D, H, Lr, Dp = g.features, g.hidden, g.num_layers, g.Dp
+    pk, aff, ctab, B = tp["pk"], tp["aff"], tp["ctab"], tp["n_img"]
+    R, cs, per, dev = B * tp["row_div"], ctab.shape[1], 1 + g.num_blocks, ctab.device
+    gv = torch.zeros(R, Dp, device=dev)
+    if g_x is not None:
+        ops.check(_lib.lib().mhe_pad64_f32(ops._ptr(g_x), ops._ptr(gv), R, D, ops._stream()), "mhe_pad64_f32")
+    if g_logq is not None:
+        ops._chk(g_logq, torch.float32, "glow.g_log_prob", (R,))
+    Gct = torch.zeros(B, cs, device=dev)
+    dAinv, dcinv = torch.zeros(Lr, Dp, Dp, device=dev), torch.empty(Lr, Dp, device=dev)
+    z = lambda *shape: torch.zeros(*shape, device=dev)
+    dst = [{"dAinv": dAinv[l], "dcinv": dcinv[l], "dwf": z(d["wf"].shape[0], H), "dbf": torch.empty(d["wf"].shape[0], device=dev), "dwx": z(H, Dp),
+            "dblocks": [(z(H, H), z(H), z(H, H), z(H)) for _ in d["blocks"]]} for l, d in enumerate(pk["layers"])]
+    # the transposed operands one layer at a time, as the reverse reaches it
+    g._reverse(tp, gv, g_logq, Gct, ({**o, "AinvT": aff["AinvT"][l], "wfT": d["wf"].t().contiguous(), "wxT": d["wx"].t().contiguous(),
+                                      "blocksT": [(w0.t().contiguous(), w1.t().contiguous()) for (w0, _, w1, _) in d["blocks"]]}
+                                     for l, (d, o) in enumerate(zip(pk["layers"], dst))))
+    dW, db = z(cs, g.context_features), z(cs)
+    ops.linear_wgrad(tp["context"], Gct, dW); ops.colsum(Gct, db)
+    g_ctx = ops.linear(Gct, pk["wctx"].t().contiguous())
+    ga = ops.glow_affine_wide_bwd(dAinv, dcinv, g_logq, Lr, D, aff["ws"]).float()
+    T, n, grads = g._transform._transforms, D * (D - 1) // 2, {}
+    for l, (d, o) in enumerate(zip(pk["layers"], dst)):
+        an, lu, cp = T[3 * l], T[3 * l + 1], T[3 * l + 2]
+        net, r, slot = cp.transform_net, ga[l], l * per
+        grads[an.log_scale], grads[an.shift] = r[:D], r[D:2 * D]
+        grads[lu.lower_entries], grads[lu.upper_entries] = r[2 * D:2 * D + n], r[2 * D + n:2 * D + 2 * n]
+        grads[lu.unconstrained_upper_diag], grads[lu.bias] = r[2 * D + 2 * n:3 * D + 2 * n], r[3 * D + 2 * n:]
+        grads[net.initial_layer.weight] = torch.cat([o["dwx"][:, cp.identity_features], dW[slot * H:(slot + 1) * H]], 1)
+        grads[net.initial_layer.bias] = db[slot * H:(slot + 1) * H]
+        grads[net.final_layer.weight], grads[net.final_layer.bias] = o["dwf"][:2 * d["T"]], o["dbf"][:2 * d["T"]]
+        for b, (blk, (dw0, db0, dw1, db1)) in enumerate(zip(net.blocks, o["dblocks"])):
+            k = slot + 1 + b
+            grads[blk.linear_layers[0].weight], grads[blk.linear_layers[0].bias] = dw0, db0
+            grads[blk.linear_layers[1].weight], grads[blk.linear_layers[1].bias] = dw1, db1
+            grads[blk.context_layer.weight], grads[blk.context_layer.bias] = dW[k * H:(k + 1) * H], db[k * H:(k + 1) * H]
+    return grads, g_ctx
+
+
 class _HeadFn(torch.autograd.Function):
-    """BodyFlowHead.forward as one autograd node: forward = the f32 sampling pass with a tape (glow_grad.sample_with_tape, bit-identical to the
+    """BodyFlowHead.forward as one autograd node: forward = the f32 sampling pass with a tape (_flow_sample_with_tape, bit-identical to the
     no-grad pass) + the body decode; backward = joints -> rotations -> 6D poses (mhe_lbs_pose_bwd_f32, mhe_rot6d_to_rotmat_bwd_f32) added to
-    dL/dpose6d on the slice's rows, then the flow's reverse pass (glow_grad.backward).  With verts_grad, a vertex gradient takes lbs_bwd (the
+    dL/dpose6d on the slice's rows, then the flow's reverse pass (_flow_backward).  With verts_grad, a vertex gradient takes lbs_bwd (the
     skinning reverse together with the joints'); without one the route is the joints-only one whatever verts_grad says."""
     @staticmethod
     def forward(ctx, head, feats, betas, noise, K, lo, hi, want_verts, verts_grad, *params):
-        from . import glow_grad
         B, D, nb, J = feats.shape[0], head.flow.features, head.body.nb, head.body.J
-        x, lp, tape = glow_grad.sample_with_tape(head.flow, noise.reshape(B * K, D).contiguous(), feats.contiguous(), K)
+        x, lp, tape = _flow_sample_with_tape(head.flow, noise.reshape(B * K, D).contiguous(), feats.contiguous(), K)
         pose = x.view(B, K, D)
         p = pose[:, lo:hi].reshape(B * (hi - lo), D).contiguous()
         bt = betas.contiguous() if betas is not None else torch.zeros(B, nb, device=feats.device)
@@ -242,7 +302,6 @@ class _HeadFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_pose, g_lp, g_joints, *g_verts):
-        from . import glow_grad
         gv = g_verts[0] if g_verts and g_verts[0] is not None and bool(g_verts[0].ne(0).any()) else None
         if gv is not None and not ctx.verts_grad:
             raise NotImplementedError("BodyFlowHead: no reverse pass through the vertex skinning by default - a loss on 'vertices' cannot be "
@@ -266,7 +325,7 @@ class _HeadFn(torch.autograd.Function):
         elif ctx.has_betas and ctx.needs_input_grad[2]:
             g_betas = torch.zeros(B, nb, device=p.device)
         glp = None if g_lp is None else g_lp.float().reshape(B * K).contiguous()
-        grads, g_feats = glow_grad.backward(head.flow, ctx.tape, gx.view(B * K, D), glp)
+        grads, g_feats = _flow_backward(head.flow, ctx.tape, gx.view(B * K, D), glp)
         ctx.tape = None
         params = list(head.flow.parameters())
         return (None, g_feats if ctx.needs_input_grad[1] else None, g_betas, None, None, None, None, None, None) + tuple(grads.get(q) for q in params)

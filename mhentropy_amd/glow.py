@@ -30,6 +30,12 @@ from torch import nn
 from . import ops, _lib
 
 
+def _colsum(rows, B, N, out):
+    """out = column sums of batch-major rows [B N, C] in a fixed order - per image, then over images (ops.colsum takes C | 256 or C >= 256;
+    the body flow's variable and coupling parameters are 192 wide)"""
+    ops.sum_row_blocks(ops.sum_row_blocks(rows, B, N), 1, B, out=out.view(1, -1))
+
+
 class _ActNorm(nn.Module):
     def __init__(self, features):
         super().__init__()
@@ -120,7 +126,7 @@ class ConditionalGlow(nn.Module):
         self.p_drop = float(dropout_probability)
         self.mask_feed, self.record_masks, self.last_masks = None, False, []
         # operand dtype of the four hidden x hidden products per layer (95 % of the flow's FLOP): float32 (parity mode) or
-        # bfloat16 with f32 accumulate (performance mode; forward / loss / sample only - the train step's pass stays f32)
+        # bfloat16 with f32 accumulate (performance mode; the train step follows it, train_glow.GlowPart)
         self.compute_dtype = torch.float32
 
     # ---- derived device operands, rebuilt when a parameter changes --------------------------------------
@@ -218,43 +224,57 @@ class ConditionalGlow(nn.Module):
         return bits
 
     # ---- the two directions ------------------------------------------------------------------------------
-    def _net(self, d, v, ctab, slot, R, row_div, n_img, bufs):
-        """coupling parameters [R,64] of layer `d` from the (padded) variable v whose identity columns are current"""
+    def _net(self, d, v, ctab, slot, R, row_div, n_img, bf16, bufs, rec):
+        """coupling parameters [R,Pp] of layer `d` from the (padded) variable v whose identity columns are current.  bufs (h, t, t2): reused
+        in place, h as the residual stream; with a tape record `rec` every stage writes a fresh tensor instead, kept in rec"""
         L, H = _lib.lib(), self.hidden
-        h, t, t2 = bufs
-        s = ops._stream
-        ops.linear(v, d["wx"], out=h)
-        cs = ctab.shape[1]
+        s, cs = ops._stream, ctab.shape[1]
+        fresh = rec is not None
+        h = ops.linear(v, d["wx"], out=None if fresh else bufs[0])
         ops.check(L.mhe_glow_add_image_rows_f32(ops._ptr(h), C.c_void_p(ctab[:, slot * H:].data_ptr()), cs, R, H, row_div, n_img, s()), "mhe_glow_add_image_rows_f32")
-        bf16 = self.compute_dtype == torch.bfloat16 and H % 64 == 0
-        if bf16:
-            tb, t2b = (torch.empty(R, 1, 1, H, device=v.device, dtype=torch.bfloat16) for _ in range(2))
+        if fresh:
+            rec.update(hs=[h], t2=[], t3=[], drop=[])
+        elif bf16:
+            t, t2 = (torch.empty(R, 1, 1, H, device=v.device, dtype=torch.bfloat16) for _ in range(2))
+        else:
+            t, t2 = bufs[1:]
         for b, (w0, b0, w1, b1) in enumerate(d["blocks"]):
+            if fresh:
+                t = torch.empty(R, 1, 1, H, device=v.device, dtype=torch.bfloat16) if bf16 else torch.empty(R, H, device=v.device)
+            ops.check(L.mhe_relu_copy_f32(ops._ptr(h), ops._ptr(t), h.numel(), ops.dtype_code(t.dtype), s()), "mhe_relu_copy_f32")
             if bf16:        # relu(h) -> bf16, two h x h products on bf16 MFMA (bias + relu in the kernel's epilogue), gate in f32
                 w0b, w1b = d["blocks_bf16"][b]
-                ops.check(L.mhe_relu_copy_f32(ops._ptr(h), ops._ptr(tb), h.numel(), ops.BF16, s()), "mhe_relu_copy_f32")
-                ops.conv2d_nhwc(tb, w0b, 1, 1, 1, 0, out_shift=b0, relu_out=True, out=t2b)
-                self.dropout_(t2b)
-                t = ops.conv2d_nhwc(t2b, w1b, 1, 1, 1, 0, out_shift=b1, out=tb).view(R, H)
+                t2 = ops.conv2d_nhwc(t, w0b, 1, 1, 1, 0, out_shift=b0, relu_out=True, out=None if fresh else t2)
+                drop = self.dropout_(t2)
+                t3 = ops.conv2d_nhwc(t2, w1b, 1, 1, 1, 0, out_shift=b1, out=None if fresh else t)
             else:
-                ops.check(L.mhe_relu_copy_f32(ops._ptr(h), ops._ptr(t), h.numel(), ops.dtype_code(t.dtype), s()), "mhe_relu_copy_f32")
-                ops.linear(t, w0, b0, relu=True, out=t2)
-                self.dropout_(t2)
-                ops.linear(t2, w1, b1, out=t)
-            ops.check(L.mhe_glow_glu_residual_f32(ops._ptr(h), ops._ptr(t), ops.dtype_code(t.dtype), C.c_void_p(ctab[:, (slot + 1 + b) * H:].data_ptr()), cs, R, H, row_div,
-                                                  n_img, s()), "mhe_glow_glu_residual_f32")
+                t2 = ops.linear(t, w0, b0, relu=True, out=None if fresh else t2)
+                drop = self.dropout_(t2)
+                t3 = ops.linear(t2, w1, b1, out=None if fresh else t)
+            if fresh:
+                h = h.clone()
+                rec["hs"].append(h); rec["t2"].append(t2); rec["t3"].append(t3); rec["drop"].append(drop)
+            ops.check(L.mhe_glow_glu_residual_f32(ops._ptr(h), ops._ptr(t3), ops.dtype_code(t3.dtype), C.c_void_p(ctab[:, (slot + 1 + b) * H:].data_ptr()), cs, R, H,
+                                                  row_div, n_img, s()), "mhe_glow_glu_residual_f32")
         return ops.linear(h, d["wf"], d["bf"])
 
-    def _run(self, v_in, context, inverse, row_div, n_img):
-        """v_in (R,D) data (forward) or noise (inverse); returns (out (R,D), log_prob (R,))"""
+    def _run(self, v_in, context, inverse, row_div, n_img, pk=None, tape=None, bf16=None):
+        """v_in (R,D) data (forward) or noise (inverse); returns (out (R,D), log_prob (R,)).  Row r belongs to image r // row_div % n_img.
+        pk: the operand pack (default: the module's own); bf16: the block products on bf16 MFMA (default: compute_dtype is bfloat16).
+        tape (a dict; sampling direction, layer by layer): holds the caller's "sample_major" (the row layout, which row_div alone does not tell
+        at one row per image; `_reverse` picks its reductions by it) and is filled with what `_reverse` reads - the pack, the context table,
+        row_div, n_img and per layer v, the residual stream h_0 .. h_NB, every block's second activation t2 (after dropout), its second product t3 and dropout
+        bits, the coupling parameters and y"""
         ops._chk(v_in, torch.float32, "glow.in"); ops._chk(context, torch.float32, "glow.context", (context.shape[0], self.context_features))
-        pk, L, D, H = self._packed(), _lib.lib(), self.features, self.hidden
+        pk = self._packed() if pk is None else pk
+        L, D, H = _lib.lib(), self.features, self.hidden
+        bf16 = self.compute_dtype == torch.bfloat16 if bf16 is None else bf16
         R = v_in.shape[0]
         dev = v_in.device
         s = ops._stream
         ctab = ops.linear(context, pk["wctx"], pk["bctx"])                       # every context-only term, once per image
         N = R // n_img
-        if (inverse and self.compute_dtype == torch.bfloat16 and pk.get("fused") is not None and row_div in (1, N)
+        if (tape is None and inverse and bf16 and pk.get("fused") is not None and row_div in (1, N)
                 and os.environ.get("MHE_GLOW_FUSED", "1") == "1" and ops.glow_layers_supported(N, n_img, D, H, self.num_layers, self.num_blocks)):
             # the sampling direction of all layers in ONE launch (csrc/glow_fwd.hip; bf16 operands on the products, f32 residual stream,
             # flow variable, coupling and affine map)
@@ -264,20 +284,91 @@ class ConditionalGlow(nn.Module):
         ops.check(L.mhe_pad64_f32(ops._ptr(v_in), ops._ptr(v), R, D, s()), "mhe_pad64_f32")
         z_in = v
         logdet = torch.zeros(R, device=dev)
-        bufs = tuple(torch.empty(R, H, device=dev) for _ in range(3))
+        bufs = None if tape is not None else tuple(torch.empty(R, H, device=dev) for _ in range(3))
+        if tape is not None:
+            tape.update(pk=pk, ctab=ctab, row_div=row_div, n_img=n_img, layers=[None] * self.num_layers)
         per = 1 + self.num_blocks
         order = range(self.num_layers - 1, -1, -1) if inverse else range(self.num_layers)
         for l in order:
             d = pk["layers"][l]
             if not inverse:
                 v = ops.linear(v, d["A"], d["c"])
-            prm = self._net(d, v, ctab, l * per, R, row_div, n_img, bufs)
+            rec = None if tape is None else {"v": v}
+            prm = self._net(d, v, ctab, l * per, R, row_div, n_img, bf16, bufs, rec)
             y = torch.empty(R, self.Dp, device=dev)
             ops.check(L.mhe_glow_coupling_f32(ops._ptr(v), ops._ptr(prm), ops._ptr(y), ops._ptr(logdet), R, D, d["first"], d["T"], int(inverse), s()),
                       "mhe_glow_coupling_f32")
+            if rec is not None:
+                rec.update(prm=prm, y=y)
+                tape["layers"][l] = rec
             v = ops.linear(y, d["Ainv"], d["cinv"]) if inverse else y
         z = z_in if inverse else v                                               # the base-density argument
         return ops.glow_finish(z, v, logdet, R, D, inverse, pk["const_parts"])
+
+    def _reverse(self, tape, gv, g_logp, Gct, layers):
+        """the staged reverse pass over a `_run` tape, layers 0 .. L-1:
+            dA^-1 = gv^T y, dc^-1 = sum gv;  gy = gv A^-1;  coupling reverse -> g_v, g_prm;  final layer;
+            per block (last first) gate, second product, dropout, ReLU, first product, ReLU of the residual stream;  gv = g_v + gh Wx.
+        gv (R, Dp) = dL/dx padded; g_logp = dL/dlog q or None; Gct (B, cs) zeroed: receives the per-image gradient of the context table.
+        layers (consumed layer by layer: a generator keeps one layer's transposes alive at a time), per layer: the transposed operands AinvT,
+        wfT, wxT, blocksT [(w0T, w1T) of the tape's dtype] and the gradient destinations dAinv, dcinv, dwf, dbf, dwx, dblocks [(dw0, db0, dw1,
+        db1)] (the weight gradients and ops.colsum add to theirs, _colsum writes).  The reductions follow the tape's row layout:
+          sample-major (the train step's entropy term): g_logp per image, weight -1/N per row (mhe_glow_coupling_inv_bwd_f32 at 64
+            columns); per-image sums mhe_sum_over_hypotheses; column sums ops.colsum;
+          batch-major: g_logp per row (mhe_glow_coupling_inv_bwd_wide_f32); per-image sums mhe_sum_row_blocks_f32; column sums of
+            the flow-width rows (gv, g_prm) per image then over images (_colsum), of the hidden-width rows ops.colsum.
+        bf16 tapes (t2, t3 as [R, 1, 1, H] bfloat16) take the block's four products on bf16 MFMA."""
+        L_, D, H = _lib.lib(), self.features, self.hidden
+        ctab, row_div, B, sample_major = tape["ctab"], tape["row_div"], tape["n_img"], tape["sample_major"]
+        R, cs = gv.shape[0], ctab.shape[1]
+        N = R // B
+        s, dev = ops._stream, gv.device
+        if sample_major:
+            img_sum = lambda rows, out: ops.sum_over_hypotheses(rows, N, B, out=out, out_stride=cs)
+            flow_colsum = ops.colsum
+        else:
+            img_sum = lambda rows, out: ops.sum_row_blocks(rows, B, N, out=out, out_stride=cs)
+            flow_colsum = lambda rows, out: _colsum(rows, B, N, out)
+        per = 1 + self.num_blocks
+        for l, (t, d, o) in enumerate(zip(tape["layers"], tape["pk"]["layers"], layers)):
+            slot = l * per
+            ops.linear_wgrad(t["y"], gv, o["dAinv"]); flow_colsum(gv, o["dcinv"])
+            gy = ops.linear(gv, o["AinvT"])
+            if sample_major:
+                gvc, gprm = torch.empty(R, 64, device=dev), torch.empty(R, 64, device=dev)
+                ops.check(L_.mhe_glow_coupling_inv_bwd_f32(ops._ptr(t["v"]), ops._ptr(t["prm"]), ops._ptr(gy), ops._ptr(g_logp), -1.0 / N,
+                                                           ops._ptr(gvc), ops._ptr(gprm), R, B, D, d["first"], d["T"], s()), "mhe_glow_coupling_inv_bwd_f32")
+            else:
+                gvc, gprm = ops.glow_coupling_inv_bwd_wide(t["v"], t["prm"], gy, g_logp, D, d["first"], d["T"])
+            ops.linear_wgrad(t["hs"][-1], gprm, o["dwf"]); flow_colsum(gprm, o["dbf"])
+            gh = ops.linear(gprm, o["wfT"])
+            for b in range(self.num_blocks - 1, -1, -1):
+                (w0T, w1T), (dw0, db0, dw1, db1) = o["blocksT"][b], o["dblocks"][b]
+                t2, t3, hb = t["t2"][b], t["t3"][b], t["hs"][b]
+                bf16 = t3.dtype == torch.bfloat16
+                gt3, ggate = torch.empty_like(t3), torch.empty(R, H, device=dev)
+                ops.check(L_.mhe_glow_glu_bwd_f32(ops._ptr(gh), ops._ptr(t3), C.c_void_p(ctab[:, (slot + 1 + b) * H:].data_ptr()), cs,
+                                                  ops._ptr(gt3), ops._ptr(ggate), R, H, row_div, B, ops.dtype_code(t3.dtype), s()), "mhe_glow_glu_bwd_f32")
+                img_sum(ggate, Gct[:, (slot + 1 + b) * H:])
+                # the four h x h products of the block's reverse pass: on bf16 MFMA over a bf16 tape (bias sums of the bf16 gradients)
+                wgrad = (lambda x, gy_, dw: ops.conv_wgrad(x, gy_, 1, 1, 1, 0, dw)) if bf16 else ops.linear_wgrad
+                dgrad = (lambda gy_, wT: ops.conv2d_nhwc(gy_, wT, 1, 1, 1, 0)) if bf16 else ops.linear
+                wgrad(t2, gt3, dw1); ops.colsum(gt3, db1)
+                gt2 = dgrad(gt3, w1T)
+                if t["drop"][b] is not None:          # dropout's reverse: the same mask and scale on the gradient
+                    ops.dropout_(gt2, self.p_drop, bits=t["drop"][b])
+                if bf16:
+                    ops.flow_lrelu_bwd_mixed(gt2.view(R, H), t2.view(R, H), out_bf16=gt2.view(R, H), slope=0.0)
+                else:
+                    ops.flow_lrelu_bwd(gt2, t2, slope=0.0)
+                tt = torch.empty_like(t2)
+                ops.check(L_.mhe_relu_copy_f32(ops._ptr(hb), ops._ptr(tt), tt.numel(), ops.dtype_code(tt.dtype), s()), "mhe_relu_copy_f32")
+                wgrad(tt, gt2, dw0); ops.colsum(gt2, db0)
+                gt = dgrad(gt2, w0T)
+                ops.check(L_.mhe_relu_bwd_add_f32(ops._ptr(gh), ops._ptr(gt), ops._ptr(hb), gh.numel(), ops.dtype_code(gt.dtype), s()), "mhe_relu_bwd_add_f32")
+            ops.linear_wgrad(t["v"], gh, o["dwx"])
+            img_sum(gh, Gct[:, slot * H:])
+            gv = ops.add(gvc, ops.linear(gh, o["wxT"]))          # (after the last layer: dL/dnoise, which no caller reads)
 
     # ---- reference call surface ----------------------------------------------------------------------------
     def log_prob(self, inputs, context=None, rows_per_context=None):

@@ -598,8 +598,6 @@ class TrainStep:
         ver = sum(p._version for p in self._params)
         if ver != self._param_ver:
             self.repack()
-            if self.glow is not None:
-                self.glow.invalidate()
             self._param_ver = ver
 
     def _buf(self, name, shape, dtype=torch.float32):
@@ -1373,8 +1371,6 @@ class TrainStep:
                       self.max_norm or 0.0, self.last_grad_scale)
         self._G_averaged = False
         self.repack()          # every derived operand layout follows the new parameters
-        if self.glow is not None:
-            self.glow.invalidate()
         self._param_ver = sum(p._version for p in self._params)
 
     def second_bn_update(self):

@@ -14,10 +14,9 @@ rounds 2-4 did it in numpy on the host, a queue drain per step that kept this br
 of every residual block in the sampling pass (mask bits kept on the tape) and to its gradient in the reverse pass (glow.py, mhe_dropout).
 """
 import ctypes as C
+import os
 
-import numpy as np
 import torch
-import torch.nn.functional as F
 
 from . import ops, _lib
 
@@ -139,23 +138,23 @@ class GlowPart:
         parameters: mhe_glow_affine_f64 into the same tensors (graph-capturable: no host value depends on the parameters)"""
         ops.glow_affine(self._ptab, self.g.num_layers, self.g.features, self.layers[0]["lu"].eps, out=self.aff)
 
-    def invalidate(self):
-        pass             # (nothing host-side follows the parameters any more; the operand layouts are refreshed by the trainer's gather)
-
-    def module_pack(self):
-        """the operand dict ConditionalGlow._run reads (glow.py:_packed), on the trainer's device-resident layouts: the modules' own forward /
-        sample / log_prob paths follow the optimizer without any host-side re-packing"""
-        self.ts.sync()
-        self.refresh_affine()
+    def _pack(self):
+        """the operand dict ConditionalGlow._run reads (glow.py:_packed), on the trainer's device-resident layouts"""
         pk = {"layers": [], "const_parts": self.aff["const_parts"], "aff": self.aff, "wctx": self.wctx, "bctx": self.bctx, "fused": self.fused}
         for l, d in enumerate(self.layers):
-            e = {"A": self.aff["A"][l], "c": self.aff["c"][l], "Ainv": self.aff["Ainv"][l], "cinv": self.aff["cinv"][l], "wx": d["wx"],
-                 "blocks": d["blocks"], "wf": d["wf"], "bf": d["bf"], "T": d["T"], "first": d["first"]}
-            if self.mixed:
-                e["blocks_bf16"] = [bb[:2] for bb in d["blocks_b"]]
-            else:
-                e["blocks_bf16"] = [(w0.to(torch.bfloat16), w1.to(torch.bfloat16)) for (w0, _, w1, _) in d["blocks"]] if self.g.compute_dtype == torch.bfloat16 else None
-            pk["layers"].append(e)
+            pk["layers"].append({"A": self.aff["A"][l], "c": self.aff["c"][l], "Ainv": self.aff["Ainv"][l], "cinv": self.aff["cinv"][l], "wx": d["wx"],
+                                 "blocks": d["blocks"], "wf": d["wf"], "bf": d["bf"], "T": d["T"], "first": d["first"],
+                                 "blocks_bf16": [bb[:2] for bb in d["blocks_b"]] if self.mixed else None})
+        return pk
+
+    def module_pack(self):
+        """_pack for the modules' own forward / sample / log_prob paths: they follow the optimizer without any host-side re-packing"""
+        self.ts.sync()
+        self.refresh_affine()
+        pk = self._pack()
+        if not self.mixed and self.g.compute_dtype == torch.bfloat16:         # (bf16 chosen after this trainer was built)
+            for e, d in zip(pk["layers"], self.layers):
+                e["blocks_bf16"] = [(w0.to(torch.bfloat16), w1.to(torch.bfloat16)) for (w0, _, w1, _) in d["blocks"]]
         return pk
 
     # ------------------------------------------------------------------ sampling pass with tape
@@ -170,7 +169,6 @@ class GlowPart:
         tape = {"v": ts._buf("glow_v", (L, R, 64)), "y": ts._buf("glow_y", (L, R, 64)), "prm": ts._buf("glow_prm", (L, R, 64)),
                 "tb": ts._buf("glow_tb", (L, NB, R, H), bf), "t2": ts._buf("glow_t2", (L, NB, R, H), bf), "t3": ts._buf("glow_t3", (L, NB, R, H), bf),
                 "hf": ts._buf("glow_hf", (L, R, H), bf)}
-        import os
         chain = (os.environ.get("MHE_GLOW_REV_FUSED", "1") == "1" and ops.glow_reverse_chain_supported(R, B, D, H, L, NB))
         if chain:           # what the one-launch reverse chain reads besides t3: parameters in column order, the bf16 layer input, the ReLU gates as bits
             tape.update({"prmc": ts._buf("glow_prmc", (L, R, 128)), "vb": ts._buf("glow_vb", (L, R, 64), bf),
@@ -180,53 +178,14 @@ class GlowPart:
         return x, logq
 
     def forward(self, z0, feat):
-        ts, g = self.ts, self.g
-        L_, D, H, B, R = _lib.lib(), g.features, g.hidden, feat.shape[0], z0.shape[0]
-        import os
+        g, B, R = self.g, feat.shape[0], z0.shape[0]
         if (self.fused is not None and os.environ.get("MHE_GLOW_FUSED", "1") == "1" and R % B == 0
-                and ops.glow_layers_supported(R // B, B, D, H, g.num_layers, g.num_blocks)):
+                and ops.glow_layers_supported(R // B, B, g.features, g.hidden, g.num_layers, g.num_blocks)):
             return self._forward_fused(z0, feat)
         self.refresh_affine()
-        s, dev = ops._stream, z0.device
-        ctab = ops.linear(feat, self.wctx, self.bctx)
-        cs = ctab.shape[1]
-        v = torch.empty(R, 64, device=dev)
-        ops.check(L_.mhe_pad64_f32(ops._ptr(z0), ops._ptr(v), R, D, s()), "mhe_pad64_f32")
-        zp = v
-        logdet = torch.zeros(R, device=dev)
-        tape = [None] * g.num_layers
-        for l in range(g.num_layers - 1, -1, -1):
-            d = self.layers[l]
-            slot = l * self.per
-            h = ops.linear(v, d["wx"])
-            ops.check(L_.mhe_glow_add_image_rows_f32(ops._ptr(h), C.c_void_p(ctab[:, slot * H:].data_ptr()), cs, R, H, 1, B, s()), "mhe_glow_add_image_rows_f32")
-            hs, t2s, t3s, drops = [h], [], [], []
-            for b, (w0, b0, w1, b1) in enumerate(d["blocks"]):
-                if self.mixed:
-                    w0b, w1b = d["blocks_b"][b][:2]
-                    t = torch.empty(R, 1, 1, H, device=dev, dtype=torch.bfloat16)
-                    ops.check(L_.mhe_relu_copy_f32(ops._ptr(hs[-1]), ops._ptr(t), t.numel(), ops.BF16, s()), "mhe_relu_copy_f32")
-                    t2 = ops.conv2d_nhwc(t, w0b, 1, 1, 1, 0, out_shift=b0, relu_out=True)
-                    drops.append(g.dropout_(t2))
-                    t3 = ops.conv2d_nhwc(t2, w1b, 1, 1, 1, 0, out_shift=b1)
-                else:
-                    t = torch.empty_like(h)
-                    ops.check(L_.mhe_relu_copy_f32(ops._ptr(hs[-1]), ops._ptr(t), t.numel(), 0, s()), "mhe_relu_copy_f32")
-                    t2 = ops.linear(t, w0, b0, relu=True)
-                    drops.append(g.dropout_(t2))
-                    t3 = ops.linear(t2, w1, b1)
-                hn = hs[-1].clone()
-                ops.check(L_.mhe_glow_glu_residual_f32(ops._ptr(hn), ops._ptr(t3), ops.dtype_code(t3.dtype), C.c_void_p(ctab[:, (slot + 1 + b) * H:].data_ptr()), cs, R, H, 1, B, s()),
-                          "mhe_glow_glu_residual_f32")
-                hs.append(hn); t2s.append(t2); t3s.append(t3)
-            prm = ops.linear(hs[-1], d["wf"], d["bf"])
-            y = torch.empty(R, 64, device=dev)
-            ops.check(L_.mhe_glow_coupling_f32(ops._ptr(v), ops._ptr(prm), ops._ptr(y), ops._ptr(logdet), R, D, d["first"], d["T"], 1, s()),
-                      "mhe_glow_coupling_f32")
-            tape[l] = {"v": v, "hs": hs, "t2": t2s, "t3": t3s, "prm": prm, "y": y, "drop": drops}
-            v = ops.linear(y, self.aff["Ainv"][l], self.aff["cinv"][l])
-        x, logq = ops.glow_finish(zp, v, logdet, R, D, True, self.aff["const_parts"])
-        self._tp = {"tape": tape, "ctab": ctab, "feat": feat}
+        tape = {"sample_major": True}           # the module's own layer-by-layer pass on sample-major rows (r = n B + b), with its tape
+        x, logq = g._run(z0, feat, True, 1, B, pk=self._pack(), tape=tape, bf16=self.mixed)
+        self._tp = {"glow": tape, "feat": feat}
         return x, logq
 
     # ------------------------------------------------------------------ reverse pass
@@ -322,84 +281,22 @@ class GlowPart:
     def backward(self, g_x, g_logp, N, B):
         """g_x (R,45) = dL/d sample, g_logp (B,) = dL/d log_p per image (None: no entropy term).  Writes every Glow
         parameter's gradient into the trainer's raw arena and returns dL/d feat (B, F) through the context terms."""
-        if self._tp.get("fused") is not None and self.mixed:
-            if self._tp.get("chain"):
-                return self._backward_chain(g_x, g_logp, N, B)
-            return self._backward_fused(g_x, g_logp, N, B)
+        tp = self._tp
+        if "fused" in tp:           # the one-launch kernel's tape (mixed mode)
+            return (self._backward_chain if tp["chain"] else self._backward_fused)(g_x, g_logp, N, B)
         ts, g = self.ts, self.g
         L_, D, H, R = _lib.lib(), g.features, g.hidden, g_x.shape[0]
-        tp = self._tp
-        s, dev = ops._stream, g_x.device
-        raw = lambda o, shape: ts._raw(o, shape)
-        ctab, cs = tp["ctab"], tp["ctab"].shape[1]
-        gv = torch.empty(R, 64, device=dev)
-        ops.check(L_.mhe_pad64_f32(ops._ptr(g_x), ops._ptr(gv), R, D, s()), "mhe_pad64_f32")
-        Gct = torch.zeros(B, cs, device=dev)
-        fused = tp.get("fused")
-        for l in range(g.num_layers):
-            d = rs = self.layers[l]
-            if fused is not None:       # the one-launch kernel's tape: relu(h) of every block and the final layer's operand as bf16
-                bits = tp["bits"]
-                t = {"y": fused["y"][l], "v": fused["v"][l], "prm": fused["prm"][l], "hf": fused["hf"][l],
-                     "tb": [fused["tb"][l, b_].view(R, 1, 1, H) for b_ in range(g.num_blocks)],
-                     "t2": [fused["t2"][l, b_].view(R, 1, 1, H) for b_ in range(g.num_blocks)],
-                     "t3": [fused["t3"][l, b_].view(R, 1, 1, H) for b_ in range(g.num_blocks)],
-                     "drop": [None if bits is None else bits[l, b_] for b_ in range(g.num_blocks)]}
-            else:
-                t = tp["tape"][l]
-            slot = l * self.per
-            ops.linear_wgrad(t["y"], gv, raw(rs["r_ainv"], (64, 64))); ops.colsum(gv, raw(rs["r_cinv"], (64,)))
-            gy = ops.linear(gv, self.aff["AinvT"][l])
-            gvc, gprm = torch.empty(R, 64, device=dev), torch.empty(R, 64, device=dev)
-            ops.check(L_.mhe_glow_coupling_inv_bwd_f32(ops._ptr(t["v"]), ops._ptr(t["prm"]), ops._ptr(gy), ops._ptr(g_logp), -1.0 / N,
-                                                       ops._ptr(gvc), ops._ptr(gprm), R, B, D, d["first"], d["T"], s()), "mhe_glow_coupling_inv_bwd_f32")
-            if fused is not None:       # the final layer's operand was kept as bf16: its weight gradient on bf16 operands, f32 accumulation
-                ops.conv_wgrad(t["hf"].view(R, 1, 1, H), gprm.to(torch.bfloat16).view(R, 1, 1, 64), 1, 1, 1, 0, raw(rs["r_wf"], (64, H)))
-            else:
-                ops.linear_wgrad(t["hs"][-1], gprm, raw(rs["r_wf"], (64, H)))
-            ops.colsum(gprm, raw(rs["r_bf"], (64,)))
-            gh = ops.linear(gprm, d["wfT"])
-            for b in range(g.num_blocks - 1, -1, -1):
-                rb = rs["r_blocks"][b]
-                w0T, w1T = d["blocksT"][b]
-                t3b, t2b = t["t3"][b], t["t2"][b]
-                gt3, ggate = torch.empty_like(t3b), torch.empty(R, H, device=dev)
-                ops.check(L_.mhe_glow_glu_bwd_f32(ops._ptr(gh), ops._ptr(t3b), C.c_void_p(ctab[:, (slot + 1 + b) * H:].data_ptr()), cs,
-                                                  ops._ptr(gt3), ops._ptr(ggate), R, H, 1, B, ops.dtype_code(t3b.dtype), s()), "mhe_glow_glu_bwd_f32")
-                ops.sum_over_hypotheses(ggate, N, B, out=Gct[:, (slot + 1 + b) * H:], out_stride=cs)
-                if self.mixed:
-                    # the four h x h products of the block's reverse pass on bf16 MFMA; bias sums from an f32 view of the bf16 gradient
-                    _, _, w0Tb, w1Tb = d["blocks_b"][b]
-                    ops.conv_wgrad(t2b, gt3, 1, 1, 1, 0, raw(rb["w1"], (H, H))); ops.colsum(gt3, raw(rb["b1"], (H,)))
-                    gt2 = ops.conv2d_nhwc(gt3, w1Tb, 1, 1, 1, 0)
-                    if t["drop"][b] is not None:          # dropout's reverse: the same mask and scale on the gradient
-                        ops.dropout_(gt2, g.p_drop, bits=t["drop"][b])
-                    ops.flow_lrelu_bwd_mixed(gt2.view(R, H), t2b.view(R, H), out_bf16=gt2.view(R, H), slope=0.0)
-                    if fused is not None:
-                        tt = t["tb"][b]
-                    else:
-                        tt = torch.empty(R, 1, 1, H, device=dev, dtype=torch.bfloat16)
-                        ops.check(L_.mhe_relu_copy_f32(ops._ptr(t["hs"][b]), ops._ptr(tt), tt.numel(), ops.BF16, s()), "mhe_relu_copy_f32")
-                    ops.conv_wgrad(tt, gt2, 1, 1, 1, 0, raw(rb["w0"], (H, H))); ops.colsum(gt2, raw(rb["b0"], (H,)))
-                    gt = ops.conv2d_nhwc(gt2, w0Tb, 1, 1, 1, 0)
-                    if fused is not None:       # relu(h) > 0  <=>  h > 0: the gate from the kept bf16 activation
-                        ops.check(L_.mhe_relu_bwd_add_mixed(ops._ptr(gh), ops._ptr(gt), ops._ptr(tt), gh.numel(), ops.BF16, ops.BF16, s()), "mhe_relu_bwd_add_mixed")
-                    else:
-                        ops.check(L_.mhe_relu_bwd_add_f32(ops._ptr(gh), ops._ptr(gt), ops._ptr(t["hs"][b]), gh.numel(), ops.BF16, s()), "mhe_relu_bwd_add_f32")
-                    continue
-                ops.linear_wgrad(t2b, gt3, raw(rb["w1"], (H, H))); ops.colsum(gt3, raw(rb["b1"], (H,)))
-                gt2 = ops.linear(gt3, w1T)
-                if t["drop"][b] is not None:
-                    ops.dropout_(gt2, g.p_drop, bits=t["drop"][b])
-                ops.flow_lrelu_bwd(gt2, t2b, slope=0.0)
-                tt = torch.empty(R, H, device=dev)
-                ops.check(L_.mhe_relu_copy_f32(ops._ptr(t["hs"][b]), ops._ptr(tt), tt.numel(), 0, s()), "mhe_relu_copy_f32")
-                ops.linear_wgrad(tt, gt2, raw(rb["w0"], (H, H))); ops.colsum(gt2, raw(rb["b0"], (H,)))
-                gt = ops.linear(gt2, w0T)
-                ops.check(L_.mhe_relu_bwd_add_f32(ops._ptr(gh), ops._ptr(gt), ops._ptr(t["hs"][b]), gh.numel(), 0, s()), "mhe_relu_bwd_add_f32")
-            ops.linear_wgrad(t["v"], gh, raw(rs["r_wx"], (H, 64)))
-            ops.sum_over_hypotheses(gh, N, B, out=Gct[:, slot * H:], out_stride=cs)
-            gv = ops.add(gvc, ops.linear(gh, d["wxT"]))
+        raw, cs = ts._raw, tp["glow"]["ctab"].shape[1]
+        gv = torch.empty(R, 64, device=g_x.device)
+        ops.check(L_.mhe_pad64_f32(ops._ptr(g_x), ops._ptr(gv), R, D, ops._stream()), "mhe_pad64_f32")
+        Gct = torch.zeros(B, cs, device=g_x.device)
+        # the staged reverse (glow.py: ConditionalGlow._reverse) with the gradients landing in the raw arena
+        layers = [{"AinvT": self.aff["AinvT"][l], "wfT": d["wfT"], "wxT": d["wxT"], "blocksT": [bb[2:] for bb in d["blocks_b"]] if self.mixed else d["blocksT"],
+                   "dAinv": raw(d["r_ainv"], (64, 64)), "dcinv": raw(d["r_cinv"], (64,)), "dwf": raw(d["r_wf"], (64, H)), "dbf": raw(d["r_bf"], (64,)),
+                   "dwx": raw(d["r_wx"], (H, 64)),
+                   "dblocks": [(raw(rb["w0"], (H, H)), raw(rb["b0"], (H,)), raw(rb["w1"], (H, H)), raw(rb["b1"], (H,))) for rb in d["r_blocks"]]}
+                  for l, d in enumerate(self.layers)]
+        g._reverse(tp["glow"], gv, g_logp, Gct, layers)
         ops.linear_wgrad(tp["feat"], Gct, raw(self.raw_wctx, (cs, g.context_features))); ops.colsum(Gct, raw(self.raw_bctx, (cs,)))
         g_feat = ops.linear(Gct, self.wctxT)
         self._reparam_backward(g_logp)

@@ -1,4 +1,4 @@
-"""GPU tests of the body flow head's reverse pass (BodyFlowHead under grad, mhentropy_amd/glow_grad.py): the new kernels - the wide float64 affine
+"""GPU tests of the body flow head's reverse pass (BodyFlowHead under grad: body._flow_backward over glow.ConditionalGlow._reverse): the new kernels - the wide float64 affine
 map and its reverse (csrc/glow_affine_wide.hip), the wide coupling reverse (csrc/glow.hip), the joint reverse (csrc/body.hip) - and the whole head,
 each against torch autograd in float64 on CPU over the oracle chain (oracle/glow_ref.py -> oracle/rot6d_ref.py -> oracle/body_ref.py)."""
 import numpy as np
@@ -152,11 +152,11 @@ def _inputs(B, K, Fc, seed=3):
     return feats, noise, betas
 
 
-def _loss(out, target, w):
-    return out["log_prob"][:, 1:].mean() + (w * (out["joints"] - target).abs()).sum() + 0.1 * out["pose6d"].square().mean()
+def _loss(out, target, w, lp_from=1):
+    return out["log_prob"][:, lp_from:].mean() + (w * (out["joints"] - target).abs()).sum() + 0.1 * out["pose6d"].square().mean()
 
 
-def _check_head(Fc, H, L, NB, B, K, hyp_slice, bound):
+def _check_head(Fc, H, L, NB, B, K, hyp_slice, bound, lp_from=1):
     from oracle import glow_ref, rot6d_ref, body_ref
     head, sd, tables = _head(Fc, H, L, NB)
     feats, noise, betas = _inputs(B, K, Fc)
@@ -166,7 +166,7 @@ def _check_head(Fc, H, L, NB, B, K, hyp_slice, bound):
     w = rng.random((B, hi - lo, 24, 1)).astype(np.float32) / (B * (hi - lo))
     f, b = torch.as_tensor(feats).cuda().requires_grad_(), torch.as_tensor(betas).cuda().requires_grad_()
     out = head(f, K, betas=b, noise=torch.as_tensor(noise).cuda(), hyp_slice=hyp_slice, want_verts=False)
-    _loss(out, torch.as_tensor(target).cuda(), torch.as_tensor(w).cuda()).backward()
+    _loss(out, torch.as_tensor(target).cuda(), torch.as_tensor(w).cuda(), lp_from).backward()
     # f64 oracle chain
     sd64 = {k: _f64(v).requires_grad_() for k, v in sd.items()}
     f64, b64 = _f64(feats).requires_grad_(), _f64(betas).requires_grad_()
@@ -175,7 +175,7 @@ def _check_head(Fc, H, L, NB, B, K, hyp_slice, bound):
     rm = rot6d_ref.rotation_from_ortho6d(p)
     tb = {k: (_f64(v) if np.asarray(v).dtype.kind == "f" else torch.as_tensor(v)) for k, v in tables.items()}
     _, joints = body_ref.lbs(tb, rm, b64.repeat_interleave(hi - lo, 0))
-    _loss({"log_prob": lp, "joints": joints.view(B, hi - lo, 24, 3), "pose6d": x}, _f64(target), _f64(w)).backward()
+    _loss({"log_prob": lp, "joints": joints.view(B, hi - lo, 24, 3), "pose6d": x}, _f64(target), _f64(w), lp_from).backward()
     errs = {"feats": _rel_l2(f.grad.cpu(), f64.grad), "betas": _rel_l2(b.grad.cpu(), b64.grad)}
     for name, prm in head.flow.named_parameters():
         assert prm.grad is not None, name
@@ -194,6 +194,12 @@ def test_head_gradients_small_geometry(gpu_lib, hyp_slice):
 def test_head_gradients_prohmr_geometry(gpu_lib):
     """hidden 1024, 4 layers x 2 blocks, context 2048, B = 4, K = 8.  Measured on an MI355X: worst per-tensor rel-L2 2.9e-6 (bound 1e-3)."""
     _check_head(2048, 1024, 4, 2, 4, 8, None, 1e-3)
+
+
+@pytest.mark.parametrize("Fc, H, L, NB", [(256, 128, 2, 1), (2048, 1024, 4, 2)])
+def test_head_gradients_one_sample(gpu_lib, Fc, H, L, NB):
+    """K = 1 (ProHMR's mode sample, ConditionalGlow.forward's default): one row per image, with the log-probability itself in the loss"""
+    _check_head(Fc, H, L, NB, 2, 1, None, 1e-4 if H == 128 else 1e-3, lp_from=0)
 
 
 def test_grad_forward_equals_eval_forward(gpu_lib):

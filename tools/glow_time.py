@@ -23,4 +23,4 @@ g45 = torch.randn(K * B, 45, device="cuda"); gl = torch.full((B,), -1.0 / B, dev
 ts.raw.zero_()
 print("glow bwd", T(lambda: ts.glow.backward(g45, gl, K, B)))
 print("reparam", T(lambda: ts.glow._reparam_backward(gl)))
-print("pack", T(lambda: (ts.glow.invalidate(), ts.glow._pack())))
+print("pack", T(lambda: ts.glow._pack()))
