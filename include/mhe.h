@@ -840,6 +840,24 @@ int mhe_glow_affine_wide_bwd_f64(const float *g_ainv, const float *g_cinv, const
  * (NULL: none).  Formulas: csrc/glow.hip. */
 int mhe_glow_coupling_inv_bwd_wide_f32(const float *v, const float *params, const float *g_y, const float *g_log_q, float *g_v,
                                        float *g_params, long R, int dim, int first, int n_transform, int ld, int ldp, void *stream);
+/* The reverse of the DENSITY direction (pose -> noise; maximum-likelihood training of ConditionalGlow.log_prob).
+ * mhe_glow_coupling_fwd_bwd_f32: reverse of the FORWARD coupling (mhe_glow_coupling_f32 with inverse = 0) at row pitches ld / ldp, multiples of 64
+ * up to 256, 2 n_transform <= ldp: g_v [R][ld] (padding columns zero), g_params [R][ldp] = [d shift | d unconstrained scale | 0]; g_log_p [R] =
+ * dL/dlog p per row (NULL: none).  mhe_glow_base_density_bwd_f32: g_y [R][ld] = g_z - g_log_p[r] z on the padded rows (g_z [R][dim] unpadded |
+ * NULL, g_log_p [R] | NULL), the gradient that enters the last layer.  Formulas: csrc/glow.hip. */
+int mhe_glow_coupling_fwd_bwd_f32(const float *v, const float *params, const float *g_y, const float *g_log_p, float *g_v,
+                                  float *g_params, long R, int dim, int first, int n_transform, int ld, int ldp, void *stream);
+int mhe_glow_base_density_bwd_f32(const float *z_padded, const float *g_z, const float *g_log_p, float *g_y, long R, int dim, int ld,
+                                  void *stream);
+/* ... and of the ActNorm + LU re-parameterisation in that direction, where v = A u + c is applied as it stands: dL/dA (g_a [layers][Dp][Dp]),
+ * dL/dc (g_c [layers][Dp]), Dp = ceil64(features), and dL/dlog p of every row (g_log_p [n_log_p], may be NULL with n_log_p = 0; S = their sum, in
+ * a fixed order) -> float64 gradients in the layout of mhe_glow_affine_wide_bwd_f64 (mhe_glow_affine_wide_grad_doubles(layers, features) in all).
+ * The narrow form (features <= 64) reads the workspace of mhe_glow_affine_f64, the wide one that of mhe_glow_affine_wide_f64 (and overwrites its
+ * scratch part).  No inverse is taken and no atomics are used: bit-identical runs.  Formulas: csrc/glow_affine.hip. */
+int mhe_glow_affine_density_bwd_f64(const float *g_a, const float *g_c, const float *g_log_p, long n_log_p, int layers, int features,
+                                    const double *workspace, double *grads, void *stream);
+int mhe_glow_affine_wide_density_bwd_f64(const float *g_a, const float *g_c, const float *g_log_p, long n_log_p, int layers, int features,
+                                         double *workspace, double *grads, void *stream);
 /* out[g * out_stride + c] (+)= sum_{n < N} rows[(g N + n) C + c]: per-image sums of batch-major rows (r = b N + n), in n order */
 int mhe_sum_row_blocks_f32(const float *rows, float *out, int groups, int N, int C, long out_stride, int accumulate, void *stream);
 /* Reverse of the posed joints of mhe_lbs_pose_f32 (csrc/body.hip; one wavefront per hypothesis, J <= 32, any tree with parents[j] < j):

@@ -114,6 +114,10 @@ SIGNATURES = {
     "mhe_glow_affine_wide_f64": (_i, [_p, _i, _i, _d] + [_p] * 7 + [_p]),
     "mhe_glow_affine_wide_bwd_f64": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p]),
     "mhe_glow_coupling_inv_bwd_wide_f32": (_i, [_p] * 6 + [_l, _i, _i, _i, _i, _i, _p]),
+    "mhe_glow_coupling_fwd_bwd_f32": (_i, [_p] * 6 + [_l, _i, _i, _i, _i, _i, _p]),
+    "mhe_glow_base_density_bwd_f32": (_i, [_p] * 4 + [_l, _i, _i, _p]),
+    "mhe_glow_affine_density_bwd_f64": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p]),
+    "mhe_glow_affine_wide_density_bwd_f64": (_i, [_p, _p, _p, _l, _i, _i, _p, _p, _p]),
     "mhe_sum_row_blocks_f32": (_i, [_p, _p, _i, _i, _i, _l, _i, _p]),
     "mhe_mano_regress_joints_f32": (_i, [_p, _p, _p, _i, _p]),
     "mhe_elbo_reduce_f32": (_i, [_p, _p, _p, _p, _p, _i, _i, _p]),

@@ -51,6 +51,14 @@ def rot6d_to_rotmat(poses6, robust=False):
     return out.view(*poses6.shape[:-1], 3, 3)
 
 
+def rotmat_to_rot6d(rotmats):
+    """(..., 3, 3) -> (..., 6): the first two COLUMNS [R[:, 0] | R[:, 1]], the layout rot6d_to_rotmat reads (reference hand/manopth/rot6d.py:12-23),
+    so that rot6d_to_rotmat(rotmat_to_rot6d(R)) == R for a rotation R.  A re-arrangement only (no arithmetic; any device)"""
+    if rotmats.shape[-2:] != (3, 3):
+        raise ValueError(f"rotmat_to_rot6d: (..., 3, 3) expected, got {tuple(rotmats.shape)}")
+    return torch.cat([rotmats[..., :, 0], rotmats[..., :, 1]], -1)
+
+
 def rot6d_to_rotmat_bwd(poses6, g_rotmats):
     p, g = poses6.reshape(-1, 6), g_rotmats.reshape(-1, 9)
     ops._chk(p, torch.float32, "rot6d.poses"); ops._chk(g, torch.float32, "rot6d.g", (p.shape[0], 9))
@@ -138,7 +146,9 @@ class BodyLayer(nn.Module):
 class BodyFlowHead(nn.Module):
     """ProHMR's sampling surface (reference README.md:26-42): `flow(conditioning_feats, num_samples)` draws K poses with
     log-probabilities from a ConditionalGlow over the 144-D 6D pose (features 144, hidden 1024, 4 layers x 2 blocks, context
-    2048: SURVEY.md appendix A5), decoded by the body layer.  Parity unpinned (ProHMR's SMPLFlow is out of tree)."""
+    2048: SURVEY.md appendix A5), decoded by the body layer; and its likelihood surface `log_prob(feats, pose6d= | rotmats=)` (README.md:32-34: the
+    NLL on annotated poses).  Both are trainable: the sampling direction's tape and reverse (_HeadFn) and the density direction's
+    (ConditionalGlow.log_prob under grad).  Parity unpinned (ProHMR's SMPLFlow is out of tree)."""
     def __init__(self, tables, context_features=2048, hidden=1024, num_layers=4, num_blocks=2):
         super().__init__()
         from .glow import ConditionalGlow
@@ -179,6 +189,17 @@ class BodyFlowHead(nn.Module):
         if want_verts:
             res["vertices"] = out["vertices"].view(B, hi - lo, self.body.NV, 3)
         return res
+
+    def log_prob(self, feats, pose6d=None, rotmats=None):
+        """ProHMR's NLL call form `flow.log_prob(smpl_params, conditioning_feats)` (reference README.md:32-34): one annotated pose per context row,
+        pose6d (R, 6J) or rotmats (R, J, 3, 3) (exactly one; rotations are re-arranged by rotmat_to_rot6d) -> (log_prob (R,), z (R, 6J)).
+        Differentiable under ConditionalGlow.log_prob's rule, so `-head.log_prob(f, rotmats=M)[0].mean()` trains the flow by maximum likelihood,
+        alone or in one loss with the entropy term of `forward`."""
+        if (pose6d is None) == (rotmats is None):
+            raise ValueError("BodyFlowHead.log_prob: give exactly one of pose6d and rotmats")
+        if pose6d is None:
+            pose6d = rotmat_to_rot6d(rotmats)
+        return self.flow.log_prob(pose6d.reshape(-1, self.flow.features), feats)
 
 
 def lbs_pose_bwd(layer, rotmats, betas, g_joints):
@@ -240,9 +261,9 @@ def _flow_backward(g, tp, g_x, g_logq):
     per-image rows, dL/dcontext and the ActNorm / LU gradients from dA^-1, dc^-1 and sum dL/dlog q in float64 (mhe_glow_affine_wide_bwd_f64).
     g_x (B N, D) = dL/dx (or None), g_logq (B N,) = dL/dlog_prob (or None) -> ({parameter: gradient}, dL/dcontext (B, F)).  The noise is an
     input, not differentiated."""
-    D, H, Lr, Dp = g.features, g.hidden, g.num_layers, g.Dp
+    D, Lr, Dp = g.features, g.num_layers, g.Dp
     pk, aff, ctab, B = tp["pk"], tp["aff"], tp["ctab"], tp["n_img"]
-    R, cs, per, dev = B * tp["row_div"], ctab.shape[1], 1 + g.num_blocks, ctab.device
+    R, cs, dev = B * tp["row_div"], ctab.shape[1], ctab.device
     gv = torch.zeros(R, Dp, device=dev)
     if g_x is not None:
         ops.check(_lib.lib().mhe_pad64_f32(ops._ptr(g_x), ops._ptr(gv), R, D, ops._stream()), "mhe_pad64_f32")
@@ -251,8 +272,7 @@ def _flow_backward(g, tp, g_x, g_logq):
     Gct = torch.zeros(B, cs, device=dev)
     dAinv, dcinv = torch.zeros(Lr, Dp, Dp, device=dev), torch.empty(Lr, Dp, device=dev)
     z = lambda *shape: torch.zeros(*shape, device=dev)
-    dst = [{"dAinv": dAinv[l], "dcinv": dcinv[l], "dwf": z(d["wf"].shape[0], H), "dbf": torch.empty(d["wf"].shape[0], device=dev), "dwx": z(H, Dp),
-            "dblocks": [(z(H, H), z(H), z(H, H), z(H)) for _ in d["blocks"]]} for l, d in enumerate(pk["layers"])]
+    dst = [{**o, "dAinv": dAinv[l], "dcinv": dcinv[l]} for l, o in enumerate(g._net_grad_buffers(pk, dev))]
     # the transposed operands one layer at a time, as the reverse reaches it
     g._reverse(tp, gv, g_logq, Gct, ({**o, "AinvT": aff["AinvT"][l], "wfT": d["wf"].t().contiguous(), "wxT": d["wx"].t().contiguous(),
                                       "blocksT": [(w0.t().contiguous(), w1.t().contiguous()) for (w0, _, w1, _) in d["blocks"]]}
@@ -261,22 +281,7 @@ def _flow_backward(g, tp, g_x, g_logq):
     ops.linear_wgrad(tp["context"], Gct, dW); ops.colsum(Gct, db)
     g_ctx = ops.linear(Gct, pk["wctx"].t().contiguous())
     ga = ops.glow_affine_wide_bwd(dAinv, dcinv, g_logq, Lr, D, aff["ws"]).float()
-    T, n, grads = g._transform._transforms, D * (D - 1) // 2, {}
-    for l, (d, o) in enumerate(zip(pk["layers"], dst)):
-        an, lu, cp = T[3 * l], T[3 * l + 1], T[3 * l + 2]
-        net, r, slot = cp.transform_net, ga[l], l * per
-        grads[an.log_scale], grads[an.shift] = r[:D], r[D:2 * D]
-        grads[lu.lower_entries], grads[lu.upper_entries] = r[2 * D:2 * D + n], r[2 * D + n:2 * D + 2 * n]
-        grads[lu.unconstrained_upper_diag], grads[lu.bias] = r[2 * D + 2 * n:3 * D + 2 * n], r[3 * D + 2 * n:]
-        grads[net.initial_layer.weight] = torch.cat([o["dwx"][:, cp.identity_features], dW[slot * H:(slot + 1) * H]], 1)
-        grads[net.initial_layer.bias] = db[slot * H:(slot + 1) * H]
-        grads[net.final_layer.weight], grads[net.final_layer.bias] = o["dwf"][:2 * d["T"]], o["dbf"][:2 * d["T"]]
-        for b, (blk, (dw0, db0, dw1, db1)) in enumerate(zip(net.blocks, o["dblocks"])):
-            k = slot + 1 + b
-            grads[blk.linear_layers[0].weight], grads[blk.linear_layers[0].bias] = dw0, db0
-            grads[blk.linear_layers[1].weight], grads[blk.linear_layers[1].bias] = dw1, db1
-            grads[blk.context_layer.weight], grads[blk.context_layer.bias] = dW[k * H:(k + 1) * H], db[k * H:(k + 1) * H]
-    return grads, g_ctx
+    return g._grads_by_param(pk, dst, dW, db, ga), g_ctx
 
 
 class _HeadFn(torch.autograd.Function):

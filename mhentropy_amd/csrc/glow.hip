@@ -134,6 +134,49 @@ __global__ __launch_bounds__(256) void coupling_inv_bwd_wide_kernel(const float 
     }
 }
 
+// Reverse of the FORWARD coupling (the density direction, pose -> noise, which maximum-likelihood training differentiates):
+//   y_t = v_t * scale + shift, scale = sigmoid(us + 2) + 1e-3, and log p gains + sum_t log scale
+// given g_y = dL/dy and a_p = dL/dlog p per row (g_logp[r]; NULL: none):  g_v_t = g_y_t scale (identity columns pass through),
+// g_prm [R, ldp] = [d shift (T) = g_y_t | d us (T) = (g_y_t v_t + a_p / scale) sig (1 - sig) | 0].  Row pitches ld / ldp: multiples of 64 up to 256.
+__global__ __launch_bounds__(256) void coupling_fwd_bwd_kernel(const float *__restrict__ v, const float *__restrict__ prm,
+                                                               const float *__restrict__ g_y, const float *__restrict__ g_logp,
+                                                               float *__restrict__ g_v, float *__restrict__ g_prm, long R, int dim, int first,
+                                                               int T, int ld, int ldp) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const float a_p = g_logp ? g_logp[r] : 0.f;
+    for (int c = 2 * T + lane; c < ldp; c += 64) g_prm[r * ldp + c] = 0.f;
+    for (int c = lane; c < ld; c += 64) {
+        const float gy = c < dim ? g_y[r * ld + c] : 0.f;
+        float gv = gy;
+        const int j = (c - first) >> 1;
+        if (c < dim && c >= first && ((c - first) & 1) == 0 && j < T) {
+            const float us = prm[r * ldp + T + j];
+            const float sig = 1.f / (1.f + expf(-(us + 2.f))), scale = sig + 1e-3f;
+            gv = gy * scale;
+            g_prm[r * ldp + j] = gy;
+            g_prm[r * ldp + T + j] = (gy * v[r * ld + c] + a_p / scale) * sig * (1.f - sig);
+        }
+        g_v[r * ld + c] = gv;
+    }
+}
+
+// Reverse of the base density of the density direction: log p = -|z|^2 / 2 + ..., and z itself is returned, so
+//   g_y [R, ld] = g_z - g_logp[r] z   on the padded rows (g_z [R, dim] unpadded or NULL, g_logp [R] or NULL; padding columns zero)
+__global__ __launch_bounds__(256) void base_density_bwd_kernel(const float *__restrict__ zp, const float *__restrict__ g_z,
+                                                               const float *__restrict__ g_logp, float *__restrict__ g_y, long R, int dim, int ld) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const float a_p = g_logp ? g_logp[r] : 0.f;
+    for (int c = lane; c < ld; c += 64) {
+        float g = 0.f;
+        if (c < dim) g = (g_z ? g_z[r * dim + c] : 0.f) - a_p * zp[r * ld + c];
+        g_y[r * ld + c] = g;
+    }
+}
+
 // out[g * out_stride + c] (+)= sum_{n < N} rows[(g N + n) C + c]: per-image sums of batch-major rows (r = b N + n), summed in n order
 __global__ __launch_bounds__(256) void sum_row_blocks_kernel(const float *__restrict__ rows, float *__restrict__ out, int G, int N, int C,
                                                              long out_stride, int accumulate) {
@@ -368,6 +411,29 @@ extern "C" int mhe_glow_coupling_inv_bwd_wide_f32(const float *v, const float *p
     hipLaunchKernelGGL(glow::coupling_inv_bwd_wide_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, v, params, g_y, g_log_q,
                        g_v, g_params, R, dim, first, n_transform, ld, ldp);
     return check_launch("coupling_inv_bwd_wide_kernel");
+}
+
+extern "C" int mhe_glow_coupling_fwd_bwd_f32(const float *v, const float *params, const float *g_y, const float *g_log_p, float *g_v,
+                                             float *g_params, long R, int dim, int first, int n_transform, int ld, int ldp, void *stream) {
+    MHE_REQUIRE(R > 0 && dim > 0 && ld % 64 == 0 && ld >= dim && ld <= 256 && ldp % 64 == 0 && ldp > 0 && ldp <= 256 && (first == 0 || first == 1) &&
+                    n_transform > 0 && first + 2 * (n_transform - 1) < dim && 2 * n_transform <= ldp && R <= (1l << 40) / ld,
+                "mhe_glow_coupling_fwd_bwd_f32: bad arguments (R=%ld dim=%d first=%d T=%d ld=%d ldp=%d)", R, dim, first, n_transform, ld, ldp);
+    MHE_REQUIRE(on_device(v) && on_device(params) && on_device(g_y) && on_device(g_v) && on_device(g_params) && (!g_log_p || on_device(g_log_p)),
+                "mhe_glow_coupling_fwd_bwd_f32: every buffer must be device memory");
+    hipLaunchKernelGGL(glow::coupling_fwd_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, v, params, g_y, g_log_p,
+                       g_v, g_params, R, dim, first, n_transform, ld, ldp);
+    return check_launch("coupling_fwd_bwd_kernel");
+}
+
+extern "C" int mhe_glow_base_density_bwd_f32(const float *z_padded, const float *g_z, const float *g_log_p, float *g_y, long R, int dim, int ld,
+                                             void *stream) {
+    MHE_REQUIRE(R > 0 && dim > 0 && ld % 64 == 0 && ld >= dim && ld <= 256 && R <= (1l << 40) / ld,
+                "mhe_glow_base_density_bwd_f32: bad arguments (R=%ld dim=%d ld=%d)", R, dim, ld);
+    MHE_REQUIRE(on_device(z_padded) && on_device(g_y) && (!g_z || on_device(g_z)) && (!g_log_p || on_device(g_log_p)),
+                "mhe_glow_base_density_bwd_f32: every buffer must be device memory");
+    hipLaunchKernelGGL(glow::base_density_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, z_padded, g_z, g_log_p, g_y,
+                       R, dim, ld);
+    return check_launch("base_density_bwd_kernel");
 }
 
 extern "C" int mhe_sum_row_blocks_f32(const float *rows, float *out, int groups, int N, int C, long out_stride, int accumulate, void *stream) {

@@ -195,6 +195,61 @@ __global__ __launch_bounds__(NT) void reparam_bwd_kernel(const float *const *__r
     }
 }
 
+// The DENSITY direction's reverse (pose -> noise: v = A u + c is applied as it stands, so the gradients arrive on A and c themselves and no
+// inverse is differentiated): dA [layers][64][64], dc [layers][64] (f32) and dL/dlog p per row, S = their sum (every layer's constant enters every
+// row's log-probability with weight +1) ->
+//   dW = dA diag(s) + dc shift^T;  dlog_scale = colsum(dA o W) s + S;  dshift = W^T dc;  dbias = dc;  dL = dW U^T (strict lower);
+//   dU = L^T dW (upper);  dudiag = (diag(dU) + S / diag) sigmoid(udiag)
+// as float64, packed per layer [log_scale D | shift D | lower n | upper n | udiag D | bias D], n = D (D - 1) / 2 (the layout of
+// mhe_glow_affine_wide_bwd_f64).  S is summed by thread in a strided, then a tree order: fixed, so runs are bit-identical.
+__host__ __device__ __forceinline__ size_t grad_stride(int D) { return (size_t)4 * D + (size_t)D * (D - 1); }
+
+__global__ __launch_bounds__(NT) void density_bwd_kernel(const float *__restrict__ g_a, const float *__restrict__ g_c, const float *__restrict__ g_logp,
+                                                         long n_logp, int D, const double *__restrict__ ws, double *__restrict__ grads) {
+    __shared__ double dA[MAXD * MAXD], dW[MAXD * MAXD];       // 64 KiB
+    __shared__ double dc[MAXD], red[NT];
+    const int l = blockIdx.x, tid = threadIdx.x;
+    const double *w = ws + (size_t)l * ws_doubles(D);
+    const double *wL = w, *wU = w + D * D, *wW = w + 2 * D * D, *wv = w + 4 * D * D;
+    const double *sc = wv, *sh = wv + D, *dg = wv + 2 * D, *ud = wv + 3 * D;
+    double *g = grads + (size_t)l * grad_stride(D);
+    const size_t n = (size_t)D * (D - 1) / 2;
+    double s = 0.0;
+    for (long i = tid; i < n_logp; i += NT) s += (double)g_logp[i];
+    red[tid] = s;
+    if (tid < D) dc[tid] = (double)g_c[(size_t)l * 64 + tid];
+    __syncthreads();
+    for (int o = NT / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+    const double S = red[0];
+    for (int i = tid; i < D * D; i += NT) {
+        const int r = i / D, k = i % D;
+        const double a = (double)g_a[(size_t)l * 4096 + r * 64 + k];
+        dA[i] = a;
+        dW[i] = a * sc[k] + dc[r] * sh[k];
+    }
+    __syncthreads();
+    if (tid < D) {
+        double a = 0.0, b = 0.0;
+        for (int m = 0; m < D; ++m) { a = fma(dA[m * D + tid], wW[m * D + tid], a); b = fma(wW[m * D + tid], dc[m], b); }
+        g[tid] = a * sc[tid] + S;                               // log_scale
+        g[D + tid] = b;                                         // shift
+        g[3 * D + 2 * n + tid] = dc[tid];                       // bias
+    }
+    for (int i = tid; i < D * D; i += NT) {
+        const int r = i / D, k = i % D;
+        if (r > k) {                                            // dL = dW U^T, strictly lower entries (U[k][m] = 0 for m < k)
+            double a = 0.0;
+            for (int m = k; m < D; ++m) a = fma(dW[r * D + m], wU[k * D + m], a);
+            g[2 * D + low_idx(r, k)] = a;
+        } else {                                                // dU = L^T dW, upper entries and the diagonal (L[m][r] = 0 for m < r)
+            double a = 0.0;
+            for (int m = r; m < D; ++m) a = fma(wL[m * D + r], dW[m * D + k], a);
+            if (r < k) g[2 * D + n + up_idx(r, k, D)] = a;
+            else g[2 * D + 2 * n + r] = (a + S / dg[r]) / (1.0 + exp(-ud[r]));
+        }
+    }
+}
+
 }}  // namespace mhe::glowaff
 
 using namespace mhe;
@@ -219,4 +274,15 @@ extern "C" int mhe_glow_reparam_bwd_f64(const void *g_ainv_ptrs, const void *g_c
     hipLaunchKernelGGL(glowaff::reparam_bwd_kernel, dim3(layers), dim3(glowaff::NT), 0, (hipStream_t)stream, (const float *const *)g_ainv_ptrs,
                        (const float *const *)g_cinv_ptrs, g_log_p, g_log_p ? n_log_p : 0, q_sign, features, workspace, (const glowaff::GPtrs *)grad_ptrs);
     return check_launch("glowaff::reparam_bwd_kernel");
+}
+
+extern "C" int mhe_glow_affine_density_bwd_f64(const float *g_a, const float *g_c, const float *g_log_p, long n_log_p, int layers, int features,
+                                               const double *workspace, double *grads, void *stream) {
+    MHE_REQUIRE(layers > 0 && layers <= 65535 && features > 1 && features <= glowaff::MAXD && n_log_p >= 0 && (n_log_p == 0 || g_log_p),
+                "mhe_glow_affine_density_bwd_f64: features=%d (2..%d), layers=%d, n_log_p=%ld", features, glowaff::MAXD, layers, n_log_p);
+    MHE_REQUIRE(on_device(g_a) && on_device(g_c) && on_device(workspace) && on_device(grads) && (n_log_p == 0 || on_device(g_log_p)),
+                "mhe_glow_affine_density_bwd_f64: every buffer must be device memory");
+    hipLaunchKernelGGL(glowaff::density_bwd_kernel, dim3(layers), dim3(glowaff::NT), 0, (hipStream_t)stream, g_a, g_c, n_log_p ? g_log_p : nullptr,
+                       n_log_p, features, workspace, grads);
+    return check_launch("glowaff::density_bwd_kernel");
 }

@@ -242,6 +242,33 @@ __global__ __launch_bounds__(NT) void bwd_lu_kernel(int D, double *__restrict__ 
     }
 }
 
+// ---- reverse of the DENSITY direction ---------------------------------------------------------------------------------------------------
+// v = A u + c is applied as it stands, so the gradients arrive on A and c themselves (formulas: csrc/glow_affine.hip, density_bwd_kernel):
+// dA (f64 copy) -> slot 8, dW = dA diag(s) + dc shift^T -> slot 6, dc -> its vector, S = sum_r dL/dlog p[r] (block 0: strided partial sums, then a
+// tree over the 256 threads - a fixed order); bwd_vec_kernel and bwd_lu_kernel then finish exactly as for the sampling direction.
+__global__ __launch_bounds__(NT) void bwd_density_kernel(const float *__restrict__ g_a, const float *__restrict__ g_c, const float *__restrict__ g_logp,
+                                                         long n_logp, int D, int Dp, double *__restrict__ ws) {
+    __shared__ double red[NT];
+    const int l = blockIdx.y, tid = threadIdx.x;
+    WS w = ws_at(ws, l, D);
+    const int i = blockIdx.x * NT + tid;
+    if (i < D * D) {
+        const int r = i / D, k = i % D;
+        const double a = (double)g_a[(size_t)l * Dp * Dp + (size_t)r * Dp + k];
+        w.m[8][i] = a;
+        w.m[6][i] = a * w.s[k] + (double)g_c[(size_t)l * Dp + r] * w.sh[k];
+    }
+    if (blockIdx.x == 0) {
+        if (tid < D) w.dc[tid] = (double)g_c[(size_t)l * Dp + tid];
+        double s = 0.0;
+        for (long q = tid; q < n_logp; q += NT) s += (double)g_logp[q];
+        red[tid] = s;
+        __syncthreads();
+        for (int o = NT / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+        if (tid == 0) w.S[0] = red[0];
+    }
+}
+
 }}  // namespace mhe::glowaffw
 
 using namespace mhe;
@@ -289,4 +316,20 @@ extern "C" int mhe_glow_affine_wide_bwd_f64(const float *g_ainv, const float *g_
     hipLaunchKernelGGL(glowaffw::bwd_vec_kernel, dim3(1, layers), dim3(glowaffw::NT), 0, s, D, workspace, grads);
     hipLaunchKernelGGL(glowaffw::bwd_lu_kernel, dim3(nd, layers), dim3(glowaffw::NT), 0, s, D, workspace, grads);
     return check_launch("glowaffw::reparam_bwd");
+}
+
+extern "C" int mhe_glow_affine_wide_density_bwd_f64(const float *g_a, const float *g_c, const float *g_log_p, long n_log_p, int layers, int features,
+                                                    double *workspace, double *grads, void *stream) {
+    MHE_REQUIRE(layers > 0 && layers <= 65535 && features > 1 && features <= 256 && n_log_p >= 0 && (n_log_p == 0 || g_log_p),
+                "mhe_glow_affine_wide_density_bwd_f64: features=%d (2..256), layers=%d, n_log_p=%ld", features, layers, n_log_p);
+    MHE_REQUIRE(on_device(g_a) && on_device(g_c) && on_device(workspace) && on_device(grads) && (n_log_p == 0 || on_device(g_log_p)),
+                "mhe_glow_affine_wide_density_bwd_f64: every buffer must be device memory");
+    const int D = features, Dp = pad64(D);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned nd = (unsigned)((D * D + glowaffw::NT - 1) / glowaffw::NT);
+    hipLaunchKernelGGL(glowaffw::bwd_density_kernel, dim3(nd, layers), dim3(glowaffw::NT), 0, s, g_a, g_c, n_log_p ? g_log_p : nullptr, n_log_p, D, Dp,
+                       workspace);
+    hipLaunchKernelGGL(glowaffw::bwd_vec_kernel, dim3(1, layers), dim3(glowaffw::NT), 0, s, D, workspace, grads);
+    hipLaunchKernelGGL(glowaffw::bwd_lu_kernel, dim3(nd, layers), dim3(glowaffw::NT), 0, s, D, workspace, grads);
+    return check_launch("glowaffw::density_bwd");
 }

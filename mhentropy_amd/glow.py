@@ -17,6 +17,11 @@ MI355X shape of the computation: ActNorm and the LU product collapse into one 45
 inverse for sampling), the flow variable is carried zero-padded to 64 columns so every dense product is an
 mhe_linear_f32 call, and everything that depends on the context only (initial-layer context columns, the GLU
 gates of every block of every layer) is ONE GEMM per image, indexed per hypothesis row by the kernels.
+
+Both directions are differentiable in f32: the sampling direction (noise -> pose; `_run(inverse=True, tape=)` + `_reverse`, driven by the train
+step and by body.BodyFlowHead) and the density direction (pose -> noise; `log_prob` under grad = `_LogProbFn`: `_run(inverse=False, tape=)` +
+`_reverse_density`, the maximum-likelihood loss of the reference's README.md:32-34).  The residual net's reverse (`_net_reverse`) is one piece
+of code for the two.
 """
 import ctypes as C
 import math
@@ -261,10 +266,11 @@ class ConditionalGlow(nn.Module):
     def _run(self, v_in, context, inverse, row_div, n_img, pk=None, tape=None, bf16=None):
         """v_in (R,D) data (forward) or noise (inverse); returns (out (R,D), log_prob (R,)).  Row r belongs to image r // row_div % n_img.
         pk: the operand pack (default: the module's own); bf16: the block products on bf16 MFMA (default: compute_dtype is bfloat16).
-        tape (a dict; sampling direction, layer by layer): holds the caller's "sample_major" (the row layout, which row_div alone does not tell
-        at one row per image; `_reverse` picks its reductions by it) and is filled with what `_reverse` reads - the pack, the context table,
-        row_div, n_img and per layer v, the residual stream h_0 .. h_NB, every block's second activation t2 (after dropout), its second product t3 and dropout
-        bits, the coupling parameters and y"""
+        tape (a dict; either direction, layer by layer): holds the caller's "sample_major" (the row layout, which row_div alone does not tell
+        at one row per image; the reverse passes pick their reductions by it) and is filled with what `_reverse` (sampling direction) or
+        `_reverse_density` (density direction) reads - the pack, the context table, row_div, n_img and per layer v, the residual stream
+        h_0 .. h_NB, every block's second activation t2 (after dropout), its second product t3 and dropout bits, the coupling parameters and y;
+        in the density direction also u, the layer's affine input (v = A u + c)"""
         ops._chk(v_in, torch.float32, "glow.in"); ops._chk(context, torch.float32, "glow.context", (context.shape[0], self.context_features))
         pk = self._packed() if pk is None else pk
         L, D, H = _lib.lib(), self.features, self.hidden
@@ -292,8 +298,8 @@ class ConditionalGlow(nn.Module):
         for l in order:
             d = pk["layers"][l]
             if not inverse:
-                v = ops.linear(v, d["A"], d["c"])
-            rec = None if tape is None else {"v": v}
+                u, v = v, ops.linear(v, d["A"], d["c"])
+            rec = None if tape is None else {"v": v} if inverse else {"v": v, "u": u}
             prm = self._net(d, v, ctab, l * per, R, row_div, n_img, bf16, bufs, rec)
             y = torch.empty(R, self.Dp, device=dev)
             ops.check(L.mhe_glow_coupling_f32(ops._ptr(v), ops._ptr(prm), ops._ptr(y), ops._ptr(logdet), R, D, d["first"], d["T"], int(inverse), s()),
@@ -304,6 +310,58 @@ class ConditionalGlow(nn.Module):
             v = ops.linear(y, d["Ainv"], d["cinv"]) if inverse else y
         z = z_in if inverse else v                                               # the base-density argument
         return ops.glow_finish(z, v, logdet, R, D, inverse, pk["const_parts"])
+
+    def _reducers(self, tape, R):
+        """(img_sum(rows, out), flow_colsum(rows, out)) of a tape's row layout (see `_reverse`): the per-image sums into a view of the context
+        table's gradient, and the column sums of the flow-width rows"""
+        B, cs = tape["n_img"], tape["ctab"].shape[1]
+        N = R // B
+        if not tape["sample_major"]:
+            return (lambda rows, out: ops.sum_row_blocks(rows, B, N, out=out, out_stride=cs)), (lambda rows, out: _colsum(rows, B, N, out))
+        img_sum = lambda rows, out: ops.sum_over_hypotheses(rows, N, B, out=out, out_stride=cs)
+        if self.Dp == 64:
+            return img_sum, ops.colsum
+        # a wide variable (ops.colsum has no 192-column form): two levels of mhe_sum_row_blocks_f32 over g blocks of R / g consecutive rows,
+        # g the largest divisor of R up to sqrt(R) - any grouping gives the column sums, this one keeps both levels short
+        g = max(k for k in range(1, int(R ** 0.5) + 1) if R % k == 0)
+        return img_sum, (lambda rows, out: _colsum(rows, g, R // g, out))
+
+    def _net_reverse(self, t, o, ctab, slot, gprm, Gct, row_div, B, img_sum, flow_colsum):
+        """the reverse of one layer's residual net over its tape record `t`, shared by both directions: gprm (R, Pp) = dL/d(coupling parameters) ->
+        final layer; per block (last first) gate, second product, dropout, ReLU, first product, ReLU of the residual stream; initial layer's
+        weight gradient and the per-image sums into Gct.  Returns gh = dL/dh_0 (R, H); the caller adds gh Wx to the variable's gradient."""
+        L_, H = _lib.lib(), self.hidden
+        R, cs = gprm.shape[0], ctab.shape[1]
+        s, dev = ops._stream, gprm.device
+        ops.linear_wgrad(t["hs"][-1], gprm, o["dwf"]); flow_colsum(gprm, o["dbf"])
+        gh = ops.linear(gprm, o["wfT"])
+        for b in range(self.num_blocks - 1, -1, -1):
+            (w0T, w1T), (dw0, db0, dw1, db1) = o["blocksT"][b], o["dblocks"][b]
+            t2, t3, hb = t["t2"][b], t["t3"][b], t["hs"][b]
+            bf16 = t3.dtype == torch.bfloat16
+            gt3, ggate = torch.empty_like(t3), torch.empty(R, H, device=dev)
+            ops.check(L_.mhe_glow_glu_bwd_f32(ops._ptr(gh), ops._ptr(t3), C.c_void_p(ctab[:, (slot + 1 + b) * H:].data_ptr()), cs,
+                                              ops._ptr(gt3), ops._ptr(ggate), R, H, row_div, B, ops.dtype_code(t3.dtype), s()), "mhe_glow_glu_bwd_f32")
+            img_sum(ggate, Gct[:, (slot + 1 + b) * H:])
+            # the four h x h products of the block's reverse pass: on bf16 MFMA over a bf16 tape (bias sums of the bf16 gradients)
+            wgrad = (lambda x, gy_, dw: ops.conv_wgrad(x, gy_, 1, 1, 1, 0, dw)) if bf16 else ops.linear_wgrad
+            dgrad = (lambda gy_, wT: ops.conv2d_nhwc(gy_, wT, 1, 1, 1, 0)) if bf16 else ops.linear
+            wgrad(t2, gt3, dw1); ops.colsum(gt3, db1)
+            gt2 = dgrad(gt3, w1T)
+            if t["drop"][b] is not None:          # dropout's reverse: the same mask and scale on the gradient
+                ops.dropout_(gt2, self.p_drop, bits=t["drop"][b])
+            if bf16:
+                ops.flow_lrelu_bwd_mixed(gt2.view(R, H), t2.view(R, H), out_bf16=gt2.view(R, H), slope=0.0)
+            else:
+                ops.flow_lrelu_bwd(gt2, t2, slope=0.0)
+            tt = torch.empty_like(t2)
+            ops.check(L_.mhe_relu_copy_f32(ops._ptr(hb), ops._ptr(tt), tt.numel(), ops.dtype_code(tt.dtype), s()), "mhe_relu_copy_f32")
+            wgrad(tt, gt2, dw0); ops.colsum(gt2, db0)
+            gt = dgrad(gt2, w0T)
+            ops.check(L_.mhe_relu_bwd_add_f32(ops._ptr(gh), ops._ptr(gt), ops._ptr(hb), gh.numel(), ops.dtype_code(gt.dtype), s()), "mhe_relu_bwd_add_f32")
+        ops.linear_wgrad(t["v"], gh, o["dwx"])
+        img_sum(gh, Gct[:, slot * H:])
+        return gh
 
     def _reverse(self, tape, gv, g_logp, Gct, layers):
         """the staged reverse pass over a `_run` tape, layers 0 .. L-1:
@@ -320,15 +378,9 @@ class ConditionalGlow(nn.Module):
         bf16 tapes (t2, t3 as [R, 1, 1, H] bfloat16) take the block's four products on bf16 MFMA."""
         L_, D, H = _lib.lib(), self.features, self.hidden
         ctab, row_div, B, sample_major = tape["ctab"], tape["row_div"], tape["n_img"], tape["sample_major"]
-        R, cs = gv.shape[0], ctab.shape[1]
-        N = R // B
+        R, N = gv.shape[0], gv.shape[0] // B
         s, dev = ops._stream, gv.device
-        if sample_major:
-            img_sum = lambda rows, out: ops.sum_over_hypotheses(rows, N, B, out=out, out_stride=cs)
-            flow_colsum = ops.colsum
-        else:
-            img_sum = lambda rows, out: ops.sum_row_blocks(rows, B, N, out=out, out_stride=cs)
-            flow_colsum = lambda rows, out: _colsum(rows, B, N, out)
+        img_sum, flow_colsum = self._reducers(tape, R)
         per = 1 + self.num_blocks
         for l, (t, d, o) in enumerate(zip(tape["layers"], tape["pk"]["layers"], layers)):
             slot = l * per
@@ -340,43 +392,99 @@ class ConditionalGlow(nn.Module):
                                                            ops._ptr(gvc), ops._ptr(gprm), R, B, D, d["first"], d["T"], s()), "mhe_glow_coupling_inv_bwd_f32")
             else:
                 gvc, gprm = ops.glow_coupling_inv_bwd_wide(t["v"], t["prm"], gy, g_logp, D, d["first"], d["T"])
-            ops.linear_wgrad(t["hs"][-1], gprm, o["dwf"]); flow_colsum(gprm, o["dbf"])
-            gh = ops.linear(gprm, o["wfT"])
-            for b in range(self.num_blocks - 1, -1, -1):
-                (w0T, w1T), (dw0, db0, dw1, db1) = o["blocksT"][b], o["dblocks"][b]
-                t2, t3, hb = t["t2"][b], t["t3"][b], t["hs"][b]
-                bf16 = t3.dtype == torch.bfloat16
-                gt3, ggate = torch.empty_like(t3), torch.empty(R, H, device=dev)
-                ops.check(L_.mhe_glow_glu_bwd_f32(ops._ptr(gh), ops._ptr(t3), C.c_void_p(ctab[:, (slot + 1 + b) * H:].data_ptr()), cs,
-                                                  ops._ptr(gt3), ops._ptr(ggate), R, H, row_div, B, ops.dtype_code(t3.dtype), s()), "mhe_glow_glu_bwd_f32")
-                img_sum(ggate, Gct[:, (slot + 1 + b) * H:])
-                # the four h x h products of the block's reverse pass: on bf16 MFMA over a bf16 tape (bias sums of the bf16 gradients)
-                wgrad = (lambda x, gy_, dw: ops.conv_wgrad(x, gy_, 1, 1, 1, 0, dw)) if bf16 else ops.linear_wgrad
-                dgrad = (lambda gy_, wT: ops.conv2d_nhwc(gy_, wT, 1, 1, 1, 0)) if bf16 else ops.linear
-                wgrad(t2, gt3, dw1); ops.colsum(gt3, db1)
-                gt2 = dgrad(gt3, w1T)
-                if t["drop"][b] is not None:          # dropout's reverse: the same mask and scale on the gradient
-                    ops.dropout_(gt2, self.p_drop, bits=t["drop"][b])
-                if bf16:
-                    ops.flow_lrelu_bwd_mixed(gt2.view(R, H), t2.view(R, H), out_bf16=gt2.view(R, H), slope=0.0)
-                else:
-                    ops.flow_lrelu_bwd(gt2, t2, slope=0.0)
-                tt = torch.empty_like(t2)
-                ops.check(L_.mhe_relu_copy_f32(ops._ptr(hb), ops._ptr(tt), tt.numel(), ops.dtype_code(tt.dtype), s()), "mhe_relu_copy_f32")
-                wgrad(tt, gt2, dw0); ops.colsum(gt2, db0)
-                gt = dgrad(gt2, w0T)
-                ops.check(L_.mhe_relu_bwd_add_f32(ops._ptr(gh), ops._ptr(gt), ops._ptr(hb), gh.numel(), ops.dtype_code(gt.dtype), s()), "mhe_relu_bwd_add_f32")
-            ops.linear_wgrad(t["v"], gh, o["dwx"])
-            img_sum(gh, Gct[:, slot * H:])
+            gh = self._net_reverse(t, o, ctab, slot, gprm, Gct, row_div, B, img_sum, flow_colsum)
             gv = ops.add(gvc, ops.linear(gh, o["wxT"]))          # (after the last layer: dL/dnoise, which no caller reads)
+
+    def _reverse_density(self, tape, g_z, g_logp, Gct, layers):
+        """the staged reverse pass of the DENSITY direction (pose -> noise: what maximum-likelihood training differentiates) over a
+        `_run(..., inverse=False, tape=)` tape, layers L-1 .. 0:
+            gy = g_z - g_logp z (the base density; mhe_glow_base_density_bwd_f32);  per layer: forward-coupling reverse -> g_v, g_prm
+            (mhe_glow_coupling_fwd_bwd_f32);  the net's reverse (`_net_reverse`, shared with `_reverse`);  g_v += gh Wx;
+            dA = g_v^T u, dc = sum g_v;  gy = g_v A.
+        g_z (R, D) = dL/dz or None, g_logp (R,) = dL/dlog_prob or None; Gct as for `_reverse`.  layers(l): called as the pass reaches layer l, gives
+        its transposed operands AT, wfT, wxT, blocksT and its ZEROED gradient destinations dA, dc, dwf, dbf, dwx, dblocks.  Returns dL/dinputs padded
+        (R, Dp).  Rows are sample-major (row r belongs to image r % B; B = R is one row per context row)."""
+        D = self.features
+        ctab, row_div, B = tape["ctab"], tape["row_div"], tape["n_img"]
+        R = tape["layers"][-1]["y"].shape[0]
+        img_sum, flow_colsum = self._reducers(tape, R)
+        per = 1 + self.num_blocks
+        gy = ops.glow_base_density_bwd(tape["layers"][-1]["y"], g_z, g_logp, D)
+        for l in range(self.num_layers - 1, -1, -1):
+            t, d, o = tape["layers"][l], tape["pk"]["layers"][l], layers(l)
+            gvc, gprm = ops.glow_coupling_fwd_bwd(t["v"], t["prm"], gy, g_logp, D, d["first"], d["T"])
+            gh = self._net_reverse(t, o, ctab, l * per, gprm, Gct, row_div, B, img_sum, flow_colsum)
+            gv = ops.add(gvc, ops.linear(gh, o["wxT"]))
+            ops.linear_wgrad(t["u"], gv, o["dA"]); flow_colsum(gv, o["dc"])
+            gy = ops.linear(gv, o["AT"])
+        return gy
+
+    def _net_grad_buffers(self, pk, dev):
+        """zeroed destinations of the nets' weight gradients, per layer (dwf, dbf, dwx, dblocks: what `_net_reverse` adds to)"""
+        H, z = self.hidden, (lambda *shape: torch.zeros(*shape, device=dev))
+        return [{"dwf": z(d["wf"].shape[0], H), "dbf": z(d["wf"].shape[0]), "dwx": z(H, self.Dp),
+                 "dblocks": [(z(H, H), z(H), z(H, H), z(H)) for _ in d["blocks"]]} for d in pk["layers"]]
+
+    def _grads_by_param(self, pk, dst, dW, db, ga):
+        """{parameter: gradient} from a reverse pass's buffers: dst (per layer dwf, dbf, dwx, dblocks), dW / db (the context table's weight and
+        bias gradients, [cs, F] / [cs]) and ga [L, 4 D + D (D - 1)] (the ActNorm / LU gradients in the packed order log_scale, shift,
+        lower_entries, upper_entries, unconstrained_upper_diag, bias)"""
+        D, H, per = self.features, self.hidden, 1 + self.num_blocks
+        T, n, grads = self._transform._transforms, D * (D - 1) // 2, {}
+        for l, (d, o) in enumerate(zip(pk["layers"], dst)):
+            an, lu, cp = T[3 * l], T[3 * l + 1], T[3 * l + 2]
+            net, r, slot = cp.transform_net, ga[l], l * per
+            grads[an.log_scale], grads[an.shift] = r[:D], r[D:2 * D]
+            grads[lu.lower_entries], grads[lu.upper_entries] = r[2 * D:2 * D + n], r[2 * D + n:2 * D + 2 * n]
+            grads[lu.unconstrained_upper_diag], grads[lu.bias] = r[2 * D + 2 * n:3 * D + 2 * n], r[3 * D + 2 * n:]
+            grads[net.initial_layer.weight] = torch.cat([o["dwx"][:, cp.identity_features], dW[slot * H:(slot + 1) * H]], 1)
+            grads[net.initial_layer.bias] = db[slot * H:(slot + 1) * H]
+            grads[net.final_layer.weight], grads[net.final_layer.bias] = o["dwf"][:2 * d["T"]], o["dbf"][:2 * d["T"]]
+            for b, (blk, (dw0, db0, dw1, db1)) in enumerate(zip(net.blocks, o["dblocks"])):
+                k = slot + 1 + b
+                grads[blk.linear_layers[0].weight], grads[blk.linear_layers[0].bias] = dw0, db0
+                grads[blk.linear_layers[1].weight], grads[blk.linear_layers[1].bias] = dw1, db1
+                grads[blk.context_layer.weight], grads[blk.context_layer.bias] = dW[k * H:(k + 1) * H], db[k * H:(k + 1) * H]
+        return grads
+
+    def _log_prob_backward(self, tape, g_z, g_logp):
+        """`_reverse_density` into fresh gradients, then the context weights' gradient from the per-image rows, dL/dcontext, and the ActNorm / LU
+        gradients from dA, dc and sum dL/dlog_prob in float64 (ops.glow_affine_density_bwd) -> ({parameter: gradient}, dL/dinputs (R, D),
+        dL/dcontext (B, F))"""
+        D, Lr, Dp = self.features, self.num_layers, self.Dp
+        pk, ctab, B = tape["pk"], tape["ctab"], tape["n_img"]
+        cs, dev = ctab.shape[1], ctab.device
+        Gct = torch.zeros(B, cs, device=dev)
+        dA, dc = torch.zeros(Lr, Dp, Dp, device=dev), torch.zeros(Lr, Dp, device=dev)
+        dst = self._net_grad_buffers(pk, dev)
+        def layer(l):           # the transposed operands one layer at a time, as the reverse reaches it
+            d = pk["layers"][l]
+            return {**dst[l], "dA": dA[l], "dc": dc[l], "AT": d["A"].t().contiguous(), "wfT": d["wf"].t().contiguous(),
+                    "wxT": d["wx"].t().contiguous(), "blocksT": [(w0.t().contiguous(), w1.t().contiguous()) for (w0, _, w1, _) in d["blocks"]]}
+        g_in = self._reverse_density(tape, g_z, g_logp, Gct, layer)
+        dW, db = torch.zeros(cs, self.context_features, device=dev), torch.zeros(cs, device=dev)
+        ops.linear_wgrad(tape["context"], Gct, dW); ops.colsum(Gct, db)
+        g_ctx = ops.linear(Gct, pk["wctx"].t().contiguous())
+        ga = ops.glow_affine_density_bwd(dA, dc, g_logp, Lr, D, pk["aff"]["ws"]).float()
+        return self._grads_by_param(pk, dst, dW, db, ga), g_in[:, :D].contiguous(), g_ctx
 
     # ---- reference call surface ----------------------------------------------------------------------------
     def log_prob(self, inputs, context=None, rows_per_context=None):
         """(log_prob (R,), noise (R,D)).  `context` has R rows (the reference passes `feat.repeat(N,1)`), or B rows with
-        sample-major inputs (row r uses context[r % B]; extension, hoists the context terms)."""
+        sample-major inputs (row r uses context[r % B]; extension, hoists the context terms).
+
+        Differentiable - the maximum-likelihood loss `-log_prob.mean()` of the reference's README.md:32-34 - when grad is enabled and `inputs` or
+        `context` require grad, or the module is in train mode with parameters that require grad: one autograd node (_LogProbFn) whose forward
+        is this very pass with a tape (bit-identical values) and whose backward is the hand-written `_reverse_density`; both results carry
+        gradients to every flow parameter, `context` (with B rows: the per-image sum) and `inputs`.  Train-mode dropout is on the tape for flows
+        of up to 64 features.  Refused there (NotImplementedError): compute_dtype bfloat16; train-mode dropout on a wider flow.  Otherwise the
+        inference pass, returning plain tensors."""
         R, Bc = inputs.shape[0], context.shape[0]
         if R % Bc:
             raise ValueError(f"glow rows ({R}) must be a multiple of context rows ({Bc})")
+        if torch.is_grad_enabled() and (inputs.requires_grad or context.requires_grad
+                                        or (self.training and any(p.requires_grad for p in self.parameters()))):
+            return _LogProbFn.apply(self, inputs, context, *self.parameters())
         z, lp = self._run(inputs.contiguous(), context.contiguous(), False, 1, Bc)
         return lp, z
 
@@ -392,3 +500,31 @@ class ConditionalGlow(nn.Module):
         """ProHMR call form `flow(conditioning_feats, num_samples)` (reference README.md:34,39)"""
         s, lp, _ = self.sample_and_log_prob(num_samples, context=context)
         return s, lp
+
+
+class _LogProbFn(torch.autograd.Function):
+    """ConditionalGlow.log_prob as one autograd node: forward = the f32 density pass with a tape (ConditionalGlow._run, the no-grad pass's own
+    code: bit-identical values); backward = ConditionalGlow._log_prob_backward"""
+    @staticmethod
+    def forward(ctx, g, inputs, context, *params):
+        if g.compute_dtype != torch.float32:
+            raise NotImplementedError("the Glow reverse pass runs in f32 parity mode: compute_dtype must be torch.float32 under grad")
+        if g.features > 64 and g.training and g.p_drop > 0.0:
+            raise NotImplementedError("the wide Glow reverse pass has no dropout: build the flow with dropout_probability=0 or call eval()")
+        inputs, context = inputs.contiguous(), context.contiguous()
+        tape = {"context": context, "sample_major": True}
+        z, lp = g._run(inputs, context, False, 1, context.shape[0], tape=tape)
+        ctx.g, ctx.tape = g, tape
+        ctx.set_materialize_grads(False)
+        return lp, z
+
+    @staticmethod
+    def backward(ctx, g_lp, g_z):
+        g, tape = ctx.g, ctx.tape
+        params = list(g.parameters())
+        if g_lp is None and g_z is None:
+            return (None,) * (3 + len(params))
+        grads, g_in, g_ctx = g._log_prob_backward(tape, None if g_z is None else g_z.float().contiguous(),
+                                                  None if g_lp is None else g_lp.float().contiguous())
+        ctx.tape = None
+        return (None, g_in if ctx.needs_input_grad[1] else None, g_ctx if ctx.needs_input_grad[2] else None) + tuple(grads.get(q) for q in params)

@@ -1660,6 +1660,58 @@ def glow_coupling_inv_bwd_wide(v, prm, g_y, g_logq, dim, first, n_transform):
     return g_v, g_prm
 
 
+def glow_coupling_fwd_bwd(v, prm, g_y, g_logp, dim, first, n_transform):
+    """reverse of the forward coupling (the density direction) at the pitches of v [R, ld] and prm [R, ldp]: (g_v [R, ld], g_prm [R, ldp]);
+    g_logp [R] = dL/dlog p per row or None: mhe_glow_coupling_fwd_bwd_f32"""
+    R, ld = v.shape
+    ldp = prm.shape[1]
+    _chk(v, torch.float32, "coupling_fwd_bwd.v"); _chk(prm, torch.float32, "coupling_fwd_bwd.prm", (R, ldp)); _chk(g_y, torch.float32, "coupling_fwd_bwd.g_y", (R, ld))
+    if g_logp is not None:
+        _chk(g_logp, torch.float32, "coupling_fwd_bwd.g_logp", (R,))
+    g_v, g_prm = torch.empty_like(v), torch.empty_like(prm)
+    check(_lib.lib().mhe_glow_coupling_fwd_bwd_f32(_ptr(v), _ptr(prm), _ptr(g_y), _ptr(g_logp), _ptr(g_v), _ptr(g_prm), R, dim, first, n_transform,
+                                                   ld, ldp, _stream()), "mhe_glow_coupling_fwd_bwd_f32")
+    return g_v, g_prm
+
+
+def glow_base_density_bwd(z_padded, g_z, g_logp, dim):
+    """g_y [R, ld] = g_z - g_logp[r] z on the padded rows z_padded [R, ld]; g_z [R, dim] or None, g_logp [R] or None: mhe_glow_base_density_bwd_f32"""
+    R, ld = z_padded.shape
+    _chk(z_padded, torch.float32, "base_density_bwd.z")
+    if g_z is not None:
+        _chk(g_z, torch.float32, "base_density_bwd.g_z", (R, dim))
+    if g_logp is not None:
+        _chk(g_logp, torch.float32, "base_density_bwd.g_logp", (R,))
+    g_y = torch.empty_like(z_padded)
+    check(_lib.lib().mhe_glow_base_density_bwd_f32(_ptr(z_padded), _ptr(g_z), _ptr(g_logp), _ptr(g_y), R, dim, ld, _stream()), "mhe_glow_base_density_bwd_f32")
+    return g_y
+
+
+def glow_affine_density_bwd(g_a, g_c, g_logp, layers, features, ws):
+    """the density direction's reverse of the ActNorm + LU re-parameterisation: float64 gradients [layers, 4 D + D (D - 1)] of every layer's
+    (log_scale, shift, lower, upper, unconstrained diag, bias) from dL/dA [L, Dp, Dp], dL/dc [L, Dp] and dL/dlog p per row (or None).  `ws`: the
+    float64 workspace of glow_affine (features <= 64 with 64-pitch operands: mhe_glow_affine_density_bwd_f64) or of glow_affine_wide
+    (mhe_glow_affine_wide_density_bwd_f64); which one is told by its size"""
+    Dp = (features + 63) // 64 * 64
+    _chk(g_a, torch.float32, "affine_density_bwd.g_a", (layers, Dp, Dp)); _chk(g_c, torch.float32, "affine_density_bwd.g_c", (layers, Dp))
+    _chk(ws, torch.float64, "affine_density_bwd.ws")
+    if g_logp is not None:
+        _chk(g_logp, torch.float32, "affine_density_bwd.g_logp")
+    L = _lib.lib()
+    n = 0 if g_logp is None else g_logp.numel()
+    out = torch.empty(layers, int(L.mhe_glow_affine_wide_grad_doubles(layers, features)) // layers, device=g_a.device, dtype=torch.float64)
+    if features <= 64 and ws.numel() == L.mhe_glow_affine_workspace_doubles(layers, features):
+        check(L.mhe_glow_affine_density_bwd_f64(_ptr(g_a), _ptr(g_c), _ptr(g_logp), n, layers, features, _ptr(ws), _ptr(out), _stream()),
+              "mhe_glow_affine_density_bwd_f64")
+    elif ws.numel() == L.mhe_glow_affine_wide_workspace_doubles(layers, features):
+        check(L.mhe_glow_affine_wide_density_bwd_f64(_ptr(g_a), _ptr(g_c), _ptr(g_logp), n, layers, features, _ptr(ws), _ptr(out), _stream()),
+              "mhe_glow_affine_wide_density_bwd_f64")
+    else:
+        raise _lib.MheError(f"affine_density_bwd.ws: {ws.numel()} doubles is the workspace of neither glow_affine nor glow_affine_wide at "
+                            f"{layers} layers x {features} features")
+    return out
+
+
 def sum_row_blocks(rows, groups, N, out=None, out_stride=0, accumulate=False):
     """out[g] (+)= sum_n rows[g*N + n] (per-image sums of batch-major rows); `out` may be a view into a wider [groups, out_stride] matrix"""
     Cc = rows.shape[1]

@@ -4,7 +4,10 @@ Glow sampling pass, the 6D -> R conversion and the SMPL-sized linear-blend skinn
 1/8 hypothesis slice (what one rank of a hypothesis-sharded 8-GPU job decodes).  Synthetic tables; parity unpinned at this size.
 TRAIN=1 adds the train leg: forward + backward of the head in f32 (log_prob[:, 1:].mean() + a joint loss, joints only) next to the f32
 forward-only time of the same call under no_grad.  VERTS=1 (with TRAIN=1) adds the vertex-loss leg: log_prob[:, 1:].mean() + |vertices - target|.mean()
-with verts_grad=True, and the time of the skinning reverse alone (body.lbs_bwd) next to the forward skinning."""
+with verts_grad=True, and the time of the skinning reverse alone (body.lbs_bwd) next to the forward skinning.
+NLL=1 runs the maximum-likelihood leg INSTEAD of the sampling legs (B rows, one annotated pose per image; K is not used): forward-only
+head.log_prob under no_grad, and forward + backward of -log_prob.mean(), both in f32, each as the median of WINDOWS (7) timing windows.  STEPS=n
+(with NLL=1) runs n untimed forward + backward steps only (for a kernel trace)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -29,6 +32,33 @@ def t(fn, n=5):
         fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n
+
+
+if os.environ.get("NLL", "0") == "1":
+    head.flow.compute_dtype = torch.float32
+    pose6d = torch.randn(B, 144, device="cuda") * 0.8
+
+    def nll_step():
+        for p_ in head.flow.parameters():
+            p_.grad = None
+        (-head.log_prob(feats, pose6d=pose6d)[0].mean()).backward()
+
+    def fwd():
+        with torch.no_grad():
+            head.log_prob(feats, pose6d=pose6d)
+
+    head.train()                                   # (dropout p = 0: train mode only switches the differentiable pass on)
+    if os.environ.get("STEPS"):
+        for _ in range(int(os.environ["STEPS"])):
+            nll_step()
+        torch.cuda.synchronize()
+        sys.exit(0)
+    W = int(os.environ.get("WINDOWS", 7))
+    fw = sorted(t(fwd, n=20) for _ in range(W))
+    tr = sorted(t(nll_step, n=10) for _ in range(W))
+    print(f"NLL leg (f32, one pose per image) B={B}: forward log_prob {fw[W // 2]:.3f} ms (min {fw[0]:.3f}, max {fw[-1]:.3f} over {W} windows) | "
+          f"forward + backward {tr[W // 2]:.3f} ms (min {tr[0]:.3f}, max {tr[-1]:.3f}) = {tr[W // 2] / fw[W // 2]:.2f}x the forward")
+    sys.exit(0)
 
 
 with torch.no_grad():
