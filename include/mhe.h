@@ -882,6 +882,30 @@ int mhe_lbs_skin_bwd_f32(const float *workspace, const float *v_template, const 
 int mhe_lbs_transforms_bwd_f32(const float *rotmats, const float *betas, const float *j_template, const float *j_shapedirs, const int *parents,
                                const float *g_joints, const float *g_transforms, const float *g_posemap, const float *g_betas_in, float *g_rotmats,
                                float *g_betas, int R, int J, int nb, void *stream);
+/* Body keypoints = regressor [NK,NV] x (scaled) vertices, 1 <= NK <= 64, accumulated INSIDE the skinning pass (fixed summation order, no atomics:
+ * bit-reproducible); `verts` may be NULL, then no [R,NV,3] tensor is written.  keypoints [R,NK,3].
+ *   mhe_lbs_skin_kp_mfma_f32 (csrc/lbs_skin.hip): the matrix-core skinning with a second product on bf16 pieces of the staged vertices and of the
+ *     regressor (`ksplit` = mhe_lbs_kp_split_floats(NK, VP) floats, filled once per model by mhe_lbs_kp_split_tables_f32), f32-class accuracy;
+ *     vertices bit-identical to mhe_lbs_skin_mfma_f32.  mhe_lbs_skin_kp_supported: that kernel's limits (want_verts: the 4 GiB vertex output).
+ *   mhe_lbs_skin_kp_f32 (csrc/body.hip): the scalar-operand skinning, one workgroup per 8 hypotheses walking all vertices; any size.
+ * mhe_lbs_keypoints_bwd_f32 (csrc/body_kp.hip): g_keypoints [R,NK,3] -> g_verts [R,NV,3] = regressor^T g_keypoints, added to g_verts when
+ * `accumulate`, written otherwise; follow with mhe_lbs_skin_bwd_f32. */
+size_t mhe_lbs_kp_split_floats(int NK, int VP);
+int mhe_lbs_kp_split_tables_f32(const float *regressor, float *ksplit, int NK, int NV, int VP, void *stream);
+int mhe_lbs_skin_kp_supported(int R, int J, int nb, int NV, int VP, int NK, int want_verts);
+int mhe_lbs_skin_kp_mfma_f32(const float *workspace, const float *split, const float *ksplit, float *verts, float *keypoints, int R, int J, int nb,
+                             int NV, int VP, int NK, float scale, void *stream);
+int mhe_lbs_skin_kp_f32(const float *workspace, const float *v_template, const float *v_shapedirs, const float *v_posedirs, const float *v_weights,
+                        const float *regressor, float *verts, float *keypoints, int R, int J, int nb, int NV, int VP, int NK, float scale, void *stream);
+int mhe_lbs_keypoints_bwd_f32(const float *regressor, const float *g_keypoints, float *g_verts, int R, int NK, int NV, int accumulate, void *stream);
+/* 2D keypoint likelihood of K hypotheses per image (csrc/body_kp.hip): keypoints [B,K,NK,3], cam [B,K,3] (cam_per_hyp) or [B,3] = (s, tx, ty),
+ * uv [B,NK,2], vis [B,NK];  proj = s xy + t,  log_p [B,K] = sum over NK x 2 of [vis == 1] (-(relu(|uv - proj| - 1e-4) + 1e-4) / b - log(2 b))
+ * (reference hand/network.py:233-258, hand/ManoLayer.py:150-165).  Reverse: g [B,K] -> g_keypoints [B,K,NK,3] (z column 0), g_cam (shape of cam;
+ * a shared camera's sum over K in a fixed order).  uv, vis and b are not differentiated. */
+int mhe_kp_log_prob_f32(const float *keypoints, const float *cam, const float *uv, const float *vis, float *log_p, int B, int K, int NK,
+                        int cam_per_hyp, float b, void *stream);
+int mhe_kp_log_prob_bwd_f32(const float *keypoints, const float *cam, const float *uv, const float *vis, const float *g, float *g_keypoints,
+                            float *g_cam, int B, int K, int NK, int cam_per_hyp, float b, void *stream);
 
 #ifdef __cplusplus
 }

@@ -183,6 +183,14 @@ SIGNATURES = {
     "mhe_lbs_bwd_tables_f32": (_i, [_p] * 4 + [_i, _i, _i, _i, _p]),
     "mhe_lbs_skin_bwd_f32": (_i, [_p] * 10 + [_i, _i, _i, _i, _i, _f, _p]),
     "mhe_lbs_transforms_bwd_f32": (_i, [_p] * 11 + [_i, _i, _i, _p]),
+    "mhe_lbs_kp_split_floats": (_sz, [_i, _i]),
+    "mhe_lbs_kp_split_tables_f32": (_i, [_p, _p, _i, _i, _i, _p]),
+    "mhe_lbs_skin_kp_supported": (_i, [_i] * 7),
+    "mhe_lbs_skin_kp_mfma_f32": (_i, [_p] * 5 + [_i] * 6 + [_f, _p]),
+    "mhe_lbs_skin_kp_f32": (_i, [_p] * 8 + [_i] * 6 + [_f, _p]),
+    "mhe_lbs_keypoints_bwd_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "mhe_kp_log_prob_f32": (_i, [_p] * 5 + [_i] * 4 + [_f, _p]),
+    "mhe_kp_log_prob_bwd_f32": (_i, [_p] * 7 + [_i] * 4 + [_f, _p]),
     "mhe_topk_gather_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "mhe_metrics_f32": (_i, [_p] * 7 + [_i, _i, _p]),
     "mhe_metrics_split_f32": (_i, [_p] * 8 + [_i, _i, _p]),

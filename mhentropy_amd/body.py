@@ -24,9 +24,11 @@ from . import ops, _lib
 SMPL_PARENTS = (-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21)
 
 
-def synthetic_body_tables(seed=0, NV=6890, J=24, nb=10, parents=SMPL_PARENTS):
+def synthetic_body_tables(seed=0, NV=6890, J=24, nb=10, parents=SMPL_PARENTS, keypoints=0):
     """SMPL-SHAPED random tables (the real model is licence-restricted): template ~ N(0, 0.3), small blend shapes,
-    positive row-normalised skinning weights concentrated on 4 joints per vertex, a joint regressor with rows summing to 1."""
+    positive row-normalised skinning weights concentrated on 4 joints per vertex, a joint regressor with rows summing to 1.
+    keypoints=NK adds "keypoint_regressor" (NK, NV): sparse positive rows summing to 1 and, from the third row on, every fourth row one-hot (a
+    picked vertex); drawn after the other tables, which do not depend on it."""
     rng = np.random.default_rng(seed + 9000)
     f32 = lambda a: np.asarray(a, np.float32)
     w = np.zeros((NV, J))
@@ -37,9 +39,18 @@ def synthetic_body_tables(seed=0, NV=6890, J=24, nb=10, parents=SMPL_PARENTS):
     jr = rng.random((J, NV)) * (rng.random((J, NV)) < 0.01)
     jr[:, 0] += 1e-3
     jr /= jr.sum(1, keepdims=True)
-    return {"v_template": f32(rng.normal(0, 0.3, (NV, 3))), "shapedirs": f32(rng.normal(0, 0.01, (NV, 3, nb))),
-            "posedirs": f32(rng.normal(0, 0.002, (NV, 3, 9 * (J - 1)))), "J_regressor": f32(jr), "weights": f32(w),
-            "parents": np.asarray(parents, np.int32)}
+    t = {"v_template": f32(rng.normal(0, 0.3, (NV, 3))), "shapedirs": f32(rng.normal(0, 0.01, (NV, 3, nb))),
+         "posedirs": f32(rng.normal(0, 0.002, (NV, 3, 9 * (J - 1)))), "J_regressor": f32(jr), "weights": f32(w),
+         "parents": np.asarray(parents, np.int32)}
+    if keypoints:
+        kr = rng.random((keypoints, NV)) * (rng.random((keypoints, NV)) < 0.01)
+        kr[:, 0] += 1e-3
+        kr /= kr.sum(1, keepdims=True)
+        for k in range(2, keypoints, 4):
+            kr[k] = 0.0
+            kr[k, rng.integers(NV)] = 1.0
+        t["keypoint_regressor"] = f32(kr)
+    return t
 
 
 def rot6d_to_rotmat(poses6, robust=False):
@@ -92,6 +103,13 @@ class BodyLayer(nn.Module):
         self.register_buffer("_vsd", f(vp(t["shapedirs"].transpose(2, 1, 0))), persistent=False)                            # [nb][3][VP]
         self.register_buffer("_vpd", f(vp(t["posedirs"].transpose(2, 1, 0))), persistent=False)                             # [9(J-1)][3][VP]
         self.register_buffer("_vw", f(vp(t["weights"].T)), persistent=False)                                                # [J][VP]
+        self.NK = 0
+        if t.get("keypoint_regressor") is not None:          # keypoints = regressor x vertices (reference hand/ManoLayer.py:141-148 at other sizes)
+            kr = t["keypoint_regressor"]
+            if kr.ndim != 2 or kr.shape[1] != self.NV or not 1 <= kr.shape[0] <= 64:
+                raise ValueError(f"BodyLayer: keypoint_regressor must be (NK, {self.NV}) with 1 <= NK <= 64, got {tuple(kr.shape)}")
+            self.NK = kr.shape[0]
+            self.register_buffer("keypoint_regressor", f(kr))
 
     def _split_tables(self, dev):
         """the vertex tables as bf16 pieces in MFMA operand order (19 MB for SMPL), made on first use per device; the tables are fixed buffers"""
@@ -103,6 +121,18 @@ class BodyLayer(nn.Module):
                                                  self.J, self.nb, self.VP, ops._stream()), "mhe_lbs_split_tables_f32")
             self._split, self._split_key = sp, key
         return self._split
+
+    def _kp_split(self, dev):
+        """the keypoint regressor as bf16 pieces in MFMA operand order (mhe_lbs_kp_split_tables_f32), made on first use per device like _split_tables
+        and again whenever the buffer is written in place (it is persistent: load_state_dict copies into it without moving it)"""
+        key = (dev.type, dev.index, self.keypoint_regressor.data_ptr(), self.keypoint_regressor._version)
+        if getattr(self, "_kp_key", None) != key:
+            L = _lib.lib()
+            sp = torch.empty(L.mhe_lbs_kp_split_floats(self.NK, self.VP), device=dev, dtype=torch.float32)
+            ops.check(L.mhe_lbs_kp_split_tables_f32(ops._ptr(self.keypoint_regressor), ops._ptr(sp), self.NK, self.NV, self.VP, ops._stream()),
+                      "mhe_lbs_kp_split_tables_f32")
+            self._kp_sp, self._kp_key = sp, key
+        return self._kp_sp
 
     def _bwd_tables(self, dev):
         """coefficient-fastest copies of the blend-shape and weight tables for the skinning reverse (mhe_lbs_bwd_tables_f32, 19 MB for SMPL), made
@@ -116,8 +146,11 @@ class BodyLayer(nn.Module):
             self._bwd_tab, self._bwd_key = tb, key
         return self._bwd_tab
 
-    def forward(self, betas, rotmats=None, pose6d=None, scale=1.0, want_verts=True):
-        """betas (R,nb); rotmats (R,J,3,3) or pose6d (R,6J) -> {'vertices' (R,NV,3), 'joints' (R,J,3), 'rotmats'}"""
+    def forward(self, betas, rotmats=None, pose6d=None, scale=1.0, want_verts=True, want_keypoints=False):
+        """betas (R,nb); rotmats (R,J,3,3) or pose6d (R,6J) -> {'vertices' (R,NV,3), 'joints' (R,J,3), 'rotmats'}; want_keypoints adds
+        'keypoints' (R,NK,3) = keypoint_regressor x vertices, accumulated inside the skinning pass (with want_verts=False no (R,NV,3) tensor exists)"""
+        if want_keypoints and not self.NK:
+            raise ValueError("BodyLayer: want_keypoints=True needs tables with a 'keypoint_regressor'")
         if rotmats is None:
             rotmats = rot6d_to_rotmat(pose6d.reshape(-1, self.J, 6).contiguous())
         R = rotmats.shape[0]
@@ -129,6 +162,21 @@ class BodyLayer(nn.Module):
         ops.check(L.mhe_lbs_pose_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(self._jt), ops._ptr(self._jsd), ops._ptr(self.parents), ops._ptr(ws),
                                      ops._ptr(joints), R, self.J, self.nb, ops._stream()), "mhe_lbs_pose_f32")
         out = {"joints": joints, "rotmats": rotmats}
+        if want_keypoints:
+            verts = torch.empty(R, self.NV, 3, device=dev, dtype=torch.float32) if want_verts else None
+            kp = torch.empty(R, self.NK, 3, device=dev, dtype=torch.float32)
+            if os.environ.get("MHE_LBS_MFMA", "1") == "1" and L.mhe_lbs_skin_kp_supported(R, self.J, self.nb, self.NV, self.VP, self.NK, int(want_verts)):
+                ops.check(L.mhe_lbs_skin_kp_mfma_f32(ops._ptr(ws), ops._ptr(self._split_tables(dev)), ops._ptr(self._kp_split(dev)), ops._ptr(verts),
+                                                     ops._ptr(kp), R, self.J, self.nb, self.NV, self.VP, self.NK, float(scale), ops._stream()),
+                          "mhe_lbs_skin_kp_mfma_f32")
+            else:
+                ops.check(L.mhe_lbs_skin_kp_f32(ops._ptr(ws), ops._ptr(self._vt), ops._ptr(self._vsd), ops._ptr(self._vpd), ops._ptr(self._vw),
+                                                ops._ptr(self.keypoint_regressor), ops._ptr(verts), ops._ptr(kp), R, self.J, self.nb, self.NV, self.VP,
+                                                self.NK, float(scale), ops._stream()), "mhe_lbs_skin_kp_f32")
+            out["keypoints"] = kp
+            if want_verts:
+                out["vertices"] = verts
+            return out
         if want_verts:
             verts = torch.empty(R, self.NV, 3, device=dev, dtype=torch.float32)
             if os.environ.get("MHE_LBS_MFMA", "1") == "1" and self.VP % 32 == 0 and L.mhe_lbs_skin_mfma_supported(R, self.J, self.nb, self.NV, self.VP):
@@ -156,9 +204,11 @@ class BodyFlowHead(nn.Module):
         self.flow = ConditionalGlow(6 * self.body.J, hidden, num_layers, num_blocks, context_features=context_features,
                                     dropout_probability=0.0)
 
-    def forward(self, feats, num_samples, betas=None, noise=None, hyp_slice=None, want_verts=True, verts_grad=False):
+    def forward(self, feats, num_samples, betas=None, noise=None, hyp_slice=None, want_verts=True, verts_grad=False, want_keypoints=False):
         """feats (B,F) -> pose6d (B,K,6J), log_prob (B,K), vertices (B,K,NV,3), joints (B,K,J,3); hyp_slice = (lo, hi) decodes only
-        hypotheses lo..hi-1 of every image (the hypothesis-sharded form).
+        hypotheses lo..hi-1 of every image (the hypothesis-sharded form).  want_keypoints adds keypoints (B, hi-lo, NK, 3) from the body layer's
+        keypoint_regressor (no vertex tensor is needed for them: want_verts=False); under grad they carry gradients like the joints, through the
+        skinning reverse, without verts_grad.
 
         Differentiable when grad is enabled and `feats` or `betas` require grad, or the head is in train mode with flow parameters that require
         grad (one autograd node, _HeadFn, whose backward is the hand-written reverse pass; an eval-mode call on plain inputs stays the
@@ -167,16 +217,20 @@ class BodyFlowHead(nn.Module):
         without verts_grad=True, compute_dtype bfloat16, dropout p > 0 in train mode.  verts_grad changes nothing on the inference pass."""
         if verts_grad and not want_verts:
             raise ValueError("BodyFlowHead: verts_grad=True needs want_verts=True")
+        if want_keypoints and not self.body.NK:
+            raise ValueError("BodyFlowHead: want_keypoints=True needs body tables with a 'keypoint_regressor'")
         params = [p for p in self.flow.parameters()]
         if torch.is_grad_enabled() and ((self.training and any(p.requires_grad for p in params)) or feats.requires_grad
                                         or (betas is not None and betas.requires_grad)):
             if noise is None:
                 noise = ops.randn(feats.shape[0] * num_samples, self.flow.features, feats.device).view(feats.shape[0], num_samples, self.flow.features)
             lo, hi = hyp_slice if hyp_slice is not None else (0, num_samples)
-            vals = _HeadFn.apply(self, feats, betas, noise, num_samples, lo, hi, want_verts, bool(verts_grad), *params)
+            vals = _HeadFn.apply(self, feats, betas, noise, num_samples, lo, hi, want_verts, bool(verts_grad), bool(want_keypoints), *params)
             res = {"pose6d": vals[0], "log_prob": vals[1], "joints": vals[2]}
             if want_verts:
                 res["vertices"] = vals[3]
+            if want_keypoints:
+                res["keypoints"] = vals[-1]
             return res
         B = feats.shape[0]
         pose, logp, _ = self.flow.sample_and_log_prob(num_samples, noise=noise, context=feats)
@@ -184,10 +238,12 @@ class BodyFlowHead(nn.Module):
         p = pose[:, lo:hi].reshape(B * (hi - lo), -1).contiguous()
         bt = betas if betas is not None else torch.zeros(B, self.body.nb, device=feats.device)
         bt = bt[:, None, :].expand(B, hi - lo, self.body.nb).reshape(B * (hi - lo), self.body.nb).contiguous()
-        out = self.body(bt, pose6d=p, want_verts=want_verts)
+        out = self.body(bt, pose6d=p, want_verts=want_verts, want_keypoints=want_keypoints)
         res = {"pose6d": pose, "log_prob": logp, "joints": out["joints"].view(B, hi - lo, self.body.J, 3)}
         if want_verts:
             res["vertices"] = out["vertices"].view(B, hi - lo, self.body.NV, 3)
+        if want_keypoints:
+            res["keypoints"] = out["keypoints"].view(B, hi - lo, self.body.NK, 3)
         return res
 
     def log_prob(self, feats, pose6d=None, rotmats=None):
@@ -213,13 +269,27 @@ def lbs_pose_bwd(layer, rotmats, betas, g_joints):
     return g_rot, g_bt
 
 
-def lbs_bwd(layer, rotmats, betas, g_verts, g_joints=None, scale=1.0):
-    """reverse of BodyLayer's vertices and posed joints: g_verts (R,NV,3) = dL/dvertices of `layer(betas, rotmats=rotmats, scale=scale)`,
-    g_joints (R,J,3) or None -> (g_rotmats (R,J,3,3), g_betas (R,nb)).  The pose pass is run again for its workspace rows; the skinning reverse
+KP_BWD_MAX_ROWS = 262144    # rows per mhe_lbs_keypoints_bwd_f32 launch (the entry takes up to 524,280: 8 rows per workgroup, 65,535 in grid y)
+KP_BWD_ROWS = 8192          # rows per pass of lbs_bwd when only keypoints carry a gradient: bounds the (rows, NV, 3) vertex-gradient buffer (677 MB for
+                            # SMPL) and still gives the skinning reverse one 32-row workgroup per CU (4,096 rows left half of the CUs idle)
+
+
+def lbs_bwd(layer, rotmats, betas, g_verts, g_joints=None, scale=1.0, g_keypoints=None):
+    """reverse of BodyLayer's vertices, keypoints and posed joints: g_verts (R,NV,3) = dL/dvertices of `layer(betas, rotmats=rotmats, scale=scale)`
+    (or None), g_keypoints (R,NK,3) or None (at least one of the two), g_joints (R,J,3) or None -> (g_rotmats (R,J,3,3), g_betas (R,nb)).  The pose
+    pass is run again for its workspace rows; the keypoints' reverse (mhe_lbs_keypoints_bwd_f32: regressor^T g_keypoints added to a copy of g_verts
+    - a second (R, NV, 3) buffer, 1.35 GB at R = 16,384 for SMPL: the caller's gradient is not written - or, without g_verts, written into a buffer of KP_BWD_ROWS rows that the skinning reverse then walks chunk by chunk); the skinning reverse
     (mhe_lbs_skin_bwd_f32, exact-f32 matrix-core reductions over the vertices) then the pose chain's (mhe_lbs_transforms_bwd_f32)."""
     R, J, nb = rotmats.shape[0], layer.J, layer.nb
+    if g_verts is None and g_keypoints is None:
+        raise ValueError("lbs_bwd: give g_verts or g_keypoints (joints alone: lbs_pose_bwd)")
+    if g_keypoints is not None and not layer.NK:
+        raise ValueError("lbs_bwd: g_keypoints given but the layer has no 'keypoint_regressor'")
     ops._chk(rotmats, torch.float32, "lbs_bwd.rotmats", (R, J, 3, 3)); ops._chk(betas, torch.float32, "lbs_bwd.betas", (R, nb))
-    ops._chk(g_verts, torch.float32, "lbs_bwd.g_verts", (R, layer.NV, 3))
+    if g_verts is not None:
+        ops._chk(g_verts, torch.float32, "lbs_bwd.g_verts", (R, layer.NV, 3))
+    if g_keypoints is not None:
+        ops._chk(g_keypoints, torch.float32, "lbs_bwd.g_keypoints", (R, layer.NK, 3))
     if g_joints is not None:
         ops._chk(g_joints, torch.float32, "lbs_bwd.g_joints", (R, J, 3))
     L, dev = _lib.lib(), rotmats.device
@@ -229,9 +299,30 @@ def lbs_bwd(layer, rotmats, betas, g_verts, g_joints=None, scale=1.0):
     g_tf = torch.empty(R, J, 12, device=dev, dtype=torch.float32)
     g_pm = torch.empty(R, 9 * (J - 1), device=dev, dtype=torch.float32)
     g_bt = torch.empty_like(betas)
-    ops.check(L.mhe_lbs_skin_bwd_f32(ops._ptr(ws), ops._ptr(layer._vt), ops._ptr(layer._vsd), ops._ptr(layer._vpd), ops._ptr(layer._vw),
-                                     ops._ptr(layer._bwd_tables(dev)), ops._ptr(g_verts), ops._ptr(g_tf), ops._ptr(g_pm), ops._ptr(g_bt), R, J, nb,
-                                     layer.NV, layer.VP, float(scale), ops._stream()), "mhe_lbs_skin_bwd_f32")
+    wstride = ws.numel() // R
+
+    def skin_bwd(gv, lo, n):          # rows lo .. lo + n - 1 (row slices of contiguous tensors are contiguous)
+        ops.check(L.mhe_lbs_skin_bwd_f32(ops._ptr(ws[lo * wstride:]), ops._ptr(layer._vt), ops._ptr(layer._vsd), ops._ptr(layer._vpd), ops._ptr(layer._vw),
+                                         ops._ptr(layer._bwd_tables(dev)), ops._ptr(gv), ops._ptr(g_tf[lo:]), ops._ptr(g_pm[lo:]), ops._ptr(g_bt[lo:]), n,
+                                         J, nb, layer.NV, layer.VP, float(scale), ops._stream()), "mhe_lbs_skin_bwd_f32")
+
+    def kp_bwd(gv, lo, n, accumulate):
+        ops.check(L.mhe_lbs_keypoints_bwd_f32(ops._ptr(layer.keypoint_regressor), ops._ptr(g_keypoints[lo:]), ops._ptr(gv), n, layer.NK, layer.NV,
+                                              int(accumulate), ops._stream()), "mhe_lbs_keypoints_bwd_f32")
+
+    if g_keypoints is None:
+        skin_bwd(g_verts, 0, R)
+    elif g_verts is not None:
+        gv = g_verts.clone()
+        for lo in range(0, R, KP_BWD_MAX_ROWS):
+            kp_bwd(gv[lo:], lo, min(KP_BWD_MAX_ROWS, R - lo), True)
+        skin_bwd(gv, 0, R)
+    else:
+        gv = torch.empty(min(R, KP_BWD_ROWS), layer.NV, 3, device=dev, dtype=torch.float32)
+        for lo in range(0, R, KP_BWD_ROWS):
+            n = min(KP_BWD_ROWS, R - lo)
+            kp_bwd(gv, lo, n, False)
+            skin_bwd(gv, lo, n)
     g_rot = torch.empty_like(rotmats)
     ops.check(L.mhe_lbs_transforms_bwd_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(layer._jt), ops._ptr(layer._jsd), ops._ptr(layer.parents),
                                            ops._ptr(g_joints), ops._ptr(g_tf), ops._ptr(g_pm), ops._ptr(g_bt), ops._ptr(g_rot), ops._ptr(g_bt), R, J, nb,
@@ -288,25 +379,31 @@ class _HeadFn(torch.autograd.Function):
     """BodyFlowHead.forward as one autograd node: forward = the f32 sampling pass with a tape (_flow_sample_with_tape, bit-identical to the
     no-grad pass) + the body decode; backward = joints -> rotations -> 6D poses (mhe_lbs_pose_bwd_f32, mhe_rot6d_to_rotmat_bwd_f32) added to
     dL/dpose6d on the slice's rows, then the flow's reverse pass (_flow_backward).  With verts_grad, a vertex gradient takes lbs_bwd (the
-    skinning reverse together with the joints'); without one the route is the joints-only one whatever verts_grad says."""
+    skinning reverse together with the joints'); without one the route is the joints-only one whatever verts_grad says.  A gradient on the
+    keypoints (want_kp: one more output) takes lbs_bwd too, through mhe_lbs_keypoints_bwd_f32, with or without verts_grad / want_verts."""
     @staticmethod
-    def forward(ctx, head, feats, betas, noise, K, lo, hi, want_verts, verts_grad, *params):
+    def forward(ctx, head, feats, betas, noise, K, lo, hi, want_verts, verts_grad, want_kp, *params):
         B, D, nb, J = feats.shape[0], head.flow.features, head.body.nb, head.body.J
         x, lp, tape = _flow_sample_with_tape(head.flow, noise.reshape(B * K, D).contiguous(), feats.contiguous(), K)
         pose = x.view(B, K, D)
         p = pose[:, lo:hi].reshape(B * (hi - lo), D).contiguous()
         bt = betas.contiguous() if betas is not None else torch.zeros(B, nb, device=feats.device)
         bt = bt[:, None, :].expand(B, hi - lo, nb).reshape(B * (hi - lo), nb).contiguous()
-        out = head.body(bt, pose6d=p, want_verts=want_verts)
+        out = head.body(bt, pose6d=p, want_verts=want_verts, want_keypoints=want_kp)
         ctx.head, ctx.tape, ctx.shape, ctx.has_betas, ctx.verts_grad = head, tape, (B, K, lo, hi), betas is not None, verts_grad
+        ctx.outs = (want_verts, want_kp)
         ctx.save_for_backward(p, out["rotmats"], bt)
         ctx.set_materialize_grads(False)
         joints = out["joints"].view(B, hi - lo, J, 3)
         verts = out["vertices"].view(B, hi - lo, head.body.NV, 3) if want_verts else None
-        return (pose, lp.view(B, K), joints) + ((verts,) if want_verts else ())
+        kp = (out["keypoints"].view(B, hi - lo, head.body.NK, 3),) if want_kp else ()
+        return (pose, lp.view(B, K), joints) + ((verts,) if want_verts else ()) + kp
 
     @staticmethod
-    def backward(ctx, g_pose, g_lp, g_joints, *g_verts):
+    def backward(ctx, g_pose, g_lp, g_joints, *g_rest):
+        want_verts, want_kp = ctx.outs
+        gk = g_rest[-1] if want_kp else None
+        g_verts = g_rest[:1] if want_verts else ()
         gv = g_verts[0] if g_verts and g_verts[0] is not None and bool(g_verts[0].ne(0).any()) else None
         if gv is not None and not ctx.verts_grad:
             raise NotImplementedError("BodyFlowHead: no reverse pass through the vertex skinning by default - a loss on 'vertices' cannot be "
@@ -316,13 +413,14 @@ class _HeadFn(torch.autograd.Function):
         D, nb, J = head.flow.features, head.body.nb, head.body.J
         gx = torch.zeros(B, K, D, device=p.device) if g_pose is None else g_pose.float().contiguous().clone()
         g_betas = None
-        if g_joints is not None or gv is not None:
+        if g_joints is not None or gv is not None or gk is not None:
             n = hi - lo
             gj = None if g_joints is None else g_joints.float().reshape(B * n, J, 3).contiguous()
-            if gv is None:
+            if gv is None and gk is None:
                 g_rot, g_bt = lbs_pose_bwd(head.body, rotmats, bt, gj)
-            else:
-                g_rot, g_bt = lbs_bwd(head.body, rotmats, bt, gv.float().reshape(B * n, head.body.NV, 3).contiguous(), gj)
+            else:          # a keypoint gradient takes the skinning reverse whatever verts_grad says (its vertex-gradient buffer is lbs_bwd's own)
+                g_rot, g_bt = lbs_bwd(head.body, rotmats, bt, None if gv is None else gv.float().reshape(B * n, head.body.NV, 3).contiguous(), gj,
+                                      g_keypoints=None if gk is None else gk.float().reshape(B * n, head.body.NK, 3).contiguous())
             g6 = rot6d_to_rotmat_bwd(p.view(B * n, J, 6), g_rot)
             gx[:, lo:hi] += g6.view(B, n, D)
             if ctx.has_betas and ctx.needs_input_grad[2]:
@@ -333,4 +431,47 @@ class _HeadFn(torch.autograd.Function):
         grads, g_feats = _flow_backward(head.flow, ctx.tape, gx.view(B * K, D), glp)
         ctx.tape = None
         params = list(head.flow.parameters())
-        return (None, g_feats if ctx.needs_input_grad[1] else None, g_betas, None, None, None, None, None, None) + tuple(grads.get(q) for q in params)
+        return (None, g_feats if ctx.needs_input_grad[1] else None, g_betas, None, None, None, None, None, None, None) + tuple(grads.get(q) for q in params)
+
+
+class _KpLogProbFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, keypoints, cam, uv, vis, b):
+        B, K, NK = keypoints.shape[:3]
+        log_p = torch.empty(B, K, device=keypoints.device, dtype=torch.float32)
+        ops.check(_lib.lib().mhe_kp_log_prob_f32(ops._ptr(keypoints), ops._ptr(cam), ops._ptr(uv), ops._ptr(vis), ops._ptr(log_p), B, K, NK,
+                                                 int(cam.dim() == 3), b, ops._stream()), "mhe_kp_log_prob_f32")
+        ctx.save_for_backward(keypoints, cam, uv, vis)
+        ctx.b = b
+        return log_p
+
+    @staticmethod
+    def backward(ctx, g):
+        keypoints, cam, uv, vis = ctx.saved_tensors
+        B, K, NK = keypoints.shape[:3]
+        g = g.float().contiguous()
+        g_kp, g_cam = torch.empty_like(keypoints), torch.empty_like(cam)
+        ops.check(_lib.lib().mhe_kp_log_prob_bwd_f32(ops._ptr(keypoints), ops._ptr(cam), ops._ptr(uv), ops._ptr(vis), ops._ptr(g), ops._ptr(g_kp),
+                                                     ops._ptr(g_cam), B, K, NK, int(cam.dim() == 3), ctx.b, ops._stream()), "mhe_kp_log_prob_bwd_f32")
+        return g_kp, g_cam, None, None, None
+
+
+def keypoint_log_prob(keypoints, cam, uv, vis, b=0.03):
+    """log-likelihood of annotated 2D keypoints under each hypothesis (the data term of the reference's loss, hand/network.py:233-258 on the
+    orthographic projection of hand/ManoLayer.py:150-165, inv_norm=False): keypoints (B,K,NK,3), cam (B,K,3) or (B,3) = (s, tx, ty), uv (B,NK,2),
+    vis (B,NK) -> (B,K):  proj = s * keypoints[..., :2] + t;  sum over NK x 2 of [vis == 1] * (-(relu(|uv - proj| - 1e-4) + 1e-4) / b - log(2 b)).
+    One autograd node (mhe_kp_log_prob_f32 / mhe_kp_log_prob_bwd_f32): gradients to keypoints (z column 0) and cam; uv, vis and b are constants.
+    b = 0.03 is the reference's shipped value (ho3d.yaml:44).  ProHMR's own perspective camera is out of tree: unpinned, not this function."""
+    if not isinstance(keypoints, torch.Tensor) or keypoints.dim() != 4 or keypoints.shape[-1] != 3:
+        raise ValueError("keypoint_log_prob: keypoints must be a (B, K, NK, 3) tensor")
+    B, K, NK = keypoints.shape[:3]
+    if not 1 <= NK <= 64:
+        raise ValueError(f"keypoint_log_prob: NK={NK} outside 1..64")
+    if not isinstance(cam, torch.Tensor) or tuple(cam.shape) not in ((B, K, 3), (B, 3)):
+        raise ValueError(f"keypoint_log_prob: cam must be ({B}, {K}, 3) or ({B}, 3), got {tuple(getattr(cam, 'shape', ()))}")
+    if not float(b) > 0.0:
+        raise ValueError("keypoint_log_prob: b must be positive")
+    keypoints, cam = keypoints.contiguous(), cam.contiguous()
+    ops._chk(keypoints, torch.float32, "keypoint_log_prob.keypoints", (B, K, NK, 3)); ops._chk(cam, torch.float32, "keypoint_log_prob.cam")
+    ops._chk(uv, torch.float32, "keypoint_log_prob.uv", (B, NK, 2)); ops._chk(vis, torch.float32, "keypoint_log_prob.vis", (B, NK))
+    return _KpLogProbFn.apply(keypoints, cam, uv, vis, float(b))

@@ -298,13 +298,11 @@ __global__ __launch_bounds__(256) void lbs_transforms_bwd_kernel(const float *__
     }
 }
 
+// vertex vc (< NV) of hypotheses r0 .. r0 + HB - 1 (rows past R: row R - 1 again): out[h][c], scaled
 template <int HB>
-__global__ __launch_bounds__(256) void lbs_skin_kernel(const float *__restrict__ ws, const float *__restrict__ Vt, const float *__restrict__ Vsd,
-                                                       const float *__restrict__ Vpd, const float *__restrict__ Vw, float *__restrict__ verts_o,
-                                                       int R, int J, int nb, int NV, int VP, float scale) {
-    const int v = blockIdx.x * 256 + threadIdx.x;
-    const int r0 = blockIdx.y * HB;
-    const int vc = v < NV ? v : NV - 1;
+__device__ __forceinline__ void lbs_skin_vertex(const float *__restrict__ ws, const float *__restrict__ Vt, const float *__restrict__ Vsd,
+                                                const float *__restrict__ Vpd, const float *__restrict__ Vw, int r0, int vc, int R, int J, int nb, int VP,
+                                                float scale, float (&out)[HB][3]) {
     const int stride = ws_stride(J, nb), NP = 9 * (J - 1), oa = ws_a(J, nb), ob = ws_bt(J, nb);
     const float *wrow[HB];
 #pragma unroll
@@ -346,13 +344,80 @@ __global__ __launch_bounds__(256) void lbs_skin_kernel(const float *__restrict__
             for (int e = 0; e < 12; ++e) T[h][e] = fmaf(wrow[h][oa + j * 12 + e], wj, T[h][e]);
     }
 #pragma unroll
+    for (int h = 0; h < HB; ++h)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            out[h][c] = affine_row(T[h][3 * c], acc[h][0], T[h][3 * c + 1], acc[h][1], T[h][3 * c + 2], acc[h][2], T[h][9 + c], scale);   // :245-246
+}
+
+template <int HB>
+__global__ __launch_bounds__(256) void lbs_skin_kernel(const float *__restrict__ ws, const float *__restrict__ Vt, const float *__restrict__ Vsd,
+                                                       const float *__restrict__ Vpd, const float *__restrict__ Vw, float *__restrict__ verts_o,
+                                                       int R, int J, int nb, int NV, int VP, float scale) {
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    const int r0 = blockIdx.y * HB;
+    float out[HB][3];
+    lbs_skin_vertex<HB>(ws, Vt, Vsd, Vpd, Vw, r0, v < NV ? v : NV - 1, R, J, nb, VP, scale, out);
+#pragma unroll
     for (int h = 0; h < HB; ++h) {
         const int r = r0 + h;
         if (v < NV && r < R) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
-                verts_o[((size_t)r * NV + v) * 3 + c] =
-                    (T[h][3 * c] * acc[h][0] + T[h][3 * c + 1] * acc[h][1] + T[h][3 * c + 2] * acc[h][2] + T[h][9 + c]) * scale;   // :245-246
+            for (int c = 0; c < 3; ++c) verts_o[((size_t)r * NV + v) * 3 + c] = out[h][c];
+        }
+    }
+}
+
+// The same skinning with the keypoints (regressor (NK, NV) x scaled vertices) accumulated inside the pass: one workgroup walks ALL vertex blocks
+// for its HB hypotheses; per block of 256 vertices the vertices and the regressor's columns go through LDS and thread t adds the block's 256
+// terms, in order, to its (hypothesis, coordinate, keypoint) sums t, t + 256, ... (at most HB * 64 * 3 / 256 = 6), which stay in registers
+// across the vertex loop and are stored once: fixed summation order, no atomics.  verts_o may be null (no vertex tensor is written).
+// Dynamic LDS: (HB * 3 * 256 + NK * 257) floats.
+template <int HB>
+__global__ __launch_bounds__(256) void lbs_skin_kp_kernel(const float *__restrict__ ws, const float *__restrict__ Vt, const float *__restrict__ Vsd,
+                                                          const float *__restrict__ Vpd, const float *__restrict__ Vw, const float *__restrict__ reg,
+                                                          float *__restrict__ verts_o, float *__restrict__ kp_o, int R, int J, int nb, int NV, int VP,
+                                                          int NK, float scale) {
+    extern __shared__ float kp_smem[];
+    float *sV = kp_smem, *sR = kp_smem + HB * 3 * 256;          // [HB * 3][256], [NK][257]
+    constexpr int NQ = HB * 64 * 3 / 256;
+    const int tid = threadIdx.x, r0 = blockIdx.x * HB, NC = HB * 3 * NK;
+    float sum[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) sum[q] = 0.f;
+    for (int v0 = 0; v0 < NV; v0 += 256) {
+        const int v = v0 + tid;
+        float out[HB][3];
+        lbs_skin_vertex<HB>(ws, Vt, Vsd, Vpd, Vw, r0, v < NV ? v : NV - 1, R, J, nb, VP, scale, out);
+        __syncthreads();                                        // the previous block's sums are done with sV / sR
+#pragma unroll
+        for (int h = 0; h < HB; ++h) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sV[(h * 3 + c) * 256 + tid] = v < NV ? out[h][c] : 0.f;
+            if (verts_o && v < NV && r0 + h < R) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) verts_o[((size_t)(r0 + h) * NV + v) * 3 + c] = out[h][c];
+            }
+        }
+        for (int k = 0; k < NK; ++k) sR[k * 257 + tid] = v < NV ? reg[(size_t)k * NV + v] : 0.f;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int idx = tid + 256 * q;
+            if (idx < NC) {
+                const float *a = sV + (idx / NK) * 256, *b = sR + (idx % NK) * 257;
+                float t = sum[q];
+                for (int i = 0; i < 256; ++i) t = fmaf(b[i], a[i], t);
+                sum[q] = t;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int idx = tid + 256 * q;
+        if (idx < NC) {
+            const int hc = idx / NK, k = idx - hc * NK, h = hc / 3, c = hc - 3 * h;
+            if (r0 + h < R) kp_o[((size_t)(r0 + h) * NK + k) * 3 + c] = sum[q];
         }
     }
 }
@@ -421,4 +486,19 @@ extern "C" int mhe_lbs_skin_f32(const float *workspace, const float *v_template,
     hipLaunchKernelGGL(body::lbs_skin_kernel<HB>, dim3((NV + 255) / 256, (R + HB - 1) / HB), dim3(256), 0, (hipStream_t)stream, workspace,
                        v_template, v_shapedirs, v_posedirs, v_weights, verts, R, J, nb, NV, VP, scale);
     return check_launch("lbs_skin_kernel");
+}
+
+extern "C" int mhe_lbs_skin_kp_f32(const float *workspace, const float *v_template, const float *v_shapedirs, const float *v_posedirs,
+                                   const float *v_weights, const float *regressor, float *verts, float *keypoints, int R, int J, int nb, int NV, int VP,
+                                   int NK, float scale, void *stream) {
+    MHE_REQUIRE(NK >= 1 && NK <= 64, "mhe_lbs_skin_kp_f32: NK=%d outside 1..64", NK);
+    MHE_REQUIRE(workspace && v_template && v_shapedirs && v_posedirs && v_weights && regressor && keypoints,
+                "mhe_lbs_skin_kp_f32: null pointer (only verts may be null)");
+    MHE_REQUIRE(R > 0 && J > 0 && J <= body::MAXJ && nb > 0 && NV > 0 && VP >= NV, "mhe_lbs_skin_kp_f32: R=%d J=%d nb=%d NV=%d VP=%d", R, J, nb, NV, VP);
+    constexpr int HB = 8;
+    const int lds = (HB * 3 * 256 + NK * 257) * (int)sizeof(float);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(body::lbs_skin_kp_kernel<HB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL(body::lbs_skin_kp_kernel<HB>, dim3((R + HB - 1) / HB), dim3(256), lds, (hipStream_t)stream, workspace, v_template, v_shapedirs,
+                       v_posedirs, v_weights, regressor, verts, keypoints, R, J, nb, NV, VP, NK, scale);
+    return check_launch("lbs_skin_kp_kernel");
 }

@@ -61,6 +61,13 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// (t0 x0 + t1 x1 + t2 x2 + t3) * scale with the roundings spelled out (one product, two fused steps, one sum, one product): left to the
+// compiler's contraction, two instantiations of one kernel template fused different terms and differed in the last bit
+__device__ __forceinline__ float affine_row(float t0, float x0, float t1, float x1, float t2, float x2, float t3, float scale) {
+#pragma clang fp contract(off)
+    return (__builtin_fmaf(t2, x2, __builtin_fmaf(t1, x1, t0 * x0)) + t3) * scale;
+}
+
 __device__ __forceinline__ float bf16_to_f32(u16 h) {
     return __uint_as_float(((unsigned)h) << 16);
 }

@@ -76,10 +76,36 @@ __global__ __launch_bounds__(256) void lbs_split_tables_kernel(const float *__re
 
 #define MFMA(a, b, c) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, (a)), __builtin_bit_cast(bf8, (b)), (c), 0, 0, 0)
 
-template <int JS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void lbs_skin_mfma_kernel(const float *__restrict__ ws, const u16 *__restrict__ split, float *__restrict__ verts_o, int R, int J, int nb, int NV, int VP,
-                          int KS, float scale) {
+// Keypoints (NKT > 0: NK <= 32 NKT regressor rows, kp = regressor x scaled vertices) are accumulated inside the skinning pass: a wave turns each
+// finished coordinate of its 32 x 32 tile into three bf16 pieces in a private LDS tile [piece][hypothesis][vertex] (row pitch 80 bytes), reads
+// them back as the A operand (hypothesis = row, vertex = k) and multiplies by the regressor's pieces for that tile (lbs_kp_split_kernel; 3 x 3
+// pieces, 6 products, small terms first, as the transforms above) into 3 x NKT accumulators that stay with the wave across its vertex tiles.
+// After the loop the four waves' partial sums meet in LDS and are added in the fixed order ((w0 + w1) + w2) + w3: no atomics, two launches give
+// the same bits.  VERTS = false neither stores nor stages the vertices.
+constexpr int KP_PITCH = 40, KP_PIECE = 32 * KP_PITCH, KP_STAGE = 3 * KP_PIECE;          // u16 elements: row, piece, one wave's tile
+__host__ __device__ inline size_t lbs_kp_split_elems(int VT, int NKT) { return (size_t)VT * 2 * NKT * 3 * 512; }    // [VT][2 k-steps][NKT][3][512]
+
+// the (NK, NV) regressor -> bf16 pieces in MFMA B-operand order (lane l: keypoint 32 nkt + (l & 31), vertex 32 vt + 16 s + 8 (l >> 5) + 0..7)
+__global__ __launch_bounds__(256) void lbs_kp_split_kernel(const float *__restrict__ reg, u16 *__restrict__ out, int NK, int NV, int VT, int NKT) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = (int)(t & 63);
+    const long f = t >> 6;
+    if (f >= (long)VT * 2 * NKT) return;
+    const int nkt = (int)(f % NKT), s = (int)((f / NKT) & 1), vt = (int)(f / (2 * NKT));
+    const int k = nkt * 32 + (lane & 31);
+    u16 *o = out + ((size_t)f * 3 * 64 + lane) * 8;
+    for (int j = 0; j < 8; ++j) {
+        const int v = vt * 32 + s * 16 + (lane >> 5) * 8 + j;
+        u16 h = 0, m = 0, l = 0;
+        if (k < NK && v < NV) split3(reg[(size_t)k * NV + v], h, m, l);
+        o[j] = h; o[512 + j] = m; o[1024 + j] = l;
+    }
+}
+
+template <int JS, int NKT, bool VERTS>
+__device__ __forceinline__ void lbs_skin_mfma_body(const float *__restrict__ ws, const u16 *__restrict__ split, float *__restrict__ verts_o, int R, int J,
+                                                   int nb, int NV, int VP, int KS, float scale, const u16 *__restrict__ ksplit,
+                                                   float *__restrict__ kp_o, int NK) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u16 *PMb = reinterpret_cast<u16 *>(smem);                    // [KS][2 pieces][2 k halves][32 hypotheses][8]
     u16 *Gb = PMb + (size_t)KS * 2 * 512;                        // [12 e][JS][3 pieces][2 joint halves][32][8]
@@ -118,6 +144,19 @@ void lbs_skin_mfma_kernel(const float *__restrict__ ws, const u16 *__restrict__ 
     const uint4 *Ag = reinterpret_cast<const uint4 *>(Gb) + lane;            // + ((e * JS + js) * 3 + p) * 64
     const uint4 *Bpd = reinterpret_cast<const uint4 *>(split) + lane;
     const uint4 *Bw = reinterpret_cast<const uint4 *>(split + lbs_split_pd(VT, KS)) + lane;
+    // keypoints: this wave's staging tile (after the four waves' [16][64] stores), the regressor's pieces and the accumulators
+    u16 *const St = reinterpret_cast<u16 *>(smem + (size_t)KS * 2 * 1024 + 12 * JS * 3 * 1024 + 4 * 4096) + wave * KP_STAGE;
+    const uint4 *const Sa = reinterpret_cast<const uint4 *>(St) + (lane & 31) * (KP_PITCH / 8) + half;          // + p * (KP_PIECE / 8) + 2 s
+    const uint4 *const Bk = reinterpret_cast<const uint4 *>(ksplit) + lane;
+    f32x16 KP[3][NKT ? NKT : 1];
+    if constexpr (NKT > 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int n = 0; n < NKT; ++n)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) KP[c][n][i] = 0.f;
+    }
 
     // table pieces: two k-steps (6 fragments each) in flight ahead of the products, running on into the wave's next tile (KS is even)
     uint4 Bf[2][6], Wp[JS][3];
@@ -132,6 +171,15 @@ void lbs_skin_mfma_kernel(const float *__restrict__ ws, const u16 *__restrict__ 
         for (int js = 0; js < JS; ++js)
 #pragma unroll
             for (int p = 0; p < 3; ++p) Wp[js][p] = Bw[((vt * JS + js) * 3 + p) * 64];
+        uint4 Kf[2][NKT ? NKT : 1][3];
+        if constexpr (NKT > 0) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int n = 0; n < NKT; ++n)
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) Kf[s][n][p] = Bk[(((size_t)(vt * 2 + s) * NKT + n) * 3 + p) * 64];
+        }
         f32x16 X[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c)
@@ -174,17 +222,72 @@ void lbs_skin_mfma_kernel(const float *__restrict__ ws, const u16 *__restrict__ 
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const int hr = (i & 3) + 8 * (i >> 2);                    // (+ 4 * half) the accumulator's row = hypothesis within the workgroup
-                const float r = (T[0][i] * X[0][i] + T[1][i] * X[1][i] + T[2][i] * X[2][i] + T[3][i]) * scale;
+                const float r = affine_row(T[0][i], X[0][i], T[1][i], X[1][i], T[2][i], X[2][i], T[3][i], scale);
                 const unsigned soff = row0 + (unsigned)(hr * NV * 12);
-                if (c == 0) o0[i * 64] = r;
-                else if (c == 1) {
-                    typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-                    const u32x2 o = {__float_as_uint(o0[i * 64]), __float_as_uint(r)};
-                    __builtin_amdgcn_raw_buffer_store_b64(o, vout, (int)(hr < hlim ? voff : 0xffffffffu), (int)soff, 0);
-                } else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r), vout, (int)(hr < hlim ? voff : 0xffffffffu), (int)(soff + 8u), 0);
+                if constexpr (NKT > 0) {
+                    u16 ph, pm, pl;
+                    split3(r, ph, pm, pl);
+                    u16 *o = St + (hr + 4 * half) * KP_PITCH + vl;
+                    o[0] = ph; o[KP_PIECE] = pm; o[2 * KP_PIECE] = pl;
+                }
+                if constexpr (VERTS) {
+                    if (c == 0) o0[i * 64] = r;
+                    else if (c == 1) {
+                        typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+                        const u32x2 o = {__float_as_uint(o0[i * 64]), __float_as_uint(r)};
+                        __builtin_amdgcn_raw_buffer_store_b64(o, vout, (int)(hr < hlim ? voff : 0xffffffffu), (int)soff, 0);
+                    } else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r), vout, (int)(hr < hlim ? voff : 0xffffffffu), (int)(soff + 8u), 0);
+                }
+            }
+            if constexpr (NKT > 0) {
+                wave_sync();                     // the tile is the wave's own: its DS operations complete in order
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const uint4 ah = Sa[2 * s], am = Sa[KP_PIECE / 8 + 2 * s], al = Sa[2 * (KP_PIECE / 8) + 2 * s];
+#pragma unroll
+                    for (int n = 0; n < NKT; ++n) {
+                        MFMA(ah, Kf[s][n][2], KP[c][n]); MFMA(al, Kf[s][n][0], KP[c][n]); MFMA(am, Kf[s][n][1], KP[c][n]);       // small terms first
+                        MFMA(ah, Kf[s][n][1], KP[c][n]); MFMA(am, Kf[s][n][0], KP[c][n]); MFMA(ah, Kf[s][n][0], KP[c][n]);
+                    }
+                }
+                wave_sync();                     // (the next coordinate overwrites the tile)
             }
         }
     }
+    if constexpr (NKT > 0) {
+        // the four waves' partial sums: [wave][c][keypoint][hypothesis, pitch 33] over the hypotheses' pieces (every wave is past its last tile)
+        __syncthreads();
+        float *P = reinterpret_cast<float *>(smem);
+        constexpr int PW = 3 * NKT * 32 * 33;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int n = 0; n < NKT; ++n)
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    P[wave * PW + ((c * NKT + n) * 32 + vl) * 33 + (i & 3) + 8 * (i >> 2) + 4 * half] = KP[c][n][i];
+        __syncthreads();
+        for (int i = tid; i < HT * NK * 3; i += 256) {
+            const int h = i / (NK * 3), e = i - h * NK * 3, k = e / 3, c = e - 3 * k;
+            const float *q = P + (c * NKT * 32 + k) * 33 + h;
+            if (r0 + h < R) kp_o[(size_t)(r0 + h) * NK * 3 + e] = ((q[0] + q[PW]) + q[2 * PW]) + q[3 * PW];
+        }
+    }
+}
+
+template <int JS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void lbs_skin_mfma_kernel(const float *__restrict__ ws, const u16 *__restrict__ split, float *__restrict__ verts_o, int R, int J, int nb, int NV, int VP,
+                          int KS, float scale) {
+    lbs_skin_mfma_body<JS, 0, true>(ws, split, verts_o, R, J, nb, NV, VP, KS, scale, nullptr, nullptr, 0);
+}
+
+// the keypoint variants: one workgroup per CU either way (LDS), so one wave per SIMD and the whole register file (the accumulators in AGPRs)
+template <int JS, int NKT, bool VERTS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void lbs_skin_kp_mfma_kernel(const float *__restrict__ ws, const u16 *__restrict__ split, const u16 *__restrict__ ksplit, float *__restrict__ verts_o,
+                             float *__restrict__ kp_o, int R, int J, int nb, int NV, int VP, int KS, int NK, float scale) {
+    lbs_skin_mfma_body<JS, NKT, VERTS>(ws, split, verts_o, R, J, nb, NV, VP, KS, scale, ksplit, kp_o, NK);
 }
 
 }}  // namespace mhe::body
@@ -232,4 +335,63 @@ extern "C" int mhe_lbs_skin_mfma_f32(const float *workspace, const float *split,
                            R, J, nb, NV, VP, KS, scale);
     }
     return check_launch("lbs_skin_mfma_kernel");
+}
+
+extern "C" size_t mhe_lbs_kp_split_floats(int NK, int VP) {
+    if (NK < 1 || NK > 64 || VP <= 0 || VP % 32) return 0;
+    return (body::lbs_kp_split_elems(VP / 32, (NK + 31) / 32) * sizeof(u16) + 3) / 4;
+}
+
+extern "C" int mhe_lbs_kp_split_tables_f32(const float *regressor, float *ksplit, int NK, int NV, int VP, void *stream) {
+    MHE_REQUIRE(regressor && ksplit, "mhe_lbs_kp_split_tables_f32: null pointer");
+    MHE_REQUIRE(NK >= 1 && NK <= 64 && NV > 0 && VP >= NV && VP % 32 == 0, "mhe_lbs_kp_split_tables_f32: NK=%d (1..64) NV=%d VP=%d (VP >= NV, a multiple of 32)",
+                NK, NV, VP);
+    const int VT = VP / 32, NKT = (NK + 31) / 32;
+    const long frags = (long)VT * 2 * NKT;
+    hipLaunchKernelGGL(body::lbs_kp_split_kernel, dim3((unsigned)((frags * 64 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, regressor,
+                       reinterpret_cast<u16 *>(ksplit), NK, NV, VT, NKT);
+    return check_launch("lbs_kp_split_kernel");
+}
+
+static size_t lbs_kp_lds(int J, int nb, int NK) {
+    const size_t skin = (size_t)body::lbs_ks(J, nb) * 2048 + (size_t)12 * body::lbs_js(J) * 3072 + 4 * 4096 + 4 * body::KP_STAGE * sizeof(u16);
+    const size_t sums = (size_t)4 * 3 * ((NK + 31) / 32) * 32 * 33 * sizeof(float);
+    return skin > sums ? skin : sums;
+}
+
+extern "C" int mhe_lbs_skin_kp_supported(int R, int J, int nb, int NV, int VP, int NK, int want_verts) {
+    if (R <= 0 || J <= 0 || J > 32 || nb <= 0 || NV <= 0 || VP < NV || VP % 32 || NK < 1 || NK > 64) return 0;
+    if (want_verts && (size_t)(R + 64) * NV * 12 >= (1ull << 32)) return 0;                     // 32-bit byte offsets of the vertex output
+    return lbs_kp_lds(J, nb, NK) <= 160 * 1024;
+}
+
+template <int JS, int NKT, bool VERTS>
+static void launch_skin_kp(const float *ws, const u16 *split, const u16 *ksplit, float *verts, float *kp, int R, int J, int nb, int NV, int VP, int NK,
+                           float scale, hipStream_t stream) {
+    const int lds = (int)lbs_kp_lds(J, nb, NK);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(body::lbs_skin_kp_mfma_kernel<JS, NKT, VERTS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL((body::lbs_skin_kp_mfma_kernel<JS, NKT, VERTS>), dim3((unsigned)((R + body::HT - 1) / body::HT)), dim3(256), lds, stream, ws, split,
+                       ksplit, verts, kp, R, J, nb, NV, VP, body::lbs_ks(J, nb), NK, scale);
+}
+
+extern "C" int mhe_lbs_skin_kp_mfma_f32(const float *workspace, const float *split, const float *ksplit, float *verts, float *keypoints, int R, int J,
+                                        int nb, int NV, int VP, int NK, float scale, void *stream) {
+    MHE_REQUIRE(NK >= 1 && NK <= 64, "mhe_lbs_skin_kp_mfma_f32: NK=%d outside 1..64", NK);
+    MHE_REQUIRE(workspace && split && ksplit && keypoints, "mhe_lbs_skin_kp_mfma_f32: null pointer (only verts may be null)");
+    MHE_REQUIRE(mhe_lbs_skin_kp_supported(R, J, nb, NV, VP, NK, verts != nullptr),
+                "mhe_lbs_skin_kp_mfma_f32: R=%d J=%d nb=%d NV=%d VP=%d NK=%d not supported (see mhe_lbs_skin_kp_supported)", R, J, nb, NV, VP, NK);
+    const u16 *sp = reinterpret_cast<const u16 *>(split), *ks = reinterpret_cast<const u16 *>(ksplit);
+    hipStream_t st = (hipStream_t)stream;
+    const int JS = body::lbs_js(J), NKT = (NK + 31) / 32;
+#define MHE_KP_LAUNCH(js, nkt)                                                                                      \
+    do {                                                                                                            \
+        if (verts) launch_skin_kp<js, nkt, true>(workspace, sp, ks, verts, keypoints, R, J, nb, NV, VP, NK, scale, st); \
+        else launch_skin_kp<js, nkt, false>(workspace, sp, ks, verts, keypoints, R, J, nb, NV, VP, NK, scale, st);      \
+    } while (0)
+    if (JS == 1 && NKT == 1) MHE_KP_LAUNCH(1, 1);
+    else if (JS == 1) MHE_KP_LAUNCH(1, 2);
+    else if (NKT == 1) MHE_KP_LAUNCH(2, 1);
+    else MHE_KP_LAUNCH(2, 2);
+#undef MHE_KP_LAUNCH
+    return check_launch("lbs_skin_kp_mfma_kernel");
 }

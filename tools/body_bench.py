@@ -7,7 +7,11 @@ forward-only time of the same call under no_grad.  VERTS=1 (with TRAIN=1) adds t
 with verts_grad=True, and the time of the skinning reverse alone (body.lbs_bwd) next to the forward skinning.
 NLL=1 runs the maximum-likelihood leg INSTEAD of the sampling legs (B rows, one annotated pose per image; K is not used): forward-only
 head.log_prob under no_grad, and forward + backward of -log_prob.mean(), both in f32, each as the median of WINDOWS (7) timing windows.  STEPS=n
-(with NLL=1) runs n untimed forward + backward steps only (for a kernel trace)."""
+(with NLL=1) runs n untimed forward + backward steps only (for a kernel trace).
+Keypoints (NK = 17 rows of a synthetic regressor; always printed): route (a) want_verts=True + torch.einsum with the regressor, route (b)
+want_verts=False, want_keypoints=True (accumulated inside the skinning pass), and the plain vertex call, as medians of WINDOWS alternating windows;
+TRAIN=1 adds the train step of log_prob.mean() - keypoint_log_prob(...).mean() next to the step of log_prob.mean() alone.  KPONLY=1 stops after
+the keypoint lines (for a kernel trace of the three routes)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -15,7 +19,8 @@ import torch
 from mhentropy_amd import body, synth
 
 B, K = int(os.environ.get("B", 128)), int(os.environ.get("K", 128))
-head = body.BodyFlowHead(body.synthetic_body_tables(0), context_features=2048, hidden=1024, num_layers=4, num_blocks=2)
+NK = 17
+head = body.BodyFlowHead(body.synthetic_body_tables(0, keypoints=NK), context_features=2048, hidden=1024, num_layers=4, num_blocks=2)
 head.flow.load_state_dict({k: torch.as_tensor(v) for k, v in synth.glow_state(1, 144, 1024, 4, 2, 2048).items()}, strict=False)
 head = head.cuda().eval()
 head.flow.compute_dtype = torch.bfloat16 if os.environ.get("DT", "bf16") == "bf16" else torch.float32
@@ -73,7 +78,27 @@ with torch.no_grad():
     ms_joints = t(lambda: head.body(bt, rotmats=rm, want_verts=False))
     ms_all = t(lambda: head(feats, K, betas=betas, noise=noise))
     ms_slice = t(lambda: head(feats, K, betas=betas, noise=noise, hyp_slice=(0, K // 8)))
+    # keypoints: what a caller could do before (vertices + a product the caller writes) against the fused pass; alternating windows, medians
+    reg = head.body.keypoint_regressor
+    route_a = lambda: torch.einsum("kv,rvc->rkc", reg, head.body(bt, rotmats=rm)["vertices"])
+    route_b = lambda: head.body(bt, rotmats=rm, want_verts=False, want_keypoints=True)["keypoints"]
+    route_v = lambda: head.body(bt, rotmats=rm)["vertices"]
+    route_vk = lambda: head.body(bt, rotmats=rm, want_keypoints=True)["keypoints"]
+    dkp = float((route_a() - route_b()).abs().max())
+    W = int(os.environ.get("WINDOWS", 7))
+    tw = {k: [] for k in "abvk"}
+    for _ in range(W):
+        for k, fn in (("a", route_a), ("b", route_b), ("v", route_v), ("k", route_vk)):
+            tw[k].append(t(fn, n=10))
+    md = {k: sorted(v)[W // 2] for k, v in tw.items()}
+    rng_ = {k: (min(v), max(v)) for k, v in tw.items()}
 vb = R * 6890 * 12
+print(f"keypoints NK={NK} R={R} (median of {W} windows [min, max]): (a) vertices + einsum {md['a']:.3f} ms [{rng_['a'][0]:.3f}, {rng_['a'][1]:.3f}] | "
+      f"(b) fused, no vertex tensor {md['b']:.3f} ms [{rng_['b'][0]:.3f}, {rng_['b'][1]:.3f}] = {md['b'] / md['a']:.3f}x of (a) | max |a - b| {dkp:.2e}")
+print(f"keypoints NK={NK} R={R}: vertices alone {md['v']:.3f} ms [{rng_['v'][0]:.3f}, {rng_['v'][1]:.3f}] | vertices + fused keypoints "
+      f"{md['k']:.3f} ms [{rng_['k'][0]:.3f}, {rng_['k'][1]:.3f}]")
+if os.environ.get("KPONLY", "0") == "1":
+    sys.exit(0)
 print(f"B={B} K={K} R={R}: glow sample+log_prob {ms_flow:.2f} ms | rot6d {ms_rot * 1e3:.0f} us | LBS 6,890 verts {ms_lbs:.2f} ms "
       f"({vb / ms_lbs / 1e6:.0f} GB/s of vertices written, {R * 6890 * 3 * (10 + 207 + 96 + 4) / ms_lbs / 1e9:.1f} TFMA/s) | joints only {ms_joints * 1e3:.0f} us")
 print(f"whole head {ms_all:.2f} ms = {R / ms_all * 1e3:.3e} hypotheses/s ; decoding a 1/8 hypothesis slice {ms_slice:.2f} ms")
@@ -95,6 +120,22 @@ if os.environ.get("TRAIN", "0") == "1":
     ms_train = t(step, n=3)
     print(f"train leg (f32, joints only) B={B} K={K}: forward {ms_fwd32:.2f} ms | forward + backward {ms_train:.2f} ms "
           f"({ms_train / ms_fwd32:.2f}x the forward)")
+
+    cam = torch.cat([torch.rand(B, 1, device="cuda") + 0.5, torch.randn(B, 2, device="cuda") * 0.1], 1)
+    uv, vis = torch.randn(B, NK, 2, device="cuda") * 0.3, (torch.rand(B, NK, device="cuda") < 0.7).float()
+
+    def kstep(with_kp):
+        for p_ in head.flow.parameters():
+            p_.grad = None
+        out = head(feats, K, betas=betas, noise=noise, want_verts=False, want_keypoints=with_kp)
+        loss = out["log_prob"].mean()
+        if with_kp:
+            loss = loss - body.keypoint_log_prob(out["keypoints"], cam, uv, vis).mean()
+        loss.backward()
+
+    ms_ent, ms_kp = t(lambda: kstep(False), n=3), t(lambda: kstep(True), n=3)
+    print(f"train leg (f32, 2D keypoints) B={B} K={K} NK={NK}: log_prob.mean() alone {ms_ent:.2f} ms | log_prob.mean() - keypoint_log_prob.mean() "
+          f"{ms_kp:.2f} ms (+{ms_kp - ms_ent:.2f} ms: fused keypoints, likelihood, keypoint + skinning reverse in {body.KP_BWD_ROWS}-row passes)")
 
     if os.environ.get("VERTS", "0") == "1":
         tv = torch.randn(B, K, 6890, 3, device="cuda") * 0.3
