@@ -906,6 +906,26 @@ int mhe_kp_log_prob_f32(const float *keypoints, const float *cam, const float *u
                         int cam_per_hyp, float b, void *stream);
 int mhe_kp_log_prob_bwd_f32(const float *keypoints, const float *cam, const float *uv, const float *vis, const float *g, float *g_keypoints,
                             float *g_cam, int B, int K, int NK, int cam_per_hyp, float b, void *stream);
+/* Mesh error of R hypotheses against B target meshes (R % B == 0, row r belongs to image r / (R / B)), accumulated INSIDE the skinning pass: no
+ * [R,NV,3] tensor exists.  err [R] = mean over v of || scale vert[r][v] - center[r] - target_verts[b][v] ||_2; target_verts [B,NV,3], center [R,3]
+ * or NULL (zero).  The vertex values are the ones mhe_lbs_skin_mfma_f32 / mhe_lbs_skin_f32 would store; fixed summation order, no atomics (two
+ * calls give the same bits); one division by NV at the end.  Inference only.
+ *   mhe_lbs_skin_err_mfma_f32 (csrc/lbs_skin.hip): the matrix-core skinning; mhe_lbs_skin_err_supported: its limits (mhe_lbs_skin_mfma_supported's
+ *     without the 4 GiB output, and B NV 3 < 2^31 target elements).
+ *   mhe_lbs_skin_err_f32 (csrc/body.hip): the scalar-operand skinning, one workgroup per 8 hypotheses walking all vertices; any size. */
+int mhe_lbs_skin_err_supported(int R, int J, int nb, int NV, int VP, int B);
+int mhe_lbs_skin_err_mfma_f32(const float *workspace, const float *split, const float *target_verts, const float *center, float *err, int R, int B,
+                              int J, int nb, int NV, int VP, float scale, void *stream);
+int mhe_lbs_skin_err_f32(const float *workspace, const float *v_template, const float *v_shapedirs, const float *v_posedirs, const float *v_weights,
+                         const float *target_verts, const float *center, float *err, int R, int B, int J, int nb, int NV, int VP, float scale,
+                         void *stream);
+/* Evaluation reductions (csrc/body_eval.hip; inference only, fixed summation order).
+ * mhe_point_errors_f32: points [B,K,P,3], target [B,P,3], 1 <= P <= 64 -> err [B,K] = mean over p of the Euclidean distance, after the mean of the
+ *   points whose bit is set in root_mask (bit q = point q; 0: none) has been subtracted from the prediction and from the target.
+ * mhe_min_of_n_f32: err [B,K], ns = n (1..8) strictly increasing integers in 1..K in HOST memory -> values [B,n] = min err[b][0 .. ns[i]-1] and
+ *   index [B,n] (int32) = the lowest k attaining it.  Non-finite input is not rejected and its result is unspecified (the index stays in range). */
+int mhe_point_errors_f32(const float *points, const float *target, float *err, int B, int K, int P, unsigned long long root_mask, void *stream);
+int mhe_min_of_n_f32(const float *err, float *values, int *index, int B, int K, const int *ns, int n, void *stream);
 
 #ifdef __cplusplus
 }

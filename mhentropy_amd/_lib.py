@@ -189,6 +189,11 @@ SIGNATURES = {
     "mhe_lbs_skin_kp_mfma_f32": (_i, [_p] * 5 + [_i] * 6 + [_f, _p]),
     "mhe_lbs_skin_kp_f32": (_i, [_p] * 8 + [_i] * 6 + [_f, _p]),
     "mhe_lbs_keypoints_bwd_f32": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "mhe_lbs_skin_err_supported": (_i, [_i] * 6),
+    "mhe_lbs_skin_err_mfma_f32": (_i, [_p] * 5 + [_i] * 6 + [_f, _p]),
+    "mhe_lbs_skin_err_f32": (_i, [_p] * 8 + [_i] * 6 + [_f, _p]),
+    "mhe_point_errors_f32": (_i, [_p] * 3 + [_i] * 3 + [C.c_ulonglong, _p]),
+    "mhe_min_of_n_f32": (_i, [_p] * 3 + [_i, _i, _p, _i, _p]),
     "mhe_kp_log_prob_f32": (_i, [_p] * 5 + [_i] * 4 + [_f, _p]),
     "mhe_kp_log_prob_bwd_f32": (_i, [_p] * 7 + [_i] * 4 + [_f, _p]),
     "mhe_topk_gather_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),

@@ -190,6 +190,124 @@ class BodyLayer(nn.Module):
             out["vertices"] = verts
         return out
 
+    def vertex_error(self, betas, rotmats=None, pose6d=None, target_verts=None, center=None, scale=1.0):
+        """mean per-vertex error of R hypotheses against B target meshes without a vertex tensor: betas (R,nb); rotmats (R,J,3,3) or pose6d (R,6J);
+        target_verts (B,NV,3) with R % B == 0 (row r belongs to image r // (R // B): the head's batch-major order); center (R,3) or None (zero) ->
+        err (R,) = mean over v of || scale * vert[r, v] - center[r] - target_verts[b, v] ||_2, accumulated inside the skinning pass
+        (mhe_lbs_skin_err_mfma_f32, or mhe_lbs_skin_err_f32 with MHE_LBS_MFMA=0 / sizes the matrix-core kernel does not take) from the values
+        `forward` would store as 'vertices'; fixed summation order (two calls give the same bits).  Inference only: no gradient."""
+        if not isinstance(target_verts, torch.Tensor) or target_verts.dim() != 3 or tuple(target_verts.shape[1:]) != (self.NV, 3):
+            raise ValueError(f"BodyLayer.vertex_error: target_verts must be a (B, {self.NV}, 3) tensor, got {tuple(getattr(target_verts, 'shape', ()))}")
+        if (rotmats is None) == (pose6d is None):
+            raise ValueError("BodyLayer.vertex_error: give exactly one of rotmats and pose6d")
+        R, B = (rotmats if rotmats is not None else pose6d).shape[0], target_verts.shape[0]
+        if B < 1 or R % B:
+            raise ValueError(f"BodyLayer.vertex_error: R={R} rows are not a multiple of B={B} target meshes")
+        if tuple(betas.shape) != (R, self.nb):
+            raise ValueError(f"BodyLayer.vertex_error: betas must be ({R}, {self.nb}), got {tuple(betas.shape)}")
+        if center is not None and tuple(center.shape) != (R, 3):
+            raise ValueError(f"BodyLayer.vertex_error: center must be ({R}, 3), got {tuple(center.shape)}")
+        with torch.no_grad():
+            if rotmats is None:
+                rotmats = rot6d_to_rotmat(pose6d.reshape(-1, self.J, 6).contiguous())
+            rotmats, betas, target_verts = rotmats.contiguous(), betas.contiguous(), target_verts.contiguous()
+            ops._chk(rotmats, torch.float32, "body.rotmats", (R, self.J, 3, 3)); ops._chk(betas, torch.float32, "body.betas", (R, self.nb))
+            ops._chk(target_verts, torch.float32, "body.target_verts", (B, self.NV, 3))
+            if center is not None:
+                center = center.contiguous()
+                ops._chk(center, torch.float32, "body.center", (R, 3))
+            L, dev = _lib.lib(), rotmats.device
+            ws = torch.empty(L.mhe_lbs_workspace_floats(R, self.J, self.nb), device=dev, dtype=torch.float32)
+            ops.check(L.mhe_lbs_pose_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(self._jt), ops._ptr(self._jsd), ops._ptr(self.parents), ops._ptr(ws),
+                                         None, R, self.J, self.nb, ops._stream()), "mhe_lbs_pose_f32")
+            err = torch.empty(R, device=dev, dtype=torch.float32)
+            if os.environ.get("MHE_LBS_MFMA", "1") == "1" and L.mhe_lbs_skin_err_supported(R, self.J, self.nb, self.NV, self.VP, B):
+                ops.check(L.mhe_lbs_skin_err_mfma_f32(ops._ptr(ws), ops._ptr(self._split_tables(dev)), ops._ptr(target_verts), ops._ptr(center), ops._ptr(err),
+                                                      R, B, self.J, self.nb, self.NV, self.VP, float(scale), ops._stream()), "mhe_lbs_skin_err_mfma_f32")
+            else:
+                ops.check(L.mhe_lbs_skin_err_f32(ops._ptr(ws), ops._ptr(self._vt), ops._ptr(self._vsd), ops._ptr(self._vpd), ops._ptr(self._vw),
+                                                 ops._ptr(target_verts), ops._ptr(center), ops._ptr(err), R, B, self.J, self.nb, self.NV, self.VP,
+                                                 float(scale), ops._stream()), "mhe_lbs_skin_err_f32")
+        return err
+
+
+def _root_indices(root, P, who):
+    """root = None | int | tuple of ints -> a tuple of distinct indices in 0..P-1 (ValueError otherwise)"""
+    if root is None:
+        return ()
+    try:
+        idx = (root,) if isinstance(root, (int, np.integer)) else tuple(root)
+    except TypeError:
+        idx = ()
+    if not idx or any(not isinstance(q, (int, np.integer)) or isinstance(q, bool) for q in idx):
+        raise ValueError(f"{who}: root must be None, an int or a non-empty tuple of ints, got {root!r}")
+    if any(not 0 <= q < P for q in idx):
+        raise ValueError(f"{who}: root index outside 0..{P - 1}: {root!r}")
+    if len(set(idx)) != len(idx):
+        raise ValueError(f"{who}: root indices repeat: {root!r}")
+    return tuple(int(q) for q in idx)
+
+
+def _check_ns(ns, K, who):
+    ns = tuple(ns) if not isinstance(ns, (int, np.integer)) else (ns,)
+    if not 1 <= len(ns) <= 8 or any(not isinstance(n, (int, np.integer)) or isinstance(n, bool) for n in ns):
+        raise ValueError(f"{who}: ns must hold 1 to 8 integers, got {ns!r}")
+    if any(not 1 <= n <= K for n in ns) or any(b <= a for a, b in zip(ns, ns[1:])):
+        raise ValueError(f"{who}: ns must be strictly increasing within 1..K={K}, got {ns!r}")
+    return tuple(int(n) for n in ns)
+
+
+def _point_errors_launch(points, target, mask):
+    B, K, P = points.shape[:3]
+    err = torch.empty(B, K, device=points.device, dtype=torch.float32)
+    ops.check(_lib.lib().mhe_point_errors_f32(ops._ptr(points), ops._ptr(target), ops._ptr(err), B, K, P, mask, ops._stream()), "mhe_point_errors_f32")
+    return err
+
+
+def point_errors(points, target, root=None):
+    """points (B,K,P,3), target (B,P,3), 1 <= P <= 64 -> {'mpjpe' (B,K), 'pa_mpjpe' (B,K)}.  `root` (None, an index or a tuple of indices, e.g. the
+    two hips): the mean of those points is subtracted from each prediction and from the target before the error is taken.
+    mpjpe = mean over P of the Euclidean distance (mhe_point_errors_f32: one wave per row, fixed summation order).  pa_mpjpe = the same error
+    after the project's Procrustes alignment with scale of every hypothesis to its target (ops.procrustes_align on the sample-major view, then the
+    same kernel without centring).  Convention, pinned with that kernel: the reference's align_w_scale (hand/utils.py:502-525), R = U V^T WITHOUT
+    the determinant correction, so the optimal map may be a reflection where the data ask for one.  ProHMR's own evaluation code is out of tree:
+    whether it corrects the determinant is unpinned.  Inference only."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 4 or points.shape[-1] != 3:
+        raise ValueError("point_errors: points must be a (B, K, P, 3) tensor")
+    B, K, P = points.shape[:3]
+    if not 1 <= P <= 64:
+        raise ValueError(f"point_errors: P={P} outside 1..64")
+    if not isinstance(target, torch.Tensor) or tuple(target.shape) != (B, P, 3):
+        raise ValueError(f"point_errors: target must be ({B}, {P}, 3), got {tuple(getattr(target, 'shape', ()))}")
+    idx = _root_indices(root, P, "point_errors")
+    mask = sum(1 << q for q in idx)
+    with torch.no_grad():
+        points, target = points.contiguous(), target.contiguous()
+        ops._chk(points, torch.float32, "point_errors.points", (B, K, P, 3)); ops._chk(target, torch.float32, "point_errors.target", (B, P, 3))
+        mpjpe = _point_errors_launch(points, target, mask)
+        aligned = ops.procrustes_align(points.permute(1, 0, 2, 3).contiguous(), target)                 # (K, B, P, 3), in the target's frame
+        pa = _point_errors_launch(aligned.permute(1, 0, 2, 3).contiguous(), target, 0)
+    return {"mpjpe": mpjpe, "pa_mpjpe": pa}
+
+
+def min_of_n(err, ns):
+    """err (B,K), ns = 1 to 8 strictly increasing integers in 1..K -> (values (B,len(ns)) f32, index (B,len(ns)) int32): values[b, i] =
+    min err[b, :ns[i]], index = the lowest k attaining it (mhe_min_of_n_f32).  Non-finite input is rejected nowhere and its result is
+    unspecified.  Inference only."""
+    if not isinstance(err, torch.Tensor) or err.dim() != 2:
+        raise ValueError("min_of_n: err must be a (B, K) tensor")
+    B, K = err.shape
+    ns = _check_ns(ns, K, "min_of_n")
+    with torch.no_grad():
+        err = err.contiguous()
+        ops._chk(err, torch.float32, "min_of_n.err", (B, K))
+        val = torch.empty(B, len(ns), device=err.device, dtype=torch.float32)
+        idx = torch.empty(B, len(ns), device=err.device, dtype=torch.int32)
+        arr = (C.c_int * len(ns))(*ns)
+        ops.check(_lib.lib().mhe_min_of_n_f32(ops._ptr(err), ops._ptr(val), ops._ptr(idx), B, K, C.cast(arr, C.c_void_p), len(ns), ops._stream()),
+                  "mhe_min_of_n_f32")
+    return val, idx
+
 
 class BodyFlowHead(nn.Module):
     """ProHMR's sampling surface (reference README.md:26-42): `flow(conditioning_feats, num_samples)` draws K poses with
@@ -244,6 +362,60 @@ class BodyFlowHead(nn.Module):
             res["vertices"] = out["vertices"].view(B, hi - lo, self.body.NV, 3)
         if want_keypoints:
             res["keypoints"] = out["keypoints"].view(B, hi - lo, self.body.NK, 3)
+        return res
+
+    def evaluate(self, feats, num_samples, target_keypoints, target_verts=None, betas=None, noise=None, ns=(1, 5, 10, 25), root=None, mode_first=True):
+        """the multi-hypothesis evaluation protocol on the GPU, under no_grad in whatever mode the module is in: feats (B,F), target_keypoints
+        (B,NK,3) (the frame of the body layer's 'keypoints'), target_verts (B,NV,3) or None, betas (B,nb) or None (zero) -> a dict of plain tensors:
+        'mpjpe', 'pa_mpjpe' (B,K) (point_errors of the mesh-regressed keypoints; `root` as there), 'pve' (B,K) (only with target_verts:
+        BodyLayer.vertex_error, the prediction centred on its own root keypoint and the target on its own - nothing is centred with root=None),
+        'min_mpjpe', 'min_pa_mpjpe', 'min_pve' (B,len(ns)) and 'argmin_*' (int32) = min_of_n over the first ns[i] hypotheses, 'log_prob' (B,K),
+        'pose6d' (B,K,6J).  mode_first: hypothesis 0 of every image is decoded from zero noise, the mode of the flow (ProHMR's protocol); a given
+        `noise` (B,K,6J) is copied, never written.  No (B K, NV, 3) tensor is allocated.  ProHMR's own joint maps, camera and Procrustes variant
+        are out of tree: parity with its published numbers is unpinned (see point_errors).  ValueError before any GPU work: tables without a
+        'keypoint_regressor', a root index outside NK, ns outside 1..K or not increasing, shape mismatches."""
+        NK, NV, nb, D = self.body.NK, self.body.NV, self.body.nb, self.flow.features
+        if not NK:
+            raise ValueError("BodyFlowHead.evaluate: needs body tables with a 'keypoint_regressor'")
+        if not isinstance(feats, torch.Tensor) or feats.dim() != 2:
+            raise ValueError("BodyFlowHead.evaluate: feats must be a (B, F) tensor")
+        B, K = feats.shape[0], int(num_samples)
+        if K < 1:
+            raise ValueError(f"BodyFlowHead.evaluate: num_samples={num_samples}")
+        if not isinstance(target_keypoints, torch.Tensor) or tuple(target_keypoints.shape) != (B, NK, 3):
+            raise ValueError(f"BodyFlowHead.evaluate: target_keypoints must be ({B}, {NK}, 3), got {tuple(getattr(target_keypoints, 'shape', ()))}")
+        if target_verts is not None and (not isinstance(target_verts, torch.Tensor) or tuple(target_verts.shape) != (B, NV, 3)):
+            raise ValueError(f"BodyFlowHead.evaluate: target_verts must be ({B}, {NV}, 3), got {tuple(getattr(target_verts, 'shape', ()))}")
+        if betas is not None and tuple(betas.shape) != (B, nb):
+            raise ValueError(f"BodyFlowHead.evaluate: betas must be ({B}, {nb}), got {tuple(betas.shape)}")
+        if noise is not None and tuple(noise.shape) != (B, K, D):
+            raise ValueError(f"BodyFlowHead.evaluate: noise must be ({B}, {K}, {D}), got {tuple(noise.shape)}")
+        idx = _root_indices(root, NK, "BodyFlowHead.evaluate")
+        ns = _check_ns(ns, K, "BodyFlowHead.evaluate")
+        with torch.no_grad():
+            dev = feats.device
+            if noise is None:
+                noise = ops.randn(B * K, D, dev).view(B, K, D)
+            elif mode_first:
+                noise = noise.clone()
+            if mode_first:
+                noise[:, 0] = 0.0
+            pose, logp, _ = self.flow.sample_and_log_prob(K, noise=noise, context=feats)
+            p = pose.reshape(B * K, D).contiguous()
+            bt = betas if betas is not None else torch.zeros(B, nb, device=dev)
+            bt = bt[:, None, :].expand(B, K, nb).reshape(B * K, nb).contiguous()
+            out = self.body(bt, pose6d=p, want_verts=False, want_keypoints=True)
+            kp = out["keypoints"].view(B, K, NK, 3)
+            res = {"pose6d": pose, "log_prob": logp, **point_errors(kp, target_keypoints, root)}
+            if target_verts is not None:
+                center, tv = None, target_verts
+                if idx:
+                    center = kp[:, :, list(idx)].mean(2).reshape(B * K, 3)
+                    tv = target_verts - target_keypoints[:, list(idx)].mean(1, keepdim=True)
+                res["pve"] = self.body.vertex_error(bt, rotmats=out["rotmats"], target_verts=tv, center=center).view(B, K)
+            for k in ("mpjpe", "pa_mpjpe", "pve"):
+                if k in res:
+                    res["min_" + k], res["argmin_" + k] = min_of_n(res[k], ns)
         return res
 
     def log_prob(self, feats, pose6d=None, rotmats=None):

@@ -422,6 +422,59 @@ __global__ __launch_bounds__(256) void lbs_skin_kp_kernel(const float *__restric
     }
 }
 
+// The same skinning with the mesh error accumulated inside the pass (no vertex tensor): err[r] = mean_v || scale vert[r][v] - center[r] -
+// target[r / rpi][v] ||.  One workgroup walks all vertex blocks for its HB hypotheses; thread t keeps HB sums over the vertices t, t + 256, ...
+// (a thread past NV adds exactly 0 and re-reads vertex NV - 1 of the target, never beyond it); then per hypothesis 16 threads add 16 consecutive
+// threads' sums each, in order, and one thread adds those 16, in order: fixed summation order, no atomics.  One division by NV at the end.
+template <int HB>
+__global__ __launch_bounds__(256) void lbs_skin_err_kernel(const float *__restrict__ ws, const float *__restrict__ Vt, const float *__restrict__ Vsd,
+                                                           const float *__restrict__ Vpd, const float *__restrict__ Vw, const float *__restrict__ tgt,
+                                                           const float *__restrict__ center, float *__restrict__ err_o, int R, int J, int nb, int NV,
+                                                           int VP, int rpi, float scale) {
+    __shared__ float sE[HB][256], sP[HB][16], sC[HB][3];
+    __shared__ size_t sT[HB];                                   // the hypotheses' centres and target offsets (registers go to the skinning)
+    const int tid = threadIdx.x, r0 = blockIdx.x * HB;
+    if (tid < HB * 3) {
+        const int h = tid / 3, r = r0 + h < R ? r0 + h : R - 1;
+        sC[h][tid - 3 * h] = center ? center[(size_t)r * 3 + (tid - 3 * h)] : 0.f;
+        if (tid == 3 * h) sT[h] = (size_t)(r / rpi) * NV * 3;
+    }
+    __syncthreads();
+    float sum[HB];
+#pragma unroll
+    for (int h = 0; h < HB; ++h) sum[h] = 0.f;
+    for (int v0 = 0; v0 < NV; v0 += 256) {
+        const int v = v0 + tid, vc = v < NV ? v : NV - 1;
+        float out[HB][3];
+        lbs_skin_vertex<HB>(ws, Vt, Vsd, Vpd, Vw, r0, vc, R, J, nb, VP, scale, out);
+#pragma unroll
+        for (int h = 0; h < HB; ++h) {
+            float sq = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float d = (out[h][c] - sC[h][c]) - tgt[sT[h] + vc * 3 + c];
+                sq = c == 0 ? d * d : fmaf(d, d, sq);
+            }
+            sum[h] += v < NV ? sqrtf(sq) : 0.f;
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < HB; ++h) sE[h][tid] = sum[h];
+    __syncthreads();
+    if (tid < HB * 16) {
+        const float *q = &sE[tid >> 4][(tid & 15) * 16];
+        float a = q[0];
+        for (int i = 1; i < 16; ++i) a += q[i];
+        sP[tid >> 4][tid & 15] = a;
+    }
+    __syncthreads();
+    if (tid < HB && r0 + tid < R) {
+        float a = sP[tid][0];
+        for (int i = 1; i < 16; ++i) a += sP[tid][i];
+        err_o[r0 + tid] = a / (float)NV;
+    }
+}
+
 }}  // namespace mhe::body
 
 using namespace mhe;
@@ -501,4 +554,17 @@ extern "C" int mhe_lbs_skin_kp_f32(const float *workspace, const float *v_templa
     hipLaunchKernelGGL(body::lbs_skin_kp_kernel<HB>, dim3((R + HB - 1) / HB), dim3(256), lds, (hipStream_t)stream, workspace, v_template, v_shapedirs,
                        v_posedirs, v_weights, regressor, verts, keypoints, R, J, nb, NV, VP, NK, scale);
     return check_launch("lbs_skin_kp_kernel");
+}
+
+extern "C" int mhe_lbs_skin_err_f32(const float *workspace, const float *v_template, const float *v_shapedirs, const float *v_posedirs,
+                                    const float *v_weights, const float *target_verts, const float *center, float *err, int R, int B, int J, int nb,
+                                    int NV, int VP, float scale, void *stream) {
+    MHE_REQUIRE(workspace && v_template && v_shapedirs && v_posedirs && v_weights && target_verts && err,
+                "mhe_lbs_skin_err_f32: null pointer (only center may be null)");
+    MHE_REQUIRE(R > 0 && J > 0 && J <= body::MAXJ && nb > 0 && NV > 0 && VP >= NV, "mhe_lbs_skin_err_f32: R=%d J=%d nb=%d NV=%d VP=%d", R, J, nb, NV, VP);
+    MHE_REQUIRE(B > 0 && R % B == 0, "mhe_lbs_skin_err_f32: R=%d is not a multiple of B=%d", R, B);
+    constexpr int HB = 8;
+    hipLaunchKernelGGL(body::lbs_skin_err_kernel<HB>, dim3((R + HB - 1) / HB), dim3(256), 0, (hipStream_t)stream, workspace, v_template, v_shapedirs,
+                       v_posedirs, v_weights, target_verts, center, err, R, J, nb, NV, VP, R / B, scale);
+    return check_launch("lbs_skin_err_kernel");
 }

@@ -102,10 +102,24 @@ __global__ __launch_bounds__(256) void lbs_kp_split_kernel(const float *__restri
     }
 }
 
-template <int JS, int NKT, bool VERTS>
+//
+// Mesh error (ERR; NKT = 0, VERTS = false): err[r] = mean_v || scale vert[r][v] - center[r] - target[r / rpi][v] ||, accumulated inside the pass from
+// the very values the vertex store would write.  The workgroup's 32 centres and target-image offsets wait in LDS (the [16][64] staging tiles of
+// the vertex store are free here); a lane loads its vertex's 12 target bytes once per tile when the 32 rows share an image, per row otherwise;
+// the squared difference is summed over c = 0..2, the root taken after c = 2 and added (0 for lanes without a vertex: a select, never a product
+// with what was loaded) to 16 per-lane row sums that stay with the wave across its tiles.  After the loop: per wave and row the 32 vertex lanes
+// in lane order, then ((w0 + w1) + w2) + w3, then one division by NV: no atomics, two launches give the same bits.
+struct ErrArgs {
+    const float *tgt, *center;          // [B][NV][3]; [R][3] or null (zero)
+    float *err_o;                       // [R]
+    int rpi;                            // rows per image (R / B)
+};
+
+template <int JS, int NKT, bool VERTS, bool ERR = false>
 __device__ __forceinline__ void lbs_skin_mfma_body(const float *__restrict__ ws, const u16 *__restrict__ split, float *__restrict__ verts_o, int R, int J,
                                                    int nb, int NV, int VP, int KS, float scale, const u16 *__restrict__ ksplit,
-                                                   float *__restrict__ kp_o, int NK) {
+                                                   float *__restrict__ kp_o, int NK, const ErrArgs ea = ErrArgs{nullptr, nullptr, nullptr, 1}) {
+    static_assert(!ERR || (NKT == 0 && !VERTS), "the error mode neither stores vertices nor regresses keypoints");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u16 *PMb = reinterpret_cast<u16 *>(smem);                    // [KS][2 pieces][2 k halves][32 hypotheses][8]
     u16 *Gb = PMb + (size_t)KS * 2 * 512;                        // [12 e][JS][3 pieces][2 joint halves][32][8]
@@ -133,8 +147,25 @@ __device__ __forceinline__ void lbs_skin_mfma_body(const float *__restrict__ ws,
         u16 *o = Gb + (((e * JS + (j >> 4)) * 3) * 2 + ((j >> 3) & 1)) * 256 + h * 8 + (j & 7);
         o[0] = hi; o[512] = mi; o[1024] = lo;
     }
+    float *const Cn = reinterpret_cast<float *>(smem + (size_t)KS * 2 * 1024 + 12 * JS * 3 * 1024);          // [32][3] centres, then [32] target offsets
+    unsigned *const Im = reinterpret_cast<unsigned *>(Cn + 3 * HT);
+    if constexpr (ERR) {
+        if (tid < 3 * HT) {
+            const int h = tid / 3, r = r0 + h < R ? r0 + h : R - 1;
+            Cn[tid] = ea.center ? ea.center[(size_t)r * 3 + (tid - 3 * h)] : 0.f;
+        } else if (tid < 4 * HT) {
+            const int h = tid - 3 * HT, r = r0 + h < R ? r0 + h : R - 1;
+            Im[h] = (unsigned)(r / ea.rpi) * (unsigned)(NV * 3);
+        }
+    }
     __syncthreads();
     const int vl = lane & 31, half = lane >> 5;
+    const bool one_image = r0 / ea.rpi == (r0 + HT - 1 < R ? r0 + HT - 1 : R - 1) / ea.rpi;          // the 32 rows share their target
+    f32x16 E, SQ;
+    if constexpr (ERR) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) E[i] = 0.f;
+    }
     float *const o0 = reinterpret_cast<float *>(smem + (size_t)KS * 2 * 1024 + 12 * JS * 3 * 1024) + wave * 1024 + lane;      // [16][64] per wave
     const int hlim = R - r0 - 4 * half;                         // rows of this lane's half past the end are not stored
     const __amdgpu_buffer_rsrc_t vout = __builtin_amdgcn_make_buffer_rsrc(verts_o, 0, (int)((unsigned)R * (unsigned)(NV * 12)), 0x00020000);
@@ -179,6 +210,14 @@ __device__ __forceinline__ void lbs_skin_mfma_body(const float *__restrict__ ws,
                 for (int n = 0; n < NKT; ++n)
 #pragma unroll
                     for (int p = 0; p < 3; ++p) Kf[s][n][p] = Bk[(((size_t)(vt * 2 + s) * NKT + n) * 3 + p) * 64];
+        }
+        const unsigned tv = (unsigned)((vt * 32 + vl < NV ? vt * 32 + vl : NV - 1) * 3);          // lanes without a vertex re-read the last one
+        float tg[3] = {0.f, 0.f, 0.f};
+        if constexpr (ERR) {
+            if (one_image) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) tg[c] = ea.tgt[Im[0] + tv + c];
+            }
         }
         f32x16 X[3];
 #pragma unroll
@@ -239,6 +278,25 @@ __device__ __forceinline__ void lbs_skin_mfma_body(const float *__restrict__ ws,
                     } else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r), vout, (int)(hr < hlim ? voff : 0xffffffffu), (int)(soff + 8u), 0);
                 }
             }
+            if constexpr (ERR) {
+                // the same affine_row on the same operands as the store above; a real branch, so that the 16 per-row loads are issued only where
+                // the rows do not share an image and one coordinate at a time
+                auto add = [&](int i, float t) {
+                    const int hr = (i & 3) + 8 * (i >> 2) + 4 * half;
+                    const float r = affine_row(T[0][i], X[0][i], T[1][i], X[1][i], T[2][i], X[2][i], T[3][i], scale);
+                    const float d = (r - Cn[hr * 3 + c]) - t;
+                    SQ[i] = c == 0 ? d * d : __builtin_fmaf(d, d, SQ[i]);
+                    if (c == 2) E[i] += v < NV ? __builtin_sqrtf(SQ[i]) : 0.f;
+                };
+                if (one_image) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) add(i, tg[c]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) add(i, ea.tgt[Im[(i & 3) + 8 * (i >> 2) + 4 * half] + tv + c]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
             if constexpr (NKT > 0) {
                 wave_sync();                     // the tile is the wave's own: its DS operations complete in order
 #pragma unroll
@@ -273,6 +331,22 @@ __device__ __forceinline__ void lbs_skin_mfma_body(const float *__restrict__ ws,
             if (r0 + h < R) kp_o[(size_t)(r0 + h) * NK * 3 + e] = ((q[0] + q[PW]) + q[2 * PW]) + q[3 * PW];
         }
     }
+    if constexpr (ERR) {
+        // [wave][row][vertex lane, pitch 33] over the hypotheses' pieces (every wave is past its last tile), then [wave][row] behind it
+        __syncthreads();
+        float *P = reinterpret_cast<float *>(smem), *S = P + 4 * HT * 33;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) P[(wave * HT + (i & 3) + 8 * (i >> 2) + 4 * half) * 33 + vl] = E[i];
+        __syncthreads();
+        if (tid < 4 * HT) {
+            const float *q = P + tid * 33;
+            float a = q[0];
+            for (int l = 1; l < 32; ++l) a += q[l];
+            S[tid] = a;
+        }
+        __syncthreads();
+        if (tid < HT && r0 + tid < R) ea.err_o[r0 + tid] = (((S[tid] + S[HT + tid]) + S[2 * HT + tid]) + S[3 * HT + tid]) / (float)NV;
+    }
 }
 
 template <int JS>
@@ -280,6 +354,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void lbs_skin_mfma_kernel(const float *__restrict__ ws, const u16 *__restrict__ split, float *__restrict__ verts_o, int R, int J, int nb, int NV, int VP,
                           int KS, float scale) {
     lbs_skin_mfma_body<JS, 0, true>(ws, split, verts_o, R, J, nb, NV, VP, KS, scale, nullptr, nullptr, 0);
+}
+
+// the mesh-error variant: one workgroup per CU (LDS), one wave per SIMD as the keypoint variants (at two waves the 32 extra accumulator
+// registers and the per-row target loads spill)
+template <int JS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void lbs_skin_err_mfma_kernel(const float *__restrict__ ws, const u16 *__restrict__ split, const float *__restrict__ tgt, const float *__restrict__ center,
+                              float *__restrict__ err_o, int R, int J, int nb, int NV, int VP, int KS, int rpi, float scale) {
+    lbs_skin_mfma_body<JS, 0, false, true>(ws, split, nullptr, R, J, nb, NV, VP, KS, scale, nullptr, nullptr, 0, ErrArgs{tgt, center, err_o, rpi});
 }
 
 // the keypoint variants: one workgroup per CU either way (LDS), so one wave per SIMD and the whole register file (the accumulators in AGPRs)
@@ -394,4 +477,32 @@ extern "C" int mhe_lbs_skin_kp_mfma_f32(const float *workspace, const float *spl
     else MHE_KP_LAUNCH(2, 2);
 #undef MHE_KP_LAUNCH
     return check_launch("lbs_skin_kp_mfma_kernel");
+}
+
+extern "C" int mhe_lbs_skin_err_supported(int R, int J, int nb, int NV, int VP, int B) {
+    if (R <= 0 || J <= 0 || J > 32 || nb <= 0 || NV <= 0 || VP < NV || VP % 32 || B <= 0 || R % B) return 0;
+    if ((size_t)B * NV * 3 >= (1ull << 31)) return 0;                                           // 32-bit element offsets into the targets
+    const size_t lds = (size_t)body::lbs_ks(J, nb) * 2048 + (size_t)12 * body::lbs_js(J) * 3072 + 4 * 4096;
+    return lds <= 160 * 1024;
+}
+
+extern "C" int mhe_lbs_skin_err_mfma_f32(const float *workspace, const float *split, const float *target_verts, const float *center, float *err, int R,
+                                         int B, int J, int nb, int NV, int VP, float scale, void *stream) {
+    MHE_REQUIRE(workspace && split && target_verts && err, "mhe_lbs_skin_err_mfma_f32: null pointer (only center may be null)");
+    MHE_REQUIRE(mhe_lbs_skin_err_supported(R, J, nb, NV, VP, B),
+                "mhe_lbs_skin_err_mfma_f32: R=%d B=%d J=%d nb=%d NV=%d VP=%d not supported (see mhe_lbs_skin_err_supported)", R, B, J, nb, NV, VP);
+    const int KS = body::lbs_ks(J, nb), JS = body::lbs_js(J);
+    const int lds = KS * 2048 + 12 * JS * 3072 + 4 * 4096;          // the plain kernel's: the sums (4 x 32 x 34 floats) fit over the pieces
+    const dim3 grid((unsigned)((R + body::HT - 1) / body::HT));
+    const u16 *sp = reinterpret_cast<const u16 *>(split);
+    if (JS == 1) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(body::lbs_skin_err_mfma_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        hipLaunchKernelGGL(body::lbs_skin_err_mfma_kernel<1>, grid, dim3(256), lds, (hipStream_t)stream, workspace, sp, target_verts, center, err, R, J, nb,
+                           NV, VP, KS, R / B, scale);
+    } else {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(body::lbs_skin_err_mfma_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        hipLaunchKernelGGL(body::lbs_skin_err_mfma_kernel<2>, grid, dim3(256), lds, (hipStream_t)stream, workspace, sp, target_verts, center, err, R, J, nb,
+                           NV, VP, KS, R / B, scale);
+    }
+    return check_launch("lbs_skin_err_mfma_kernel");
 }

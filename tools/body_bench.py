@@ -11,7 +11,11 @@ head.log_prob under no_grad, and forward + backward of -log_prob.mean(), both in
 Keypoints (NK = 17 rows of a synthetic regressor; always printed): route (a) want_verts=True + torch.einsum with the regressor, route (b)
 want_verts=False, want_keypoints=True (accumulated inside the skinning pass), and the plain vertex call, as medians of WINDOWS alternating windows;
 TRAIN=1 adds the train step of log_prob.mean() - keypoint_log_prob(...).mean() next to the step of log_prob.mean() alone.  KPONLY=1 stops after
-the keypoint lines (for a kernel trace of the three routes)."""
+the keypoint lines (for a kernel trace of the three routes).
+EVAL=1 runs the evaluation leg INSTEAD of the other legs: head.evaluate(...) with target_verts (min-of-n MPJPE / PA-MPJPE / per-vertex error, no
+vertex tensor) against the composition from the calls that existed before it - head(..., want_verts=True, want_keypoints=True), the same errors
+in torch on the (B, K, NV, 3) tensor, ops.procrustes_align for the aligned error, torch.cummin for the minima - on the same noise, as medians of
+WINDOWS alternating windows; prints the largest difference between the two routes' errors."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -63,6 +67,45 @@ if os.environ.get("NLL", "0") == "1":
     tr = sorted(t(nll_step, n=10) for _ in range(W))
     print(f"NLL leg (f32, one pose per image) B={B}: forward log_prob {fw[W // 2]:.3f} ms (min {fw[0]:.3f}, max {fw[-1]:.3f} over {W} windows) | "
           f"forward + backward {tr[W // 2]:.3f} ms (min {tr[0]:.3f}, max {tr[-1]:.3f}) = {tr[W // 2] / fw[W // 2]:.2f}x the forward")
+    sys.exit(0)
+
+
+if os.environ.get("EVAL", "0") == "1":
+    from mhentropy_amd import ops
+    ns, root, NV = (1, 5, 10, 25), (11, 12), head.body.NV
+    tk, tv = torch.randn(B, NK, 3, device="cuda") * 0.3, torch.randn(B, NV, 3, device="cuda") * 0.3
+    z = noise.clone()
+    z[:, 0] = 0.0
+
+    def fused():
+        return head.evaluate(feats, K, tk, target_verts=tv, betas=betas, noise=noise, ns=ns, root=root)
+
+    def composed():
+        with torch.no_grad():
+            out = head(feats, K, betas=betas, noise=z, want_verts=True, want_keypoints=True)
+            kp, r = out["keypoints"], list(root)
+            cen, tcen = kp[:, :, r].mean(2, keepdim=True), tk[:, r].mean(1, keepdim=True)
+            res = {"mpjpe": ((kp - cen) - (tk - tcen)[:, None]).norm(dim=-1).mean(-1)}
+            al = ops.procrustes_align(kp.permute(1, 0, 2, 3).contiguous(), tk).permute(1, 0, 2, 3)
+            res["pa_mpjpe"] = (al - tk[:, None]).norm(dim=-1).mean(-1)
+            res["pve"] = ((out["vertices"] - cen) - (tv - tcen)[:, None]).norm(dim=-1).mean(-1)
+            for k in ("mpjpe", "pa_mpjpe", "pve"):
+                cm = torch.cummin(res[k], 1)
+                res["min_" + k], res["argmin_" + k] = cm.values[:, [n - 1 for n in ns]], cm.indices[:, [n - 1 for n in ns]]
+        return res
+
+    a_, b_ = fused(), composed()
+    diff = {k: float((a_[k] - b_[k]).abs().max()) for k in ("mpjpe", "pa_mpjpe", "pve", "min_pve")}
+    del a_, b_
+    W = int(os.environ.get("WINDOWS", 7))
+    tf, tc = [], []
+    for _ in range(W):
+        tf.append(t(fused, n=5)); tc.append(t(composed, n=5))
+    tf, tc = sorted(tf), sorted(tc)
+    print(f"EVAL leg B={B} K={K} NK={NK} NV={NV} ns={ns} (flow {os.environ.get('DT', 'bf16')}; median of {W} alternating windows of 5 [min, max]): "
+          f"head.evaluate (fused mesh error, no vertex tensor) {tf[W // 2]:.3f} ms [{tf[0]:.3f}, {tf[-1]:.3f}] | composition (vertices + torch errors) "
+          f"{tc[W // 2]:.3f} ms [{tc[0]:.3f}, {tc[-1]:.3f}] = {tc[W // 2] / tf[W // 2]:.2f}x the fused call | max |fused - composed|: "
+          + ", ".join(f"{k} {v:.2e}" for k, v in diff.items()))
     sys.exit(0)
 
 
