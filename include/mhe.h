@@ -313,6 +313,13 @@ int mhe_bottleneck_tail_nhwc(const mhe_conv_desc *d, int Cb, const void *y2, con
                              const void *w3, const float *bn3_scale, const float *bn3_shift, const void *identity,
                              const float *id_scale, const float *id_shift, const void *w1, void *a_out, void *y1, mhe_stat_t *stats,
                              void *stream);
+/* ... at a stage entry of the forward-only path, where the one reader of `a` left is the next block's stride-2 1x1 shortcut: a_quarter
+ * [B, ceil(H/2), ceil(W/2), Cin] receives `a` at the pixels on even rows and even columns only, pixel (b, oy, ox) at
+ * ((b * ceil(H/2) + oy / 2) * ceil(W/2) + ox / 2) * Cin; nothing else is written of it.  y1 and stats equal mhe_bottleneck_tail_nhwc's bit for bit. */
+int mhe_bottleneck_tail_quarter_nhwc(const mhe_conv_desc *d, int Cb, const void *y2, const float *bn2_scale, const float *bn2_shift,
+                                     const void *w3, const float *bn3_scale, const float *bn3_shift, const void *identity,
+                                     const float *id_scale, const float *id_shift, const void *w1, void *a_quarter, void *y1,
+                                     mhe_stat_t *stats, void *stream);
 
 int mhe_conv2d_nhwc(const mhe_conv_desc *d, const void *x, const void *w, void *y,
                     const float *in_scale, const float *in_shift,
@@ -366,6 +373,12 @@ int mhe_conv_tile_mode(const mhe_conv_desc *d, int mode);
 int mhe_conv1x1_residual_in_nhwc(const mhe_conv_desc *d, const void *x, const void *x2, const void *w, void *y,
                                  const float *in_scale, const float *in_shift, const float *x2_scale,
                                  const float *x2_shift, void *a_out, mhe_stat_t *stats, void *stream);
+/* The same with `a` written at even rows and even columns only, into the compact a_quarter [B, ceil(H/2), ceil(W/2), Cin] (layout as
+ * mhe_bottleneck_tail_quarter_nhwc): the stage entries of the forward-only path.  y and stats are unchanged bit for bit.  Only the
+ * residual-tail kernel (variant 10: mhe_conv_tile_mode(d, 2) == 10) has this output; any other geometry is refused. */
+int mhe_conv1x1_residual_in_quarter_nhwc(const mhe_conv_desc *d, const void *x, const void *x2, const void *w, void *y,
+                                         const float *in_scale, const float *in_shift, const float *x2_scale,
+                                         const float *x2_shift, void *a_quarter, mhe_stat_t *stats, void *stream);
 
 /* ResNet stem: 7x7 stride-2 pad-3 convolution 3 -> 64 (torchvision `conv1`, reference hand/network.py:54-61)
  * read straight from the NCHW f32 image x [B,3,H,W]; w [64][192] with k = 24*kh + 3*kw + c (each kh row of
@@ -398,6 +411,13 @@ int mhe_bn_finalize(const mhe_stat_t *stats, const float *gamma, const float *be
 int mhe_bn_finalize_step(mhe_stat_t *stats, const float *gamma, const float *beta,
                          float *running_mean, float *running_var, float *scale, float *shift, float *mean_invstd,
                          int C, double count, float momentum, float eps, int clear_stats, long long *num_batches_tracked, void *stream);
+/* mhe_bn_finalize_step for TWO independent units in one launch (bn3 and the shortcut's BatchNorm of a downsample block): each unit has its
+ * own channel count, pixel count, parameters, running buffers and counter, and comes out bit for bit as from a launch of its own. */
+int mhe_bn_finalize_pair_step(mhe_stat_t *stats0, const float *gamma0, const float *beta0, float *running_mean0, float *running_var0,
+                              float *scale0, float *shift0, float *mean_invstd0, int C0, double count0, long long *num_batches_tracked0,
+                              mhe_stat_t *stats1, const float *gamma1, const float *beta1, float *running_mean1, float *running_var1,
+                              float *scale1, float *shift1, float *mean_invstd1, int C1, double count1, long long *num_batches_tracked1,
+                              float momentum, float eps, int clear_stats, void *stream);
 
 /* y = relu?(x*scale+shift (+ r*r_scale+r_shift | + r)) elementwise over NHWC
  * [P,C]; the bottleneck tail bn3 + identity + relu (torchvision Bottleneck). */

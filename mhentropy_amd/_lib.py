@@ -133,6 +133,7 @@ SIGNATURES = {
     "mhe_conv_tile": (_i, [C.POINTER(ConvDesc)]),
     "mhe_conv_tile_mode": (_i, [C.POINTER(ConvDesc), _i]),
     "mhe_conv1x1_residual_in_nhwc": (_i, [C.POINTER(ConvDesc)] + [_p] * 11),
+    "mhe_conv1x1_residual_in_quarter_nhwc": (_i, [C.POINTER(ConvDesc)] + [_p] * 11),
     "mhe_stem_conv7x7s2": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "mhe_conv1x1_stats_nhwc": (_i, [_p, _p, _p, _p, _p, _p, _p]),
     "mhe_conv_wgrad_batched_workspace_floats": (_sz, [_p, _i]),
@@ -159,10 +160,12 @@ SIGNATURES = {
     "mhe_gram_bn_finalize": (_i, [_p] * 10 + [_i, _i, _d, _f, _f, _p, _p]),
     "mhe_bottleneck_tail_supported": (_i, [_p, _i]),
     "mhe_bottleneck_tail_nhwc": (_i, [_p, _i] + [_p] * 14),
+    "mhe_bottleneck_tail_quarter_nhwc": (_i, [_p, _i] + [_p] * 14),
     "mhe_stem_pool_supported": (_i, [_i, _i, _i, _i]),
     "mhe_stem_conv7x7s2_pool": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "mhe_bn_finalize": (_i, [_p] * 8 + [_i, _d, _f, _f, _p]),
     "mhe_bn_finalize_step": (_i, [_p] * 8 + [_i, _d, _f, _f, _i, _p, _p]),
+    "mhe_bn_finalize_pair_step": (_i, ([_p] * 8 + [_i, _d, _p]) * 2 + [_f, _f, _i, _p]),
     "mhe_bn_act_nhwc": (_i, [_p] * 7 + [_l, _i, _i, _i, _p]),
     "mhe_maxpool3x3s2_nhwc": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "mhe_avgpool_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _p]),

@@ -300,15 +300,11 @@ __global__ __launch_bounds__(256) void stem_kernel(const float *__restrict__ x, 
 // one wavefront per channel: lane = statistic shard (NSH == 64); the shard words are summed as INTEGERS (exact, order-free) and
 // decoded to f64 once (the serial walk over the 64 shards made this ~6 us latency-bound kernel, launched once per BatchNorm, 3 % of
 // the forward step).  `stats` is read and - clear != 0 - zeroed through the SAME pointer (loads first, then the zero stores).
-__global__ __launch_bounds__(256) void bn_finalize_kernel(mhe_stat_t *stats, const float *__restrict__ gamma,
-                                                          const float *__restrict__ beta, float *__restrict__ rmean, float *__restrict__ rvar,
-                                                          float *__restrict__ scale, float *__restrict__ shift, float *__restrict__ mean_invstd, int C,
-                                                          double count, float momentum, float eps, int clear,
-                                                          long long *__restrict__ num_batches_tracked) {
-    static_assert(NSH == 64, "one lane per statistic shard");
-    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (num_batches_tracked && blockIdx.x == 0 && threadIdx.x == 0) *num_batches_tracked += 1;      // nn.BatchNorm2d's counter (int64)
-    if (c >= C) return;
+// (the body of both finalize kernels: channel c of one BatchNorm unit, one wavefront)
+__device__ __forceinline__ void bn_finalize_channel(mhe_stat_t *stats, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                    float *__restrict__ rmean, float *__restrict__ rvar, float *__restrict__ scale,
+                                                    float *__restrict__ shift, float *__restrict__ mean_invstd, int C, int c, int lane,
+                                                    double count, float momentum, float eps, int clear) {
     // self-cleaning accumulators: the arena is zero again when the next forward starts (no memset launch per step)
     double s1, s2;
     fx::wave_totals(stats, C, c, lane, clear != 0, s1, s2);
@@ -324,6 +320,35 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(mhe_stat_t *stats, con
     if (mean_invstd) { mean_invstd[c] = mean; mean_invstd[C + c] = 1.f / sqrtf(var + eps); }     // kept for the reverse pass
     if (rmean) rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
     if (rvar) rvar[c] = (1.f - momentum) * rvar[c] + momentum * var * (float)(count / (count - 1.0));
+}
+
+__global__ __launch_bounds__(256) void bn_finalize_kernel(mhe_stat_t *stats, const float *__restrict__ gamma,
+                                                          const float *__restrict__ beta, float *__restrict__ rmean, float *__restrict__ rvar,
+                                                          float *__restrict__ scale, float *__restrict__ shift, float *__restrict__ mean_invstd, int C,
+                                                          double count, float momentum, float eps, int clear,
+                                                          long long *__restrict__ num_batches_tracked) {
+    static_assert(NSH == 64, "one lane per statistic shard");
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (num_batches_tracked && blockIdx.x == 0 && threadIdx.x == 0) *num_batches_tracked += 1;      // nn.BatchNorm2d's counter (int64)
+    if (c >= C) return;
+    bn_finalize_channel(stats, gamma, beta, rmean, rvar, scale, shift, mean_invstd, C, c, lane, count, momentum, eps, clear);
+}
+
+// Two independent BatchNorm units in ONE launch (bn3 and the shortcut's BatchNorm of a downsample block: both sets of statistics are complete
+// before either affine is needed, and a finalize launch is ~6 us of pure dependency chain).  Blocks 0 .. nb0 - 1 own unit 0, the rest unit 1;
+// each unit is finalized exactly as bn_finalize_kernel does it.
+struct BnUnit {
+    mhe_stat_t *stats; const float *gamma, *beta; float *rmean, *rvar, *scale, *shift, *mean_invstd;
+    long long *num_batches_tracked; double count; int C;
+};
+__global__ __launch_bounds__(256) void bn_finalize_pair_kernel(const BnUnit u0, const BnUnit u1, int nb0, float momentum, float eps, int clear) {
+    const bool second = (int)blockIdx.x >= nb0;
+    const BnUnit &u = second ? u1 : u0;
+    const int blk = (int)blockIdx.x - (second ? nb0 : 0);
+    const int c = blk * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (u.num_batches_tracked && blk == 0 && threadIdx.x == 0) *u.num_batches_tracked += 1;
+    if (c >= u.C) return;
+    bn_finalize_channel(u.stats, u.gamma, u.beta, u.rmean, u.rvar, u.scale, u.shift, u.mean_invstd, u.C, c, lane, u.count, momentum, eps, clear);
 }
 
 // y = relu?(x*scale+shift + (res*rscale+rshift | res))   4 channels per thread
@@ -636,7 +661,7 @@ static int conv_entry(const mhe_conv_desc *d, const void *x, const void *w, void
                       const float *in_shift, const float *out_scale, const float *out_shift, const void *residual,
                       mhe_stat_t *stats, const void *x2, const float *x2_scale, const float *x2_shift, void *a_out, void *stream,
                       const void *mask = nullptr, const struct BnRev *bn = nullptr, float *y32 = nullptr, const int *scatter = nullptr,
-                      const void *xcat = nullptr, int cin2 = 0, const void *mask_bits = nullptr);
+                      const void *xcat = nullptr, int cin2 = 0, const void *mask_bits = nullptr, int a_quarter = 0);
 struct BnRev { const void *y[2]; const float *mi[2]; mhe_stat_t *stats[2]; };
 
 extern "C" int mhe_conv2d_nhwc(const mhe_conv_desc *d, const void *x, const void *w, void *y, const float *in_scale,
@@ -659,6 +684,16 @@ extern "C" int mhe_conv1x1_residual_in_nhwc(const mhe_conv_desc *d, const void *
     MHE_REQUIRE(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0, "mhe_conv1x1_residual_in_nhwc: 1x1 stride-1 only");
     MHE_REQUIRE((x2_scale == nullptr) == (x2_shift == nullptr), "mhe_conv1x1_residual_in_nhwc: x2_scale/x2_shift must come together");
     return conv_entry(d, x, w, y, in_scale, in_shift, nullptr, nullptr, nullptr, stats, x2, x2_scale, x2_shift, a_out, stream);
+}
+
+extern "C" int mhe_conv1x1_residual_in_quarter_nhwc(const mhe_conv_desc *d, const void *x, const void *x2, const void *w, void *y,
+                                                    const float *in_scale, const float *in_shift, const float *x2_scale,
+                                                    const float *x2_shift, void *a_quarter, mhe_stat_t *stats, void *stream) {
+    MHE_REQUIRE(d && x2 && in_scale && in_shift && a_quarter, "mhe_conv1x1_residual_in_quarter_nhwc: x2, in_scale, in_shift and a_quarter are required");
+    MHE_REQUIRE(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0, "mhe_conv1x1_residual_in_quarter_nhwc: 1x1 stride-1 only");
+    MHE_REQUIRE((x2_scale == nullptr) == (x2_shift == nullptr), "mhe_conv1x1_residual_in_quarter_nhwc: x2_scale/x2_shift must come together");
+    return conv_entry(d, x, w, y, in_scale, in_shift, nullptr, nullptr, nullptr, stats, x2, x2_scale, x2_shift, a_quarter, stream, nullptr, nullptr, nullptr,
+                      nullptr, nullptr, 0, nullptr, 1);
 }
 
 extern "C" int mhe_conv1x1_cat_bias_nhwc(const mhe_conv_desc *d, const void *x, const void *xcat, int cin2, const void *w, void *y, const void *residual,
@@ -742,7 +777,8 @@ extern "C" int mhe_conv3x3s2_dgrad_nhwc(int B, int Ho, int Wo, int Cout, int Cin
 static int conv_entry(const mhe_conv_desc *d, const void *x, const void *w, void *y, const float *in_scale,
                       const float *in_shift, const float *out_scale, const float *out_shift, const void *residual,
                       mhe_stat_t *stats, const void *x2, const float *x2_scale, const float *x2_shift, void *a_out, void *stream,
-                      const void *mask, const BnRev *bn, float *y32, const int *scatter, const void *xcat, int cin2, const void *mask_bits) {
+                      const void *mask, const BnRev *bn, float *y32, const int *scatter, const void *xcat, int cin2, const void *mask_bits,
+                      int a_quarter) {
     MHE_REQUIRE(d && x && w && (y || y32), "mhe_conv2d_nhwc: null pointer");
     MHE_REQUIRE(d->dtype == MHE_F32 || d->dtype == MHE_BF16, "mhe_conv2d_nhwc: dtype=%d", d->dtype);
     const int ce = elem_chunk(d->dtype), bke = 8 * ce;
@@ -782,6 +818,12 @@ static int conv_entry(const mhe_conv_desc *d, const void *x, const void *w, void
                     "mhe_conv2d_f32out_nhwc: bf16 operands, optional out_shift only");
         p.y32 = y32;
         if (p.force < 0 || p.force > 4) p.force = p.Cout <= 64 ? 0 : 1;
+    }
+    if (a_quarter) {      // the compact operand output exists in the transfer-wave tail kernel only: no other variant may see the smaller tensor
+        p.a_quarter = 1;
+        MHE_REQUIRE(d->dtype == MHE_BF16 && conv::choose_tile(p, d->Cin % bke == 0, true) == 10,
+                    "mhe_conv1x1_residual_in_quarter_nhwc: geometry not taken by the residual-tail kernel (variant 10; Cin=%d Cout=%d M=%lld)", d->Cin, d->Cout, M);
+        return conv::launch_tail(p, (hipStream_t)stream);
     }
     if (d->dtype == MHE_F32) return conv::launch_conv<float>(p, (hipStream_t)stream);
     return conv::launch_conv<u16>(p, (hipStream_t)stream);
@@ -845,6 +887,28 @@ extern "C" int mhe_bottleneck_tail_bits_nhwc(const mhe_conv_desc *d, int Cb, con
     MHE_REQUIRE(M > 0 && M < (1ll << 31), "mhe_bottleneck_tail_nhwc: bad pixel count");
     p.M = (int)M;
     MHE_REQUIRE(conv::fuse_supports(p, Cb), "mhe_bottleneck_tail_nhwc: needs Cin = 4 Cb, Cb 64 / 128, Cout 64 / 128, pixels %% 128 == 0 (Cin=%d Cb=%d Cout=%d M=%lld)",
+                d->Cin, Cb, d->Cout, M);
+    return conv::launch_fuse(p, Cb, (hipStream_t)stream);
+}
+
+extern "C" int mhe_bottleneck_tail_quarter_nhwc(const mhe_conv_desc *d, int Cb, const void *y2, const float *bn2_scale, const float *bn2_shift,
+                                                const void *w3, const float *bn3_scale, const float *bn3_shift, const void *identity,
+                                                const float *id_scale, const float *id_shift, const void *w1, void *a_quarter, void *y1,
+                                                mhe_stat_t *stats, void *stream) {
+    MHE_REQUIRE(d && y2 && bn2_scale && bn2_shift && w3 && bn3_scale && bn3_shift && identity && w1 && a_quarter && y1, "mhe_bottleneck_tail_quarter_nhwc: null pointer");
+    MHE_REQUIRE(d->dtype == MHE_BF16, "mhe_bottleneck_tail_quarter_nhwc: bf16 storage only");
+    MHE_REQUIRE((id_scale == nullptr) == (id_shift == nullptr), "mhe_bottleneck_tail_quarter_nhwc: id_scale/id_shift must come together");
+    MHE_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0, "mhe_bottleneck_tail_quarter_nhwc: bad geometry");
+    conv::Params p{};
+    p.x = y2; p.in_scale = bn2_scale; p.in_shift = bn2_shift; p.w3 = w3; p.mid_scale = bn3_scale; p.mid_shift = bn3_shift;
+    p.x2 = identity; p.x2_scale = id_scale; p.x2_shift = id_shift; p.w = w1; p.a_out = a_quarter; p.y = y1; p.stats = stats;
+    p.a_quarter = 1;
+    p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
+    p.Ho = d->H; p.Wo = d->W; p.Kpad = d->Cin; p.relu_in = 1; p.force = -1;
+    const long long M = (long long)d->B * d->H * d->W;
+    MHE_REQUIRE(M > 0 && M * d->Cin < (1ll << 31), "mhe_bottleneck_tail_quarter_nhwc: bad pixel count");
+    p.M = (int)M;
+    MHE_REQUIRE(conv::fuse_supports(p, Cb), "mhe_bottleneck_tail_quarter_nhwc: needs Cin = 4 Cb, Cb 64 / 128, Cout 64 / 128, pixels %% 128 == 0 (Cin=%d Cb=%d Cout=%d M=%lld)",
                 d->Cin, Cb, d->Cout, M);
     return conv::launch_fuse(p, Cb, (hipStream_t)stream);
 }
@@ -932,6 +996,21 @@ extern "C" int mhe_bn_finalize_step(mhe_stat_t *stats, const float *gamma, const
                        beta, running_mean, running_var, scale, shift, mean_invstd, C, count, momentum, eps, clear_stats,
                        num_batches_tracked);
     return check_launch("bn_finalize_kernel");
+}
+
+extern "C" int mhe_bn_finalize_pair_step(mhe_stat_t *stats0, const float *gamma0, const float *beta0, float *running_mean0, float *running_var0,
+                                         float *scale0, float *shift0, float *mean_invstd0, int C0, double count0, long long *num_batches_tracked0,
+                                         mhe_stat_t *stats1, const float *gamma1, const float *beta1, float *running_mean1, float *running_var1,
+                                         float *scale1, float *shift1, float *mean_invstd1, int C1, double count1, long long *num_batches_tracked1,
+                                         float momentum, float eps, int clear_stats, void *stream) {
+    MHE_REQUIRE(stats0 && gamma0 && beta0 && scale0 && shift0 && C0 > 0 && count0 > 1.f && stats1 && gamma1 && beta1 && scale1 && shift1 && C1 > 0 && count1 > 1.f,
+                "mhe_bn_finalize_pair_step: bad arguments");
+    MHE_REQUIRE(stats0 != stats1 && scale0 != scale1 && shift0 != shift1, "mhe_bn_finalize_pair_step: the two units must not share buffers");
+    const conv::BnUnit u0 = {stats0, gamma0, beta0, running_mean0, running_var0, scale0, shift0, mean_invstd0, num_batches_tracked0, count0, C0};
+    const conv::BnUnit u1 = {stats1, gamma1, beta1, running_mean1, running_var1, scale1, shift1, mean_invstd1, num_batches_tracked1, count1, C1};
+    const int nb0 = (C0 + 3) / 4, nb1 = (C1 + 3) / 4;
+    hipLaunchKernelGGL(conv::bn_finalize_pair_kernel, dim3((unsigned)(nb0 + nb1)), dim3(256), 0, (hipStream_t)stream, u0, u1, nb0, momentum, eps, clear_stats);
+    return check_launch("bn_finalize_pair_kernel");
 }
 
 static inline int ew_blocks(size_t n) { size_t b = (n + 255) / 256; return (int)(b < 4096 ? (b ? b : 1) : 4096); }

@@ -50,8 +50,10 @@ __device__ __forceinline__ void bst(__amdgpu_buffer_rsrc_t r, unsigned toff, uns
 }
 }
 
-template <int CB, int N2>
-__global__ __launch_bounds__(512) void bottleneck_tail_kernel(const Params p) {
+// AQ: the block output goes out for the pixels on even rows and even columns only, into a compact [B, ceil(H/2), ceil(W/2), C] tensor -
+// all that a stride-2 1x1 shortcut reads of it (the stage entries of the forward-only path); conv1 is fed the whole tile as before
+template <int CB, int N2, bool AQ>
+__device__ __forceinline__ void bottleneck_tail_body(const Params &p) {
     using T = u16;
     constexpr int C = 4 * CB, NT = C / 64, KT1 = CB / 64;
     constexpr int R3S = KT1 * 64 * 8, R1S = N2 * 8;                  // uint4 per W3 / W1 ring stage
@@ -75,7 +77,8 @@ __global__ __launch_bounds__(512) void bottleneck_tail_kernel(const Params p) {
     __syncthreads();                                           // the tables are read by the transfer role before its first top barrier
     const __amdgpu_buffer_rsrc_t y2g = rsrc_of(p.x, (size_t)p.M * CB * 2), idg = rsrc_of(p.x2, (size_t)p.M * C * 2);
     const __amdgpu_buffer_rsrc_t w3g = rsrc_of(p.w3, (size_t)C * CB * 2), w1g = rsrc_of(p.w, (size_t)N2 * C * 2);
-    const __amdgpu_buffer_rsrc_t ag = rsrc_of(p.a_out, (size_t)p.M * C * 2), yg = rsrc_of(p.y, (size_t)p.M * N2 * 2);
+    const __amdgpu_buffer_rsrc_t ag = rsrc_of(p.a_out, AQ ? (size_t)p.B * ((p.H + 1) >> 1) * ((p.W + 1) >> 1) * C * 2 : (size_t)p.M * C * 2);
+    const __amdgpu_buffer_rsrc_t yg = rsrc_of(p.y, (size_t)p.M * N2 * 2);
     const __amdgpu_buffer_rsrc_t abg = rsrc_of(p.a_bits, (size_t)p.M * (C / 8));
     // output epilogue (the four transfer waves; the multiply waves go on to the next tile's top barrier): staged 128 x N2 tile -> 16-byte
     // stores + per-thread partial statistics of the stored values
@@ -193,6 +196,8 @@ __global__ __launch_bounds__(512) void bottleneck_tail_kernel(const Params p) {
         IdSet id0, id1;                                        // identity chunks of ticks t (set t & 1), loaded two ticks ahead
         uint4 a2r[KT1 * 4];
         u32x4 w3r[KT1 * 2], w1r[N2 / 32];
+        unsigned aqoff[4] = {0u, 0u, 0u, 0u};                  // AQ: byte offset of this thread's chunk of row rbase + 32 j in the compact tensor ...
+        bool aqkeep[4] = {false, false, false, false};         // ... and whether that row is written at all; per tile, fixed over its channel slots
         auto load_id = [&](int m0, int t, IdSet &st) __attribute__((always_inline)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) st.v[j] = bld(idg, toffC, (unsigned)(m0 + 32 * j) * (C * 2) + t * 128);
@@ -254,6 +259,10 @@ __global__ __launch_bounds__(512) void bottleneck_tail_kernel(const Params p) {
                 }
                 const uint4 o = Chunk<T>::pack(v);
                 As[swz(row, s8)] = o;
+                if constexpr (AQ) {
+                    if (aqkeep[j]) bst(ag, aqoff[j], (unsigned)(t * 128), o);
+                    continue;
+                }
                 bst(ag, toffC, (unsigned)(m0 + 32 * j) * (C * 2) + t * 128, o);
                 // the gate of the reverse pass, one bit per stored value (bf16: sign clear and not zero)
                 const unsigned wds[4] = {o.x, o.y, o.z, o.w};
@@ -298,6 +307,15 @@ __global__ __launch_bounds__(512) void bottleneck_tail_kernel(const Params p) {
             const int Ln = L + (int)gridDim.x;
             const bool more = Ln < ntiles;
             const int m0n = more ? Ln * FPIX : m0;             // (clamped: the loads of a tile that does not exist are harmless re-reads)
+            if constexpr (AQ) {
+                const int Hq = (p.H + 1) >> 1, Wq = (p.W + 1) >> 1;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int m = m0 + rbase + 32 * j, ox = m % p.W, r = m / p.W, oy = r % p.H, b = r / p.H;
+                    aqkeep[j] = ((ox | oy) & 1) == 0;
+                    aqoff[j] = ((unsigned)((b * Hq + (oy >> 1)) * Wq + (ox >> 1)) * (unsigned)C + s8 * 8) * 2u;
+                }
+            }
             stage_a2();
             store_w3(0);
             load_w3(1);
@@ -342,7 +360,15 @@ __global__ __launch_bounds__(512) void bottleneck_tail_kernel(const Params p) {
     }
 }
 
+template <int CB, int N2>
+__global__ __launch_bounds__(512) void bottleneck_tail_kernel(const Params p) { bottleneck_tail_body<CB, N2, false>(p); }
+template <int CB, int N2>
+__global__ __launch_bounds__(512) void bottleneck_tail_quarter_kernel(const Params p) { bottleneck_tail_body<CB, N2, true>(p); }
+
 bool fuse_supports(const Params &p, int cb) {
+    // (a_quarter: forward form only - no gate bits - and the map's geometry must be the launch's own; the compact tensor's byte
+    // offsets are 32-bit like the full tensor's, which M < 2^31 / Cin bounds already)
+    if (p.a_quarter && (p.a_bits || p.H <= 0 || p.W <= 0 || (long long)p.B * p.H * p.W != (long long)p.M)) return false;
     return p.x && p.x2 && p.w && p.w3 && p.y && p.a_out && p.in_scale && p.in_shift && p.mid_scale && p.mid_shift &&
            (cb == 64 || cb == 128) && p.Cin == 4 * cb && (p.Cout == 64 || p.Cout == 128) && p.Kpad == p.Cin &&
            p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.M % FPIX == 0 && p.M > 0;
@@ -351,6 +377,13 @@ bool fuse_supports(const Params &p, int cb) {
 int launch_fuse(const Params &p, int cb, hipStream_t s) {
     const int ntiles = p.M / FPIX;
     const dim3 grid((unsigned)(ntiles < 256 ? ntiles : 256)), block(512);
+    if (p.a_quarter) {
+        if (cb == 64 && p.Cout == 64) hipLaunchKernelGGL((bottleneck_tail_quarter_kernel<64, 64>), grid, block, 0, s, p);
+        else if (cb == 64 && p.Cout == 128) hipLaunchKernelGGL((bottleneck_tail_quarter_kernel<64, 128>), grid, block, 0, s, p);
+        else if (cb == 128 && p.Cout == 64) hipLaunchKernelGGL((bottleneck_tail_quarter_kernel<128, 64>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((bottleneck_tail_quarter_kernel<128, 128>), grid, block, 0, s, p);
+        return check_launch("bottleneck_tail_quarter_kernel");
+    }
     if (cb == 64 && p.Cout == 64) hipLaunchKernelGGL((bottleneck_tail_kernel<64, 64>), grid, block, 0, s, p);
     else if (cb == 64 && p.Cout == 128) hipLaunchKernelGGL((bottleneck_tail_kernel<64, 128>), grid, block, 0, s, p);
     else if (cb == 128 && p.Cout == 64) hipLaunchKernelGGL((bottleneck_tail_kernel<128, 64>), grid, block, 0, s, p);

@@ -39,6 +39,9 @@ struct Params {
     // conv_halo.hip, data-gradient form with the BatchNorm reverse of the convolution's own output gradient on the operand load:
     // operand = k2 x + k1 x2 + k0 per channel (rev_coef = k2 | k1 | k0, [3][Cin]; x2 = the raw output that BatchNorm normalised), written to a_out
     const float *rev_coef;
+    // stage-entry tails of the forward-only path (conv_fuse.hip, conv_tail.hip forward form): a_out is the COMPACT tensor
+    // [B, ceil(H/2), ceil(W/2), Cin] and receives the operand at even rows and even columns only - what a stride-2 1x1 shortcut reads
+    int a_quarter;
 };
 
 // tile row -> global output pixel index the epilogue addresses (or -1 outside the problem)

@@ -26,8 +26,11 @@ constexpr int T_A = TBM * 8, T_W = TBN * 8, T_STAGE = T_A + T_W;        // uint4
 
 // DG: data-gradient form - the operand is gy = k2 g + k1 y + k0 (the BatchNorm reverse of the convolution's own output gradient, written out
 // once for the weight gradient); the outputs are ReLU-gated by p.mask (+ residual) and feed the BatchNorm-reverse sums of up to two consumers
-template <bool DG>
-__global__ __launch_bounds__(512) void conv_tail_kernel(const Params p) {
+// AQ (forward form): a_out is the compact [B, ceil(H/2), ceil(W/2), Cin] tensor and receives the operand's pixels on even rows and even
+// columns only (Params::a_quarter) - the stage entries, where a stride-2 1x1 shortcut is the one reader left
+template <bool DG, bool AQ>
+__device__ __forceinline__ void conv_tail_body(const Params &p) {
+    static_assert(!(DG && AQ), "the compact operand output belongs to the forward form");
     using T = u16;
     __shared__ uint4 lds[2 * T_STAGE];                                   // 96 KiB; the epilogue's 64 KiB staging buffer lies over it
     __shared__ float aff[4 * TMAXK];                                      // scale | shift of x, scale | shift of x2 (1 | 0 without its affine)   32 KiB
@@ -56,6 +59,7 @@ __global__ __launch_bounds__(512) void conv_tail_kernel(const Params p) {
     // lasted one memory latency, 4.6 us for 64 KiB per CU: the first version ran 148 us against the tiled kernel's 119; three sets spill)
     struct Set { uint4 a[4], b[4], w[8]; };
     Set st0, st1;
+    int aqrow[4] = {-1, -1, -1, -1};                                      // AQ: row of the compact tensor that tile row rbase + 32 j goes to, -1 = not written; per pixel tile
     auto load_tile = [&](int t, Set &st, int m0, int n0) __attribute__((always_inline)) {
         const int kc = t * TBK + s * 8;
 #pragma unroll
@@ -95,7 +99,11 @@ __global__ __launch_bounds__(512) void conv_tail_kernel(const Params p) {
             }
             const uint4 o = Chunk<T>::pack(v);
             At[swz(rbase + 32 * j, s)] = o;
-            if (ag) *reinterpret_cast<uint4 *>(ag + (size_t)(m0 + rbase + 32 * j) * K + kc) = o;
+            if constexpr (AQ) {
+                if (ag && aqrow[j] >= 0) *reinterpret_cast<uint4 *>(ag + (size_t)aqrow[j] * K + kc) = o;
+            } else {
+                if (ag) *reinterpret_cast<uint4 *>(ag + (size_t)(m0 + rbase + 32 * j) * K + kc) = o;
+            }
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) Wt[swz(rbase + 32 * j, s)] = st.w[j];
@@ -259,6 +267,14 @@ __global__ __launch_bounds__(512) void conv_tail_kernel(const Params p) {
             tile_at(L, mt, ntile);
             const int m0 = mt * TBM, n0 = ntile * TBN;
             T *ag = p.a_out && ntile == 0 ? reinterpret_cast<T *>(p.a_out) : nullptr;
+            if constexpr (AQ) {
+                const int Hq = (p.Ho + 1) >> 1, Wq = (p.Wo + 1) >> 1;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int m = m0 + rbase + 32 * j, ox = m % p.Wo, r = m / p.Wo, oy = r % p.Ho, b = r / p.Ho;
+                    aqrow[j] = ((ox | oy) & 1) == 0 ? (b * Hq + (oy >> 1)) * Wq + (ox >> 1) : -1;
+                }
+            }
             __syncthreads();
             // K tile u lives in set u & 1; tiles 0 and 1 are in flight (loaded during the previous pixel tile's epilogue)
             store_tile(0, st0, m0, ag);
@@ -297,8 +313,13 @@ __global__ __launch_bounds__(512) void conv_tail_kernel(const Params p) {
 }
 
 
+template <bool DG>
+__global__ __launch_bounds__(512) void conv_tail_kernel(const Params p) { conv_tail_body<DG, false>(p); }
+__global__ __launch_bounds__(512) void conv_tail_quarter_kernel(const Params p) { conv_tail_body<false, true>(p); }
+
 bool tail_supports(const Params &p) {
     if (p.mask ? (p.stats != nullptr) : (p.residual != nullptr)) return false;      // data-gradient form: gate (+ residual) + BatchNorm-reverse sums, no statistics
+    if (p.a_quarter && (p.mask || !p.a_out || (long long)p.B * p.Ho * p.Wo != (long long)p.M)) return false;      // forward form only
     return p.x2 && p.in_scale && !p.out_scale && !p.out_shift && !p.relu_out && !p.y32 && !p.os2 && !p.res_s2 &&
            p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.Kpad == p.Cin && p.Cin % TBK == 0 && p.Cin >= 2 * TBK && p.Cin <= TMAXK &&
            p.Cout % TBN == 0 && p.M % TBM == 0;
@@ -308,6 +329,7 @@ int launch_tail(const Params &p, hipStream_t s) {
     const int ntiles = (p.M / TBM) * (p.Cout / TBN);
     const dim3 grid((unsigned)(ntiles < 256 ? ntiles : 256));
     if (p.mask) hipLaunchKernelGGL(conv_tail_kernel<true>, grid, dim3(512), 0, s, p);
+    else if (p.a_quarter) hipLaunchKernelGGL(conv_tail_quarter_kernel, grid, dim3(512), 0, s, p);
     else hipLaunchKernelGGL(conv_tail_kernel<false>, grid, dim3(512), 0, s, p);
     return check_launch("conv_tail_kernel");
 }

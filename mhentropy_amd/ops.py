@@ -755,9 +755,10 @@ def bottleneck_tail_supported(B, H, W, Cb, Cout):
     return bool(_lib.lib().mhe_bottleneck_tail_supported(C.byref(d), int(Cb)))
 
 
-def bottleneck_tail(y2, bn2, w3, bn3, identity, id_aff, w1, stats=None, want_bits=False):
+def bottleneck_tail(y2, bn2, w3, bn3, identity, id_aff, w1, stats=None, want_bits=False, quarter=False, a_out=None):
     """(a, y1) of mhe_bottleneck_tail_nhwc: a = relu(bn3(conv3(relu(bn2(y2)))) + identity) with conv3 re-evaluated in place of being read
-    back, y1 = the next block's conv1 of a (+ its batch statistics).  bn2 / bn3 / id_aff = (scale, shift) pairs (id_aff may be None)."""
+    back, y1 = the next block's conv1 of a (+ its batch statistics).  bn2 / bn3 / id_aff = (scale, shift) pairs (id_aff may be None).
+    quarter: a is the compact [B, ceil(H/2), ceil(W/2), C] tensor a[:, ::2, ::2] (mhe_bottleneck_tail_quarter_nhwc); a_out: where a goes."""
     B, H, W, Cb = y2.shape
     Cw, Cout = w3.shape[0], w1.shape[0]
     _chk(y2, torch.bfloat16, "tail.y2"); _chk(w3, torch.bfloat16, "tail.w3", (Cw, Cb)); _chk(w1, torch.bfloat16, "tail.w1", (Cout, Cw))
@@ -766,7 +767,11 @@ def bottleneck_tail(y2, bn2, w3, bn3, identity, id_aff, w1, stats=None, want_bit
         _chk(sc, torch.float32, f"tail.{n}_scale", (c,)); _chk(sh, torch.float32, f"tail.{n}_shift", (c,))
     if stats is not None:
         _chk_stats(stats, "tail.stats", Cout)
-    a = torch.empty(B, H, W, Cw, device=y2.device, dtype=torch.bfloat16)
+    a_shape = (B, (H + 1) // 2, (W + 1) // 2, Cw) if quarter else (B, H, W, Cw)
+    if quarter and want_bits:
+        raise _lib.MheError("tail: the compact block output has no gate bits (forward-only path)")
+    a = a_out if a_out is not None else torch.empty(a_shape, device=y2.device, dtype=torch.bfloat16)
+    _chk(a, torch.bfloat16, "tail.a_out", a_shape)
     y1 = torch.empty(B, H, W, Cout, device=y2.device, dtype=torch.bfloat16)
     # want_bits: also [a > 0] as bits, byte [pixel][channel / 8] - the gate the reverse pass reads instead of `a` (conv2d_nhwc mask_bits=)
     bits = torch.empty(B, H, W, Cw // 8, device=y2.device, dtype=torch.uint8) if want_bits else None
@@ -774,13 +779,17 @@ def bottleneck_tail(y2, bn2, w3, bn3, identity, id_aff, w1, stats=None, want_bit
     if TIMING:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    check(_lib.lib().mhe_bottleneck_tail_bits_nhwc(C.byref(d), Cb, _ptr(y2), _ptr(bn2[0]), _ptr(bn2[1]), _ptr(w3), _ptr(bn3[0]), _ptr(bn3[1]), _ptr(identity),
-                                                   _ptr(id_aff[0] if id_aff is not None else None), _ptr(id_aff[1] if id_aff is not None else None),
-                                                   _ptr(w1), _ptr(a), _ptr(bits), _ptr(y1), _ptr(stats), _stream()), "mhe_bottleneck_tail_bits_nhwc")
+    ida = (_ptr(id_aff[0] if id_aff is not None else None), _ptr(id_aff[1] if id_aff is not None else None))
+    if quarter:
+        check(_lib.lib().mhe_bottleneck_tail_quarter_nhwc(C.byref(d), Cb, _ptr(y2), _ptr(bn2[0]), _ptr(bn2[1]), _ptr(w3), _ptr(bn3[0]), _ptr(bn3[1]), _ptr(identity),
+                                                          *ida, _ptr(w1), _ptr(a), _ptr(y1), _ptr(stats), _stream()), "mhe_bottleneck_tail_quarter_nhwc")
+    else:
+        check(_lib.lib().mhe_bottleneck_tail_bits_nhwc(C.byref(d), Cb, _ptr(y2), _ptr(bn2[0]), _ptr(bn2[1]), _ptr(w3), _ptr(bn3[0]), _ptr(bn3[1]), _ptr(identity),
+                                                       *ida, _ptr(w1), _ptr(a), _ptr(bits), _ptr(y1), _ptr(stats), _stream()), "mhe_bottleneck_tail_bits_nhwc")
     if TIMING:
         ev1.record()
         nbytes = 2 * (y2.numel() + identity.numel() + a.numel() + y1.numel() + w3.numel() + w1.numel())
-        KERNEL_TIMES.append(("mhe::conv::bottleneck_tail_kernel<%d, %d>" % (Cb, Cout), 2.0 * B * H * W * Cw * (Cb + Cout), ev0, ev1, nbytes))
+        KERNEL_TIMES.append(("mhe::conv::bottleneck_tail%s_kernel<%d, %d>" % ("_quarter" if quarter else "", Cb, Cout), 2.0 * B * H * W * Cw * (Cb + Cout), ev0, ev1, nbytes))
     return (a, y1, bits) if want_bits else (a, y1)
 
 
@@ -823,8 +832,10 @@ def conv3x3s2_dgrad(gy, w4, residual=None, mask=None, bn=None, tile=0):
     return dx
 
 
-def conv1x1_residual_in(x, x2, w, in_scale, in_shift, x2_scale=None, x2_shift=None, a_out=None, stats=None, tile=0):
-    """y = conv1x1(relu(x*in_scale+in_shift + (x2*x2_scale+x2_shift | x2))); optionally writes that operand to a_out."""
+def conv1x1_residual_in(x, x2, w, in_scale, in_shift, x2_scale=None, x2_shift=None, a_out=None, stats=None, tile=0, quarter=False):
+    """y = conv1x1(relu(x*in_scale+in_shift + (x2*x2_scale+x2_shift | x2))); optionally writes that operand to a_out.
+    quarter: a_out is the compact [B, ceil(H/2), ceil(W/2), Cin] tensor and receives operand[:, ::2, ::2] only
+    (mhe_conv1x1_residual_in_quarter_nhwc: the residual-tail kernel, conv_tile_choice(..., mode=2) == 10, or an error)."""
     B, H, W, Cin = x.shape
     Cout = w.shape[0]
     dt = x.dtype
@@ -832,8 +843,10 @@ def conv1x1_residual_in(x, x2, w, in_scale, in_shift, x2_scale=None, x2_shift=No
     _chk(in_scale, torch.float32, "conv_res.in_scale", (Cin,)); _chk(in_shift, torch.float32, "conv_res.in_shift", (Cin,))
     if x2_scale is not None:
         _chk(x2_scale, torch.float32, "conv_res.x2_scale", (Cin,)); _chk(x2_shift, torch.float32, "conv_res.x2_shift", (Cin,))
+    if quarter and (a_out is None or tile):
+        raise _lib.MheError("conv_res: quarter needs a_out and the launcher's own kernel choice")
     if a_out is not None:
-        _chk(a_out, dt, "conv_res.a_out", x.shape)
+        _chk(a_out, dt, "conv_res.a_out", (B, (H + 1) // 2, (W + 1) // 2, Cin) if quarter else x.shape)
     if stats is not None:
         _chk_stats(stats, "conv_res.stats", Cout)
     y = torch.empty(B, H, W, Cout, device=x.device, dtype=dt)
@@ -841,14 +854,14 @@ def conv1x1_residual_in(x, x2, w, in_scale, in_shift, x2_scale=None, x2_shift=No
     if TIMING:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    check(_lib.lib().mhe_conv1x1_residual_in_nhwc(C.byref(d), _ptr(x), _ptr(x2), _ptr(w), _ptr(y), _ptr(in_scale), _ptr(in_shift),
-                                                  _ptr(x2_scale), _ptr(x2_shift), _ptr(a_out), _ptr(stats), _stream()),
-          "mhe_conv1x1_residual_in_nhwc")
+    entry = "mhe_conv1x1_residual_in_quarter_nhwc" if quarter else "mhe_conv1x1_residual_in_nhwc"
+    check(getattr(_lib.lib(), entry)(C.byref(d), _ptr(x), _ptr(x2), _ptr(w), _ptr(y), _ptr(in_scale), _ptr(in_shift),
+                                     _ptr(x2_scale), _ptr(x2_shift), _ptr(a_out), _ptr(stats), _stream()), entry)
     if TIMING:
         ev1.record()
         es = x.element_size()
         nbytes = es * (2 * x.numel() + y.numel() + w.numel() + (a_out.numel() if a_out is not None else 0))
-        name = _conv_kernel_name(d, dt, 2)
+        name = "mhe::conv::conv_tail_quarter_kernel" if quarter else _conv_kernel_name(d, dt, 2)
         KERNEL_TIMES.append((name, 2.0 * B * H * W * Cout * Cin, ev0, ev1, nbytes))
     return y
 
@@ -942,6 +955,23 @@ def bn_finalize(stats, gamma, beta, running_mean, running_var, count, momentum=0
                                          _ptr(scale), _ptr(shift), _ptr(mi), Cn, float(count), float(momentum), float(eps), _stream()),
               "mhe_bn_finalize")
     return (scale, shift, mi) if want_mean_invstd else (scale, shift)
+
+
+def bn_finalize_pair(unit0, unit1, momentum=0.1, eps=1e-5, clear=True):
+    """two independent BatchNorm units finalized in ONE launch (mhe_bn_finalize_pair_step), each bit for bit as bn_finalize(clear=...) would.
+    unit = (stats, gamma, beta, running_mean, running_var, count, num_batches_tracked | None) -> ((scale0, shift0), (scale1, shift1))"""
+    args, outs = [], []
+    for k, (stats, gamma, beta, rmean, rvar, count, nbt) in enumerate((unit0, unit1)):
+        Cn = gamma.shape[0]
+        _chk_stats(stats, f"bn_finalize_pair.stats{k}", Cn)
+        if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
+            raise _lib.MheError("bn_finalize_pair.num_batches_tracked: int64 device tensor expected")
+        scale = torch.empty(Cn, device=gamma.device, dtype=torch.float32)
+        shift = torch.empty_like(scale)
+        outs.append((scale, shift))
+        args += [_ptr(stats), _ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar), _ptr(scale), _ptr(shift), None, Cn, float(count), _ptr(nbt)]
+    check(_lib.lib().mhe_bn_finalize_pair_step(*args, float(momentum), float(eps), int(clear), _stream()), "mhe_bn_finalize_pair_step")
+    return outs[0], outs[1]
 
 
 def bn_act(x, scale, shift, res=None, res_scale=None, res_shift=None, relu=True, out=None):

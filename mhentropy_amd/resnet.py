@@ -112,6 +112,10 @@ class ResNetTrunk(nn.Module):
         self.stem_pool_fused = os.environ.get("MHE_STEM_POOL", "1") == "1"
         # the last block's relu(bn(y) + identity) evaluated inside the global average pool (csrc/conv.hip: bn_act_avgpool_kernel)
         self.fuse_pool = os.environ.get("MHE_FUSE_POOL", "1") == "1"
+        # stage entries (layer1->2, 2->3, 3->4) of the forward-only path: the fused tail writes the block output at even rows and even
+        # columns only, compact - its one reader left is the stride-2 1x1 shortcut, which then runs at stride 1 on the compact tensor - and
+        # a downsample block's bn3 and shortcut BatchNorm are finalized by one launch instead of two
+        self.stage_entry = os.environ.get("MHE_STAGE_ENTRY", "1") == "1"
 
     # -- packed-weight cache keyed on the parameter's version counter
     def _w(self, conv, cin_pad=None, stem=False):
@@ -150,6 +154,22 @@ class ResNetTrunk(nn.Module):
 
     def _conv_bn(self, x, conv, bn, stats_pool, in_aff=None, stride=1, pad=0, k=1, cin_pad=None, apply=None):
         """raw conv output + this layer's BatchNorm folded to (scale, shift)."""
+        y, st = self._conv_raw(x, conv, stats_pool, in_aff, stride, pad, k, cin_pad, apply)
+        return y, self._bn_affine(y, bn, st)
+
+    def _bn_unit(self, bn, st, count):
+        return (st, bn.weight, bn.bias, bn.running_mean, bn.running_var, count, bn.num_batches_tracked)
+
+    def _quarter_entry(self, blk, dt):
+        """blk's only use of its input besides conv1 is a stride-2 1x1 shortcut: the tail kernel that feeds conv1 may write a[:, ::2, ::2] alone
+        (conv1 is fed inside that kernel, the 3x3 reads conv1's output)"""
+        if not (self.stage_entry and self.training and dt == torch.bfloat16 and blk.kind == "bottleneck" and blk.downsample is not None):
+            return False
+        c = blk.downsample[0]
+        return c.kernel_size == (1, 1) and c.stride == (2, 2) and c.padding == (0, 0)
+
+    def _conv_raw(self, x, conv, stats_pool, in_aff=None, stride=1, pad=0, k=1, cin_pad=None, apply=None):
+        """raw conv output + its statistics slice (still to be finalized)"""
         w = self._w(conv, cin_pad)
         if in_aff is not None and (apply or self.bn_apply) == "pass":
             x = ops.bn_act(x, in_aff[0], in_aff[1], relu=True, out=x)
@@ -157,7 +177,7 @@ class ResNetTrunk(nn.Module):
         isc, ish = in_aff if in_aff is not None else (None, None)
         st = stats_pool.take(conv.out_channels) if self.training else None
         y = ops.conv2d_nhwc(x, w, k, k, stride, pad, in_scale=isc, in_shift=ish, relu_in=in_aff is not None, stats=st)
-        return y, self._bn_affine(y, bn, st)
+        return y, st
 
     def forward(self, x):
         """x (B,3,H,W) float32 NCHW -> (B, feat_dim) float32."""
@@ -178,23 +198,29 @@ class ResNetTrunk(nn.Module):
             a = ops.maxpool3x3s2(y, aff[0], aff[1])
         pending = None          # (raw conv3 output, bn3 affine, identity tensor, identity affine | None): an unevaluated block tail
         for bi, blk in enumerate(blocks):
+            a_quarter = False       # `a` is the compact a[:, ::2, ::2] of this block's input (stage entries, see _quarter_entry)
             if blk.kind == "bottleneck":
                 if pending is not None and isinstance(pending[0], str):
                     # ... with the previous block's conv3 evaluated again inside the same kernel (its raw output was never written)
                     _, y2_p, a2_p, w3_p, al_p, idt_p, idaff_p = pending
                     st = pool.take(blk.conv1.out_channels) if self.training else None
-                    a, y1 = ops.bottleneck_tail(y2_p, a2_p, w3_p, al_p, idt_p, idaff_p, self._w(blk.conv1), stats=st)
+                    a_quarter = self._quarter_entry(blk, y2_p.dtype)
+                    a, y1 = ops.bottleneck_tail(y2_p, a2_p, w3_p, al_p, idt_p, idaff_p, self._w(blk.conv1), stats=st, quarter=a_quarter)
                     a1 = self._bn_affine(y1, blk.bn1, st)
                     pending = None
                 elif pending is not None:
                     # the previous block's relu(bn3(y3) + identity) is evaluated inside this conv1's operand load,
                     # which also writes it out once as this block's identity
                     yl_p, al_p, idt_p, idaff_p = pending
-                    a = torch.empty_like(yl_p)
+                    Bp, Hp, Wp, Cp = yl_p.shape
+                    # (the compact output exists in the residual-tail kernel only)
+                    a_quarter = self._quarter_entry(blk, yl_p.dtype) and ops.conv_tile_choice(
+                        Bp, Hp, Wp, Cp, blk.conv1.out_channels, 1, 1, 0, yl_p.dtype, 2) == 10
+                    a = torch.empty((Bp, (Hp + 1) // 2, (Wp + 1) // 2, Cp), device=yl_p.device, dtype=yl_p.dtype) if a_quarter else torch.empty_like(yl_p)
                     st = pool.take(blk.conv1.out_channels) if self.training else None
                     y1 = ops.conv1x1_residual_in(yl_p, idt_p, self._w(blk.conv1), al_p[0], al_p[1],
                                                  None if idaff_p is None else idaff_p[0],
-                                                 None if idaff_p is None else idaff_p[1], a_out=a, stats=st)
+                                                 None if idaff_p is None else idaff_p[1], a_out=a, stats=st, quarter=a_quarter)
                     a1 = self._bn_affine(y1, blk.bn1, st)
                     pending = None
                 else:
@@ -221,6 +247,11 @@ class ResNetTrunk(nn.Module):
                 recompute = (self.fuse_recompute and self.fuse_tail and nxt is not None and nxt.kind == "bottleneck" and y2.dtype == torch.bfloat16
                              and nxt.conv1.kernel_size == (1, 1) and nxt.conv1.stride == (1, 1)
                              and ops.bottleneck_tail_supported(y2.shape[0], y2.shape[1], y2.shape[2], y2.shape[3], nxt.conv1.out_channels))
+                # a downsample block's bn3 and shortcut BatchNorm: both sets of statistics are complete before either affine is needed ->
+                # one finalize launch for the two (not where bn3 comes out of the Gram finalize)
+                pair3 = None
+                merge = (self.stage_entry and self.training and blk.downsample is not None
+                         and not (recompute and self.recompute_stats == "gram"))
                 if recompute:
                     w3 = self._w(blk.conv3)
                     st3 = None
@@ -232,15 +263,27 @@ class ResNetTrunk(nn.Module):
                         if self.training:    # bn3's batch statistics from the products as they would be stored - nothing is stored
                             st3 = pool.take(blk.conv3.out_channels)
                             ops.conv1x1_stats(y2, w3, a2[0], a2[1], st3)
-                        yl, al = None, self._bn_affine(None, blk.bn3, st3, count=y2.numel() // y2.shape[-1])
+                        if merge:
+                            yl, al, pair3 = None, None, self._bn_unit(blk.bn3, st3, y2.numel() // y2.shape[-1])
+                        else:
+                            yl, al = None, self._bn_affine(None, blk.bn3, st3, count=y2.numel() // y2.shape[-1])
+                elif merge:
+                    yl, st3 = self._conv_raw(y2, blk.conv3, pool, a2, apply=ap3)
+                    al, pair3 = None, self._bn_unit(blk.bn3, st3, yl.numel() // yl.shape[-1])
                 else:
                     yl, al = self._conv_bn(y2, blk.conv3, blk.bn3, pool, a2, apply=ap3)
             else:
-                recompute = False
+                recompute, pair3 = False, None
                 y1, a1 = self._conv_bn(a, blk.conv1, blk.bn1, pool, None, blk.stride, 1, 3)
                 yl, al = self._conv_bn(y1, blk.conv2, blk.bn2, pool, a1, 1, 1, 3)
             if blk.downsample is not None:
-                idt, idaff = self._conv_bn(a, blk.downsample[0], blk.downsample[1], pool, a_aff, blk.stride, 0, 1, apply="load")
+                # (on the compact tensor the stride-2 1x1 shortcut is a stride-1 one: same weights, same products, same statistics)
+                ds_stride = 1 if a_quarter else blk.stride
+                if pair3 is not None:
+                    idt, std = self._conv_raw(a, blk.downsample[0], pool, a_aff, ds_stride, 0, 1, apply="load")
+                    al, idaff = ops.bn_finalize_pair(pair3, self._bn_unit(blk.downsample[1], std, idt.numel() // idt.shape[-1]), BN_MOMENTUM, BN_EPS)
+                else:
+                    idt, idaff = self._conv_bn(a, blk.downsample[0], blk.downsample[1], pool, a_aff, ds_stride, 0, 1, apply="load")
                 a_aff = None        # (only the first block sees the un-normalised pooled stem output)
             else:
                 idt, idaff = a, None

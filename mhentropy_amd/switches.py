@@ -28,6 +28,7 @@ SWITCHES = {
     "MHE_RECOMPUTE_STATS": ("gram", "resnet.py", "stream: bn3 statistics from the statistics-only launch instead of the Gram matrix"),
     "MHE_STEM_POOL": ("1", "resnet.py", "0: stem convolution and max pool as two kernels"),
     "MHE_FUSE_POOL": ("1", "resnet.py", "0: last block tail and average pool as two launches"),
+    "MHE_STAGE_ENTRY": ("1", "resnet.py", "0: stage-entry tails write the whole block output, the stride-2 shortcut reads it, bn3 / shortcut finalized by two launches"),
     "MHE_GRAM_WGS_64": ("512", "csrc/conv_gram.hip", "workgroups of the 64-channel Gram launch"),
     "MHE_GRAM_WGS_128": ("256", "csrc/conv_gram.hip", "workgroups of the 128-channel Gram launch"),
     # ---- flow / MANO
