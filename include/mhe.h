@@ -504,7 +504,8 @@ int mhe_sum_over_hypotheses_f32(const float *rows, float *out, int N, int B, int
 int mhe_conv_wgrad_nhwc(const mhe_conv_desc *d, const void *x, const void *gy, float *dw, int ldw, void *stream);
 /* The same with a workspace of >= mhe_conv_wgrad_workspace_floats(d) floats: every pixel-range slice stores its partial tile
  * into the workspace with plain coalesced stores and a reducer launch adds the slabs to dW (dW += as above; nothing needs
- * zeroing in the workspace).  Falls back to the atomic form when the workspace is NULL or too small. */
+ * zeroing in the workspace).  workspace == NULL: the atomic form above.  A workspace that is too small for a launch that takes
+ * slabs is an error (MHE_ERR_ARG, dW untouched, nothing launched): never a silent fall-back to order-dependent sums. */
 size_t mhe_conv_wgrad_workspace_floats(const mhe_conv_desc *d);
 int mhe_conv_wgrad_ws_nhwc(const mhe_conv_desc *d, const void *x, const void *gy, float *dw, int ldw, float *workspace,
                            size_t workspace_floats, void *stream);
