@@ -58,7 +58,7 @@ def rot6d_to_rotmat(poses6, robust=False):
     p = poses6.reshape(-1, 6)
     ops._chk(p, torch.float32, "rot6d.poses")
     out = torch.empty(p.shape[0], 3, 3, device=p.device, dtype=torch.float32)
-    ops.check(_lib.lib().mhe_rot6d_to_rotmat_f32(ops._ptr(p), ops._ptr(out), p.shape[0], int(robust), ops._stream()), "mhe_rot6d_to_rotmat_f32")
+    ops.launch("mhe_rot6d_to_rotmat_f32", p, out, p.shape[0], int(robust))
     return out.view(*poses6.shape[:-1], 3, 3)
 
 
@@ -74,7 +74,7 @@ def rot6d_to_rotmat_bwd(poses6, g_rotmats):
     p, g = poses6.reshape(-1, 6), g_rotmats.reshape(-1, 9)
     ops._chk(p, torch.float32, "rot6d.poses"); ops._chk(g, torch.float32, "rot6d.g", (p.shape[0], 9))
     out = torch.empty_like(p)
-    ops.check(_lib.lib().mhe_rot6d_to_rotmat_bwd_f32(ops._ptr(p), ops._ptr(g), ops._ptr(out), p.shape[0], ops._stream()), "mhe_rot6d_to_rotmat_bwd_f32")
+    ops.launch("mhe_rot6d_to_rotmat_bwd_f32", p, g, out, p.shape[0])
     return out.view(poses6.shape)
 
 
@@ -117,8 +117,7 @@ class BodyLayer(nn.Module):
         if getattr(self, "_split_key", None) != key:
             L = _lib.lib()
             sp = torch.empty(L.mhe_lbs_split_floats(self.J, self.nb, self.VP), device=dev, dtype=torch.float32)
-            ops.check(L.mhe_lbs_split_tables_f32(ops._ptr(self._vt), ops._ptr(self._vsd), ops._ptr(self._vpd), ops._ptr(self._vw), ops._ptr(sp),
-                                                 self.J, self.nb, self.VP, ops._stream()), "mhe_lbs_split_tables_f32")
+            ops.launch("mhe_lbs_split_tables_f32", self._vt, self._vsd, self._vpd, self._vw, sp, self.J, self.nb, self.VP)
             self._split, self._split_key = sp, key
         return self._split
 
@@ -129,8 +128,7 @@ class BodyLayer(nn.Module):
         if getattr(self, "_kp_key", None) != key:
             L = _lib.lib()
             sp = torch.empty(L.mhe_lbs_kp_split_floats(self.NK, self.VP), device=dev, dtype=torch.float32)
-            ops.check(L.mhe_lbs_kp_split_tables_f32(ops._ptr(self.keypoint_regressor), ops._ptr(sp), self.NK, self.NV, self.VP, ops._stream()),
-                      "mhe_lbs_kp_split_tables_f32")
+            ops.launch("mhe_lbs_kp_split_tables_f32", self.keypoint_regressor, sp, self.NK, self.NV, self.VP)
             self._kp_sp, self._kp_key = sp, key
         return self._kp_sp
 
@@ -141,8 +139,7 @@ class BodyLayer(nn.Module):
         if getattr(self, "_bwd_key", None) != key:
             L = _lib.lib()
             tb = torch.empty(L.mhe_lbs_bwd_tables_floats(self.J, self.nb, self.VP), device=dev, dtype=torch.float32)
-            ops.check(L.mhe_lbs_bwd_tables_f32(ops._ptr(self._vsd), ops._ptr(self._vpd), ops._ptr(self._vw), ops._ptr(tb), self.J, self.nb, self.NV,
-                                               self.VP, ops._stream()), "mhe_lbs_bwd_tables_f32")
+            ops.launch("mhe_lbs_bwd_tables_f32", self._vsd, self._vpd, self._vw, tb, self.J, self.nb, self.NV, self.VP)
             self._bwd_tab, self._bwd_key = tb, key
         return self._bwd_tab
 
@@ -159,20 +156,17 @@ class BodyLayer(nn.Module):
         L, dev = _lib.lib(), rotmats.device
         ws = torch.empty(L.mhe_lbs_workspace_floats(R, self.J, self.nb), device=dev, dtype=torch.float32)
         joints = torch.empty(R, self.J, 3, device=dev, dtype=torch.float32)
-        ops.check(L.mhe_lbs_pose_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(self._jt), ops._ptr(self._jsd), ops._ptr(self.parents), ops._ptr(ws),
-                                     ops._ptr(joints), R, self.J, self.nb, ops._stream()), "mhe_lbs_pose_f32")
+        ops.launch("mhe_lbs_pose_f32", rotmats, betas, self._jt, self._jsd, self.parents, ws, joints, R, self.J, self.nb)
         out = {"joints": joints, "rotmats": rotmats}
         if want_keypoints:
             verts = torch.empty(R, self.NV, 3, device=dev, dtype=torch.float32) if want_verts else None
             kp = torch.empty(R, self.NK, 3, device=dev, dtype=torch.float32)
             if os.environ.get("MHE_LBS_MFMA", "1") == "1" and L.mhe_lbs_skin_kp_supported(R, self.J, self.nb, self.NV, self.VP, self.NK, int(want_verts)):
-                ops.check(L.mhe_lbs_skin_kp_mfma_f32(ops._ptr(ws), ops._ptr(self._split_tables(dev)), ops._ptr(self._kp_split(dev)), ops._ptr(verts),
-                                                     ops._ptr(kp), R, self.J, self.nb, self.NV, self.VP, self.NK, float(scale), ops._stream()),
-                          "mhe_lbs_skin_kp_mfma_f32")
+                ops.launch("mhe_lbs_skin_kp_mfma_f32", ws, self._split_tables(dev), self._kp_split(dev), verts, kp, R, self.J, self.nb, self.NV, self.VP, self.NK,
+                           float(scale))
             else:
-                ops.check(L.mhe_lbs_skin_kp_f32(ops._ptr(ws), ops._ptr(self._vt), ops._ptr(self._vsd), ops._ptr(self._vpd), ops._ptr(self._vw),
-                                                ops._ptr(self.keypoint_regressor), ops._ptr(verts), ops._ptr(kp), R, self.J, self.nb, self.NV, self.VP,
-                                                self.NK, float(scale), ops._stream()), "mhe_lbs_skin_kp_f32")
+                ops.launch("mhe_lbs_skin_kp_f32", ws, self._vt, self._vsd, self._vpd, self._vw, self.keypoint_regressor, verts, kp, R, self.J, self.nb, self.NV,
+                           self.VP, self.NK, float(scale))
             out["keypoints"] = kp
             if want_verts:
                 out["vertices"] = verts
@@ -181,12 +175,10 @@ class BodyLayer(nn.Module):
             verts = torch.empty(R, self.NV, 3, device=dev, dtype=torch.float32)
             if os.environ.get("MHE_LBS_MFMA", "1") == "1" and self.VP % 32 == 0 and L.mhe_lbs_skin_mfma_supported(R, self.J, self.nb, self.NV, self.VP):
                 # both products on the matrix cores from bf16 pieces of the f32 operands (csrc/lbs_skin.hip); the table pieces are made once
-                ops.check(L.mhe_lbs_skin_mfma_f32(ops._ptr(ws), ops._ptr(self._split_tables(dev)), ops._ptr(verts), R, self.J, self.nb, self.NV, self.VP,
-                                                  float(scale), ops._stream()), "mhe_lbs_skin_mfma_f32")
+                ops.launch("mhe_lbs_skin_mfma_f32", ws, self._split_tables(dev), verts, R, self.J, self.nb, self.NV, self.VP, float(scale))
                 out["vertices"] = verts
                 return out
-            ops.check(L.mhe_lbs_skin_f32(ops._ptr(ws), ops._ptr(self._vt), ops._ptr(self._vsd), ops._ptr(self._vpd), ops._ptr(self._vw), ops._ptr(verts),
-                                         R, self.J, self.nb, self.NV, self.VP, float(scale), ops._stream()), "mhe_lbs_skin_f32")
+            ops.launch("mhe_lbs_skin_f32", ws, self._vt, self._vsd, self._vpd, self._vw, verts, R, self.J, self.nb, self.NV, self.VP, float(scale))
             out["vertices"] = verts
         return out
 
@@ -218,16 +210,14 @@ class BodyLayer(nn.Module):
                 ops._chk(center, torch.float32, "body.center", (R, 3))
             L, dev = _lib.lib(), rotmats.device
             ws = torch.empty(L.mhe_lbs_workspace_floats(R, self.J, self.nb), device=dev, dtype=torch.float32)
-            ops.check(L.mhe_lbs_pose_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(self._jt), ops._ptr(self._jsd), ops._ptr(self.parents), ops._ptr(ws),
-                                         None, R, self.J, self.nb, ops._stream()), "mhe_lbs_pose_f32")
+            ops.launch("mhe_lbs_pose_f32", rotmats, betas, self._jt, self._jsd, self.parents, ws, None, R, self.J, self.nb)
             err = torch.empty(R, device=dev, dtype=torch.float32)
             if os.environ.get("MHE_LBS_MFMA", "1") == "1" and L.mhe_lbs_skin_err_supported(R, self.J, self.nb, self.NV, self.VP, B):
-                ops.check(L.mhe_lbs_skin_err_mfma_f32(ops._ptr(ws), ops._ptr(self._split_tables(dev)), ops._ptr(target_verts), ops._ptr(center), ops._ptr(err),
-                                                      R, B, self.J, self.nb, self.NV, self.VP, float(scale), ops._stream()), "mhe_lbs_skin_err_mfma_f32")
+                ops.launch("mhe_lbs_skin_err_mfma_f32", ws, self._split_tables(dev), target_verts, center, err, R, B, self.J, self.nb, self.NV, self.VP,
+                           float(scale))
             else:
-                ops.check(L.mhe_lbs_skin_err_f32(ops._ptr(ws), ops._ptr(self._vt), ops._ptr(self._vsd), ops._ptr(self._vpd), ops._ptr(self._vw),
-                                                 ops._ptr(target_verts), ops._ptr(center), ops._ptr(err), R, B, self.J, self.nb, self.NV, self.VP,
-                                                 float(scale), ops._stream()), "mhe_lbs_skin_err_f32")
+                ops.launch("mhe_lbs_skin_err_f32", ws, self._vt, self._vsd, self._vpd, self._vw, target_verts, center, err, R, B, self.J, self.nb, self.NV, self.VP,
+                           float(scale))
         return err
 
 
@@ -260,7 +250,7 @@ def _check_ns(ns, K, who):
 def _point_errors_launch(points, target, mask):
     B, K, P = points.shape[:3]
     err = torch.empty(B, K, device=points.device, dtype=torch.float32)
-    ops.check(_lib.lib().mhe_point_errors_f32(ops._ptr(points), ops._ptr(target), ops._ptr(err), B, K, P, mask, ops._stream()), "mhe_point_errors_f32")
+    ops.launch("mhe_point_errors_f32", points, target, err, B, K, P, mask)
     return err
 
 
@@ -304,8 +294,7 @@ def min_of_n(err, ns):
         val = torch.empty(B, len(ns), device=err.device, dtype=torch.float32)
         idx = torch.empty(B, len(ns), device=err.device, dtype=torch.int32)
         arr = (C.c_int * len(ns))(*ns)
-        ops.check(_lib.lib().mhe_min_of_n_f32(ops._ptr(err), ops._ptr(val), ops._ptr(idx), B, K, C.cast(arr, C.c_void_p), len(ns), ops._stream()),
-                  "mhe_min_of_n_f32")
+        ops.launch("mhe_min_of_n_f32", err, val, idx, B, K, C.cast(arr, C.c_void_p), len(ns))
     return val, idx
 
 
@@ -436,8 +425,7 @@ def lbs_pose_bwd(layer, rotmats, betas, g_joints):
     ops._chk(rotmats, torch.float32, "lbs_bwd.rotmats", (R, layer.J, 3, 3)); ops._chk(betas, torch.float32, "lbs_bwd.betas", (R, layer.nb))
     ops._chk(g_joints, torch.float32, "lbs_bwd.g_joints", (R, layer.J, 3))
     g_rot, g_bt = torch.empty_like(rotmats), torch.empty_like(betas)
-    ops.check(_lib.lib().mhe_lbs_pose_bwd_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(layer._jt), ops._ptr(layer._jsd), ops._ptr(layer.parents),
-                                              ops._ptr(g_joints), ops._ptr(g_rot), ops._ptr(g_bt), R, layer.J, layer.nb, ops._stream()), "mhe_lbs_pose_bwd_f32")
+    ops.launch("mhe_lbs_pose_bwd_f32", rotmats, betas, layer._jt, layer._jsd, layer.parents, g_joints, g_rot, g_bt, R, layer.J, layer.nb)
     return g_rot, g_bt
 
 
@@ -466,21 +454,18 @@ def lbs_bwd(layer, rotmats, betas, g_verts, g_joints=None, scale=1.0, g_keypoint
         ops._chk(g_joints, torch.float32, "lbs_bwd.g_joints", (R, J, 3))
     L, dev = _lib.lib(), rotmats.device
     ws = torch.empty(L.mhe_lbs_workspace_floats(R, J, nb), device=dev, dtype=torch.float32)
-    ops.check(L.mhe_lbs_pose_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(layer._jt), ops._ptr(layer._jsd), ops._ptr(layer.parents), ops._ptr(ws),
-                                 None, R, J, nb, ops._stream()), "mhe_lbs_pose_f32")
+    ops.launch("mhe_lbs_pose_f32", rotmats, betas, layer._jt, layer._jsd, layer.parents, ws, None, R, J, nb)
     g_tf = torch.empty(R, J, 12, device=dev, dtype=torch.float32)
     g_pm = torch.empty(R, 9 * (J - 1), device=dev, dtype=torch.float32)
     g_bt = torch.empty_like(betas)
     wstride = ws.numel() // R
 
     def skin_bwd(gv, lo, n):          # rows lo .. lo + n - 1 (row slices of contiguous tensors are contiguous)
-        ops.check(L.mhe_lbs_skin_bwd_f32(ops._ptr(ws[lo * wstride:]), ops._ptr(layer._vt), ops._ptr(layer._vsd), ops._ptr(layer._vpd), ops._ptr(layer._vw),
-                                         ops._ptr(layer._bwd_tables(dev)), ops._ptr(gv), ops._ptr(g_tf[lo:]), ops._ptr(g_pm[lo:]), ops._ptr(g_bt[lo:]), n,
-                                         J, nb, layer.NV, layer.VP, float(scale), ops._stream()), "mhe_lbs_skin_bwd_f32")
+        ops.launch("mhe_lbs_skin_bwd_f32", ws[lo * wstride:], layer._vt, layer._vsd, layer._vpd, layer._vw, layer._bwd_tables(dev), gv, g_tf[lo:], g_pm[lo:],
+                   g_bt[lo:], n, J, nb, layer.NV, layer.VP, float(scale))
 
     def kp_bwd(gv, lo, n, accumulate):
-        ops.check(L.mhe_lbs_keypoints_bwd_f32(ops._ptr(layer.keypoint_regressor), ops._ptr(g_keypoints[lo:]), ops._ptr(gv), n, layer.NK, layer.NV,
-                                              int(accumulate), ops._stream()), "mhe_lbs_keypoints_bwd_f32")
+        ops.launch("mhe_lbs_keypoints_bwd_f32", layer.keypoint_regressor, g_keypoints[lo:], gv, n, layer.NK, layer.NV, int(accumulate))
 
     if g_keypoints is None:
         skin_bwd(g_verts, 0, R)
@@ -496,9 +481,7 @@ def lbs_bwd(layer, rotmats, betas, g_verts, g_joints=None, scale=1.0, g_keypoint
             kp_bwd(gv, lo, n, False)
             skin_bwd(gv, lo, n)
     g_rot = torch.empty_like(rotmats)
-    ops.check(L.mhe_lbs_transforms_bwd_f32(ops._ptr(rotmats), ops._ptr(betas), ops._ptr(layer._jt), ops._ptr(layer._jsd), ops._ptr(layer.parents),
-                                           ops._ptr(g_joints), ops._ptr(g_tf), ops._ptr(g_pm), ops._ptr(g_bt), ops._ptr(g_rot), ops._ptr(g_bt), R, J, nb,
-                                           ops._stream()), "mhe_lbs_transforms_bwd_f32")
+    ops.launch("mhe_lbs_transforms_bwd_f32", rotmats, betas, layer._jt, layer._jsd, layer.parents, g_joints, g_tf, g_pm, g_bt, g_rot, g_bt, R, J, nb)
     return g_rot, g_bt
 
 
@@ -529,7 +512,7 @@ def _flow_backward(g, tp, g_x, g_logq):
     R, cs, dev = B * tp["row_div"], ctab.shape[1], ctab.device
     gv = torch.zeros(R, Dp, device=dev)
     if g_x is not None:
-        ops.check(_lib.lib().mhe_pad64_f32(ops._ptr(g_x), ops._ptr(gv), R, D, ops._stream()), "mhe_pad64_f32")
+        ops.launch("mhe_pad64_f32", g_x, gv, R, D)
     if g_logq is not None:
         ops._chk(g_logq, torch.float32, "glow.g_log_prob", (R,))
     Gct = torch.zeros(B, cs, device=dev)
@@ -611,8 +594,7 @@ class _KpLogProbFn(torch.autograd.Function):
     def forward(ctx, keypoints, cam, uv, vis, b):
         B, K, NK = keypoints.shape[:3]
         log_p = torch.empty(B, K, device=keypoints.device, dtype=torch.float32)
-        ops.check(_lib.lib().mhe_kp_log_prob_f32(ops._ptr(keypoints), ops._ptr(cam), ops._ptr(uv), ops._ptr(vis), ops._ptr(log_p), B, K, NK,
-                                                 int(cam.dim() == 3), b, ops._stream()), "mhe_kp_log_prob_f32")
+        ops.launch("mhe_kp_log_prob_f32", keypoints, cam, uv, vis, log_p, B, K, NK, int(cam.dim() == 3), b)
         ctx.save_for_backward(keypoints, cam, uv, vis)
         ctx.b = b
         return log_p
@@ -623,8 +605,7 @@ class _KpLogProbFn(torch.autograd.Function):
         B, K, NK = keypoints.shape[:3]
         g = g.float().contiguous()
         g_kp, g_cam = torch.empty_like(keypoints), torch.empty_like(cam)
-        ops.check(_lib.lib().mhe_kp_log_prob_bwd_f32(ops._ptr(keypoints), ops._ptr(cam), ops._ptr(uv), ops._ptr(vis), ops._ptr(g), ops._ptr(g_kp),
-                                                     ops._ptr(g_cam), B, K, NK, int(cam.dim() == 3), ctx.b, ops._stream()), "mhe_kp_log_prob_bwd_f32")
+        ops.launch("mhe_kp_log_prob_bwd_f32", keypoints, cam, uv, vis, g, g_kp, g_cam, B, K, NK, int(cam.dim() == 3), ctx.b)
         return g_kp, g_cam, None, None, None
 
 

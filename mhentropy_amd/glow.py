@@ -23,7 +23,6 @@ step and by body.BodyFlowHead) and the density direction (pose -> noise; `log_pr
 `_reverse_density`, the maximum-likelihood loss of the reference's README.md:32-34).  The residual net's reverse (`_net_reverse`) is one piece
 of code for the two.
 """
-import ctypes as C
 import math
 import os
 
@@ -32,7 +31,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import ops, _lib
+from . import ops
 
 
 def _colsum(rows, B, N, out):
@@ -232,11 +231,10 @@ class ConditionalGlow(nn.Module):
     def _net(self, d, v, ctab, slot, R, row_div, n_img, bf16, bufs, rec):
         """coupling parameters [R,Pp] of layer `d` from the (padded) variable v whose identity columns are current.  bufs (h, t, t2): reused
         in place, h as the residual stream; with a tape record `rec` every stage writes a fresh tensor instead, kept in rec"""
-        L, H = _lib.lib(), self.hidden
-        s, cs = ops._stream, ctab.shape[1]
+        H, cs = self.hidden, ctab.shape[1]
         fresh = rec is not None
         h = ops.linear(v, d["wx"], out=None if fresh else bufs[0])
-        ops.check(L.mhe_glow_add_image_rows_f32(ops._ptr(h), C.c_void_p(ctab[:, slot * H:].data_ptr()), cs, R, H, row_div, n_img, s()), "mhe_glow_add_image_rows_f32")
+        ops.launch("mhe_glow_add_image_rows_f32", h, ctab[:, slot * H:], cs, R, H, row_div, n_img)
         if fresh:
             rec.update(hs=[h], t2=[], t3=[], drop=[])
         elif bf16:
@@ -246,7 +244,7 @@ class ConditionalGlow(nn.Module):
         for b, (w0, b0, w1, b1) in enumerate(d["blocks"]):
             if fresh:
                 t = torch.empty(R, 1, 1, H, device=v.device, dtype=torch.bfloat16) if bf16 else torch.empty(R, H, device=v.device)
-            ops.check(L.mhe_relu_copy_f32(ops._ptr(h), ops._ptr(t), h.numel(), ops.dtype_code(t.dtype), s()), "mhe_relu_copy_f32")
+            ops.launch("mhe_relu_copy_f32", h, t, h.numel(), ops.dtype_code(t.dtype))
             if bf16:        # relu(h) -> bf16, two h x h products on bf16 MFMA (bias + relu in the kernel's epilogue), gate in f32
                 w0b, w1b = d["blocks_bf16"][b]
                 t2 = ops.conv2d_nhwc(t, w0b, 1, 1, 1, 0, out_shift=b0, relu_out=True, out=None if fresh else t2)
@@ -259,8 +257,7 @@ class ConditionalGlow(nn.Module):
             if fresh:
                 h = h.clone()
                 rec["hs"].append(h); rec["t2"].append(t2); rec["t3"].append(t3); rec["drop"].append(drop)
-            ops.check(L.mhe_glow_glu_residual_f32(ops._ptr(h), ops._ptr(t3), ops.dtype_code(t3.dtype), C.c_void_p(ctab[:, (slot + 1 + b) * H:].data_ptr()), cs, R, H,
-                                                  row_div, n_img, s()), "mhe_glow_glu_residual_f32")
+            ops.launch("mhe_glow_glu_residual_f32", h, t3, ops.dtype_code(t3.dtype), ctab[:, (slot + 1 + b) * H:], cs, R, H, row_div, n_img)
         return ops.linear(h, d["wf"], d["bf"])
 
     def _run(self, v_in, context, inverse, row_div, n_img, pk=None, tape=None, bf16=None):
@@ -273,11 +270,10 @@ class ConditionalGlow(nn.Module):
         in the density direction also u, the layer's affine input (v = A u + c)"""
         ops._chk(v_in, torch.float32, "glow.in"); ops._chk(context, torch.float32, "glow.context", (context.shape[0], self.context_features))
         pk = self._packed() if pk is None else pk
-        L, D, H = _lib.lib(), self.features, self.hidden
+        D, H = self.features, self.hidden
         bf16 = self.compute_dtype == torch.bfloat16 if bf16 is None else bf16
         R = v_in.shape[0]
         dev = v_in.device
-        s = ops._stream
         ctab = ops.linear(context, pk["wctx"], pk["bctx"])                       # every context-only term, once per image
         N = R // n_img
         if (tape is None and inverse and bf16 and pk.get("fused") is not None and row_div in (1, N)
@@ -287,7 +283,7 @@ class ConditionalGlow(nn.Module):
             rn, rb = (n_img, 1) if row_div == 1 else (1, N)
             return ops.glow_layers(v_in, ctab, pk["fused"], pk["aff"], self._drop_bits(R), self.p_drop, N, n_img, D, rn, rb)
         v = torch.empty(R, self.Dp, device=dev)
-        ops.check(L.mhe_pad64_f32(ops._ptr(v_in), ops._ptr(v), R, D, s()), "mhe_pad64_f32")
+        ops.launch("mhe_pad64_f32", v_in, v, R, D)
         z_in = v
         logdet = torch.zeros(R, device=dev)
         bufs = None if tape is not None else tuple(torch.empty(R, H, device=dev) for _ in range(3))
@@ -302,8 +298,7 @@ class ConditionalGlow(nn.Module):
             rec = None if tape is None else {"v": v} if inverse else {"v": v, "u": u}
             prm = self._net(d, v, ctab, l * per, R, row_div, n_img, bf16, bufs, rec)
             y = torch.empty(R, self.Dp, device=dev)
-            ops.check(L.mhe_glow_coupling_f32(ops._ptr(v), ops._ptr(prm), ops._ptr(y), ops._ptr(logdet), R, D, d["first"], d["T"], int(inverse), s()),
-                      "mhe_glow_coupling_f32")
+            ops.launch("mhe_glow_coupling_f32", v, prm, y, logdet, R, D, d["first"], d["T"], int(inverse))
             if rec is not None:
                 rec.update(prm=prm, y=y)
                 tape["layers"][l] = rec
@@ -330,9 +325,9 @@ class ConditionalGlow(nn.Module):
         """the reverse of one layer's residual net over its tape record `t`, shared by both directions: gprm (R, Pp) = dL/d(coupling parameters) ->
         final layer; per block (last first) gate, second product, dropout, ReLU, first product, ReLU of the residual stream; initial layer's
         weight gradient and the per-image sums into Gct.  Returns gh = dL/dh_0 (R, H); the caller adds gh Wx to the variable's gradient."""
-        L_, H = _lib.lib(), self.hidden
+        H = self.hidden
         R, cs = gprm.shape[0], ctab.shape[1]
-        s, dev = ops._stream, gprm.device
+        dev = gprm.device
         ops.linear_wgrad(t["hs"][-1], gprm, o["dwf"]); flow_colsum(gprm, o["dbf"])
         gh = ops.linear(gprm, o["wfT"])
         for b in range(self.num_blocks - 1, -1, -1):
@@ -340,8 +335,8 @@ class ConditionalGlow(nn.Module):
             t2, t3, hb = t["t2"][b], t["t3"][b], t["hs"][b]
             bf16 = t3.dtype == torch.bfloat16
             gt3, ggate = torch.empty_like(t3), torch.empty(R, H, device=dev)
-            ops.check(L_.mhe_glow_glu_bwd_f32(ops._ptr(gh), ops._ptr(t3), C.c_void_p(ctab[:, (slot + 1 + b) * H:].data_ptr()), cs,
-                                              ops._ptr(gt3), ops._ptr(ggate), R, H, row_div, B, ops.dtype_code(t3.dtype), s()), "mhe_glow_glu_bwd_f32")
+            ops.launch("mhe_glow_glu_bwd_f32", gh, t3, ctab[:, (slot + 1 + b) * H:], cs, gt3, ggate, R, H, row_div, B,
+                       ops.dtype_code(t3.dtype))
             img_sum(ggate, Gct[:, (slot + 1 + b) * H:])
             # the four h x h products of the block's reverse pass: on bf16 MFMA over a bf16 tape (bias sums of the bf16 gradients)
             wgrad = (lambda x, gy_, dw: ops.conv_wgrad(x, gy_, 1, 1, 1, 0, dw)) if bf16 else ops.linear_wgrad
@@ -355,10 +350,10 @@ class ConditionalGlow(nn.Module):
             else:
                 ops.flow_lrelu_bwd(gt2, t2, slope=0.0)
             tt = torch.empty_like(t2)
-            ops.check(L_.mhe_relu_copy_f32(ops._ptr(hb), ops._ptr(tt), tt.numel(), ops.dtype_code(tt.dtype), s()), "mhe_relu_copy_f32")
+            ops.launch("mhe_relu_copy_f32", hb, tt, tt.numel(), ops.dtype_code(tt.dtype))
             wgrad(tt, gt2, dw0); ops.colsum(gt2, db0)
             gt = dgrad(gt2, w0T)
-            ops.check(L_.mhe_relu_bwd_add_f32(ops._ptr(gh), ops._ptr(gt), ops._ptr(hb), gh.numel(), ops.dtype_code(gt.dtype), s()), "mhe_relu_bwd_add_f32")
+            ops.launch("mhe_relu_bwd_add_f32", gh, gt, hb, gh.numel(), ops.dtype_code(gt.dtype))
         ops.linear_wgrad(t["v"], gh, o["dwx"])
         img_sum(gh, Gct[:, slot * H:])
         return gh
@@ -376,10 +371,10 @@ class ConditionalGlow(nn.Module):
           batch-major: g_logp per row (mhe_glow_coupling_inv_bwd_wide_f32); per-image sums mhe_sum_row_blocks_f32; column sums of
             the flow-width rows (gv, g_prm) per image then over images (_colsum), of the hidden-width rows ops.colsum.
         bf16 tapes (t2, t3 as [R, 1, 1, H] bfloat16) take the block's four products on bf16 MFMA."""
-        L_, D, H = _lib.lib(), self.features, self.hidden
+        D, H = self.features, self.hidden
         ctab, row_div, B, sample_major = tape["ctab"], tape["row_div"], tape["n_img"], tape["sample_major"]
         R, N = gv.shape[0], gv.shape[0] // B
-        s, dev = ops._stream, gv.device
+        dev = gv.device
         img_sum, flow_colsum = self._reducers(tape, R)
         per = 1 + self.num_blocks
         for l, (t, d, o) in enumerate(zip(tape["layers"], tape["pk"]["layers"], layers)):
@@ -388,8 +383,7 @@ class ConditionalGlow(nn.Module):
             gy = ops.linear(gv, o["AinvT"])
             if sample_major:
                 gvc, gprm = torch.empty(R, 64, device=dev), torch.empty(R, 64, device=dev)
-                ops.check(L_.mhe_glow_coupling_inv_bwd_f32(ops._ptr(t["v"]), ops._ptr(t["prm"]), ops._ptr(gy), ops._ptr(g_logp), -1.0 / N,
-                                                           ops._ptr(gvc), ops._ptr(gprm), R, B, D, d["first"], d["T"], s()), "mhe_glow_coupling_inv_bwd_f32")
+                ops.launch("mhe_glow_coupling_inv_bwd_f32", t["v"], t["prm"], gy, g_logp, -1.0 / N, gvc, gprm, R, B, D, d["first"], d["T"])
             else:
                 gvc, gprm = ops.glow_coupling_inv_bwd_wide(t["v"], t["prm"], gy, g_logp, D, d["first"], d["T"])
             gh = self._net_reverse(t, o, ctab, slot, gprm, Gct, row_div, B, img_sum, flow_colsum)

@@ -79,18 +79,14 @@ class HO3DBatchPipeline:
              "uvd": f(B, 63)}
         obj_all = f(B, nv, 3)
         geom = torch.empty(B, L.mhe_ho3d_geom_doubles(), device=dev, dtype=torch.float64)
-        p = ops._ptr
-        ops.check(L.mhe_ho3d_targets(p(raw["joints3d"]), p(raw["mesh"]), p(raw["cam"]), p(raw["obj_rot"]), p(raw["obj_trans"]), p(raw["obj_verts"]),
-                                     p(raw["obj_count"]), nv, p(raw["seg"]), p(raw["depth_png"]), p(aug), p(t["crop_uv"]), p(t["vis"]),
-                                     p(t["original_pose3d"]), p(t["verts"]), p(t["pose3d"]), p(t["st"]), p(t["scale"]), p(t["crop_center"]),
-                                     p(t["crop_size"]), p(t["pose3d_root"]), p(t["rot_mat_inv"]), p(t["_rot_mat"]), p(t["uvd"]), p(obj_all), p(geom),
-                                     B, ops._stream()), "mhe_ho3d_targets")
+        ops.launch("mhe_ho3d_targets", raw["joints3d"], raw["mesh"], raw["cam"], raw["obj_rot"], raw["obj_trans"], raw["obj_verts"], raw["obj_count"], nv,
+                   raw["seg"], raw["depth_png"], aug, t["crop_uv"], t["vis"], t["original_pose3d"], t["verts"], t["pose3d"], t["st"], t["scale"], t["crop_center"],
+                   t["crop_size"], t["pose3d_root"], t["rot_mat_inv"], t["_rot_mat"], t["uvd"], obj_all, geom, B)
         image = f(B, 3, 256, 256)
         hm = torch.empty(B, 256, 256, device=dev, dtype=torch.uint8)
         om = torch.empty_like(hm)
         depth = f(B, 256, 256)
-        ops.check(L.mhe_ho3d_images(p(img), p(raw["seg"]), p(raw["depth_png"]), p(geom), p(aug), p(image), p(hm), p(om), p(depth), B, ops._stream()),
-                  "mhe_ho3d_images")
+        ops.launch("mhe_ho3d_images", img, raw["seg"], raw["depth_png"], geom, aug, image, hm, om, depth, B)
         t.update(hand_mask=hm.bool(), object_mask=om.bool(), depth=depth, _root_idx=12, patch=torch.zeros(B, 3, device=dev),
                  hand_side=torch.zeros(B, device=dev), bone_length=t["scale"], camera=raw["cam"], dataset=["ho3d"] * B)
         t["object_verts"] = (obj_all if object_idx is None else

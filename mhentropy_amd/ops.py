@@ -43,6 +43,72 @@ def _chk(t, dtype, name, shape=None):
     return t
 
 
+def launch(entry, *args):
+    """one kernel launch through the C ABI: tensors go as their device address (None as null; ints, floats, byref and explicit c_void_p
+    sub-addresses as they are), the current stream is appended, the status is checked under the entry's own name.  A tensor that is not on
+    the GPU is refused here: its host address must never reach a kernel."""
+    conv = []
+    for i, a in enumerate(args):
+        if a is None or isinstance(a, torch.Tensor):
+            if a is not None and not a.is_cuda:
+                raise _lib.MheError(f"{entry}: argument {i} is a {a.device.type} tensor, every tensor operand must be device memory (the hot path has no CPU fallback)")
+            a = _ptr(a)
+        conv.append(a)
+    check(getattr(_lib.lib(), entry)(*conv, _stream()), entry)
+
+
+class _Timed:
+    """HIP events on the launch stream around the launches of its body, appended to KERNEL_TIMES while TIMING is on (bench.py's live roofline
+    pass).  what() -> (kernel name, algorithmic flops, algorithmic HBM bytes), evaluated only then; what=None: never timed"""
+    def __init__(self, what):
+        self.what = what if TIMING else None
+
+    def __enter__(self):
+        if self.what is not None:
+            self.rec = self.what()
+            self.ev0, self.ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.ev0.record()
+        return self
+
+    def __exit__(self, exc_type, *exc):
+        if self.what is not None and exc_type is None:
+            self.ev1.record()
+            name, flops, nbytes = self.rec
+            KERNEL_TIMES.append((name, flops, self.ev0, self.ev1, nbytes))
+        return False
+
+
+def _bn_consumers(bn, n, dt, shape, Cn, prefix, only_one=None):
+    """bn: up to n (raw output y, mean_invstd [2, Cn], stats) triples of the BatchNorm units whose reverse sums a data-gradient epilogue
+    accumulates.  Checks every triple given and returns the flat operand list [y, mean_invstd, stats] * n with None for the units that are
+    absent; only_one: the ValueError of a form that takes a single consumer"""
+    bn = list(bn or [])
+    if only_one and len(bn) > 1:
+        raise ValueError(only_one)
+    flat = []
+    for by, bmi, bst in (bn + [(None, None, None)] * n)[:n]:
+        if by is not None:
+            _chk(by, dt, prefix + ".bn_y", shape); _chk(bmi, torch.float32, prefix + ".bn_mean_invstd", (2, Cn))
+            _chk_stats(bst, prefix + ".bn_stats", Cn)
+        flat += [by, bmi, bst]
+    return flat
+
+
+def _grow_only_workspace():
+    """get(device, need): one f32 workspace per device, grown to the largest request.  A superseded buffer stays referenced for the life of
+    the process: a captured HIP graph (train.GraphedStep) may have baked its address in"""
+    live, retired = {}, []
+
+    def get(device, need):
+        ws = live.get(device)
+        if ws is None or ws.numel() < need:
+            if ws is not None:
+                retired.append(ws)
+            ws = live[device] = torch.empty(need, device=device, dtype=torch.float32)
+        return ws
+    return get
+
+
 def stat_shards():
     return _lib.lib().mhe_conv_stat_shards()
 
@@ -128,11 +194,11 @@ def linear(x, w, bias=None, relu=False, out=None, want_bf16=False):
     if want_bf16:
         if M <= 256 and K % 64 == 0 and N % 4 == 0:
             yb = torch.empty(M, N, device=x.device, dtype=torch.bfloat16)
-            check(_lib.lib().mhe_linear_f32_bf16copy(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), _ptr(yb), M, N, K, int(relu), _stream()), "mhe_linear_f32_bf16copy")
+            launch("mhe_linear_f32_bf16copy", x, w, bias, y, yb, M, N, K, int(relu))
             return y, yb
-        check(_lib.lib().mhe_linear_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), M, N, K, int(relu), _stream()), "mhe_linear_f32")
+        launch("mhe_linear_f32", x, w, bias, y, M, N, K, int(relu))
         return y, None
-    check(_lib.lib().mhe_linear_f32(_ptr(x), _ptr(w), _ptr(bias), _ptr(y), M, N, K, int(relu), _stream()), "mhe_linear_f32")
+    launch("mhe_linear_f32", x, w, bias, y, M, N, K, int(relu))
     return y
 
 
@@ -171,7 +237,7 @@ def randn(rows, cols, device, scale=1.0, state=None):
     """[rows, cols] f32 ~ N(0, scale^2) drawn on the device by mhe_randn_f32 (graph-capturable: the launch advances its own counter)"""
     out = torch.empty(rows, cols, device=device, dtype=torch.float32)
     st = state if state is not None else rng_state(out.device)
-    check(_lib.lib().mhe_randn_f32(_ptr(out), out.numel(), _ptr(st), float(scale), _stream()), "mhe_randn_f32")
+    launch("mhe_randn_f32", out, out.numel(), st, float(scale))
     return out
 
 
@@ -187,7 +253,7 @@ def dropout_(x, p, bits=None, state=None):
     else:
         _chk(bits, torch.uint8, "dropout.bits", (x.numel() // 8,))
         st = None
-    check(_lib.lib().mhe_dropout(_ptr(x), dtype_code(x.dtype), _ptr(bits), x.numel(), float(p), _ptr(st), int(draw), _stream()), "mhe_dropout")
+    launch("mhe_dropout", x, dtype_code(x.dtype), bits, x.numel(), float(p), st, int(draw))
     return bits
 
 
@@ -203,8 +269,7 @@ def reparam(mn, l2, eps=None, sigmoid_act=False, deterministic=False):
     if eps is not None:
         _chk(eps, torch.float32, "reparam.eps", mn.shape)
     sd, z = torch.empty_like(mn), torch.empty_like(mn)
-    check(_lib.lib().mhe_reparam_f32(_ptr(mn), _ptr(l2), _ptr(eps), _ptr(sd), _ptr(z), mn.numel(), int(sigmoid_act), int(deterministic or eps is None),
-                                     _stream()), "mhe_reparam_f32")
+    launch("mhe_reparam_f32", mn, l2, eps, sd, z, mn.numel(), int(sigmoid_act), int(deterministic or eps is None))
     return sd, z
 
 
@@ -252,9 +317,8 @@ def flow_couplings(x_in, cond, wstream, bias2, mask, B, hidden, direction, want_
     out = torch.empty_like(x_in)
     sum_s = torch.empty(R, device=x_in.device, dtype=torch.float32)
     logp = torch.empty(R, device=x_in.device, dtype=torch.float32) if want_log_prob else None
-    fn = _lib.lib().mhe_flow_couplings_bf16 if bf16 else _lib.lib().mhe_flow_couplings_f32
-    check(fn(_ptr(x_in), _ptr(out), _ptr(cond), _ptr(wstream), _ptr(bias2), _ptr(mask), _ptr(sum_s), _ptr(logp), R, B, dim,
-             hidden, ncoup, direction, _stream()), "mhe_flow_couplings_bf16" if bf16 else "mhe_flow_couplings_f32")
+    launch("mhe_flow_couplings_bf16" if bf16 else "mhe_flow_couplings_f32", x_in, out, cond, wstream, bias2, mask, sum_s, logp, R, B, dim, hidden, ncoup,
+           direction)
     return out, sum_s, logp
 
 
@@ -271,9 +335,7 @@ def flow_couplings_emit(x_in, cond, wstream, bias2, mask, B, hidden, direction, 
     out = torch.empty_like(x_in)
     sum_s = torch.empty(R, device=x_in.device, dtype=torch.float32)
     logp = torch.empty(R, device=x_in.device, dtype=torch.float32)
-    check(_lib.lib().mhe_flow_couplings_bf16_emit(_ptr(x_in), _ptr(out), _ptr(cond), _ptr(wstream), _ptr(bias2), _ptr(mask), _ptr(sum_s),
-                                                  _ptr(logp), _ptr(h1), _ptr(h2), _ptr(o), R, B, dim, hidden, ncoup, direction, _stream()),
-          "mhe_flow_couplings_bf16_emit")
+    launch("mhe_flow_couplings_bf16_emit", x_in, out, cond, wstream, bias2, mask, sum_s, logp, h1, h2, o, R, B, dim, hidden, ncoup, direction)
     return out, sum_s, logp
 
 
@@ -310,9 +372,8 @@ def flow_couplings_frag(x_in, cond, w0F, w1F, w2F, w_net_stride, bias2, mask, B,
     out = torch.empty_like(x_in)
     sum_s = torch.empty(R, device=x_in.device, dtype=torch.float32)
     logp = torch.empty(R, device=x_in.device, dtype=torch.float32) if want_log_prob else None
-    check(_lib.lib().mhe_flow_couplings_frag_bf16(_ptr(x_in), _ptr(out), _ptr(cond), 4 * ncoup * hidden, _ptr(w0F), _ptr(w1F), _ptr(w2F),
-                                                  int(w_net_stride), _ptr(bias2), _ptr(mask), _ptr(sum_s), _ptr(logp), _ptr(h1), _ptr(h2), _ptr(o),
-                                                  _ptr(sign_bits), R, B, dim, hidden, ncoup, direction, _stream()), "mhe_flow_couplings_frag_bf16")
+    launch("mhe_flow_couplings_frag_bf16", x_in, out, cond, 4 * ncoup * hidden, w0F, w1F, w2F, int(w_net_stride), bias2, mask, sum_s, logp, h1, h2, o, sign_bits, R,
+           B, dim, hidden, ncoup, direction)
     return out, sum_s, logp
 
 
@@ -358,10 +419,8 @@ def mano_joints(th45, det, tables, crop_uv=None, vis=None, laplace_b=0.03, th45_
     if bits is not None:
         if "verts" in want or "mesh_mm" in want:
             raise ValueError("mano_joints: the mesh outputs come from the uv-only pass (mods=None)")
-        check(_lib.lib().mhe_mano_joints_mods_f32(_ptr(th45), _ptr(det), _ptr(crop_uv), _ptr(vis), _ptr(pose3d), _ptr(tables),
-                                                  _ptr(o["z"]), _ptr(o["xyz"]), _ptr(o["uv"]), _ptr(o["terms"]), _ptr(o["log_p"]),
-                                                  _ptr(o["norms"]), _ptr(o["joints_mm"]), R, B, bits, float(laplace_b), float(laplace_b_3d),
-                                                  float(th45_alpha), int(inv_norm), float(image_size), _stream()), "mhe_mano_joints_mods_f32")
+        launch("mhe_mano_joints_mods_f32", th45, det, crop_uv, vis, pose3d, tables, o["z"], o["xyz"], o["uv"], o["terms"], o["log_p"], o["norms"], o["joints_mm"], R,
+               B, bits, float(laplace_b), float(laplace_b_3d), float(th45_alpha), int(inv_norm), float(image_size))
         return o
     if "verts" in want or "mesh_mm" in want:
         if "verts" in want and "mesh_mm" in want:
@@ -369,16 +428,11 @@ def mano_joints(th45, det, tables, crop_uv=None, vis=None, laplace_b=0.03, th45_
         key = "verts" if "verts" in want else "mesh_mm"
         o[key] = torch.empty(R, 778, 3, device=dev, dtype=torch.float32)
         ws = torch.empty(_lib.lib().mhe_mano_verts_workspace_floats(R), device=dev, dtype=torch.float32)
-        check(_lib.lib().mhe_mano_decode_f32(_ptr(th45), _ptr(det), _ptr(crop_uv), _ptr(vis), _ptr(tables),
-                                             _ptr(o["z"]), _ptr(o["xyz"]), _ptr(o["uv"]), _ptr(o["terms"]), _ptr(o["log_p"]),
-                                             _ptr(o["norms"]), _ptr(o["joints_mm"]), _ptr(o[key]), _ptr(ws), R, B, float(laplace_b),
-                                             float(th45_alpha), int(inv_norm), float(image_size), int(key == "mesh_mm"), _stream()),
-              "mhe_mano_decode_f32")
+        launch("mhe_mano_decode_f32", th45, det, crop_uv, vis, tables, o["z"], o["xyz"], o["uv"], o["terms"], o["log_p"], o["norms"], o["joints_mm"], o[key], ws, R,
+               B, float(laplace_b), float(th45_alpha), int(inv_norm), float(image_size), int(key == "mesh_mm"))
         return o
-    check(_lib.lib().mhe_mano_joints_f32(_ptr(th45), _ptr(det), _ptr(crop_uv), _ptr(vis), _ptr(tables),
-                                         _ptr(o["z"]), _ptr(o["xyz"]), _ptr(o["uv"]), _ptr(o["terms"]), _ptr(o["log_p"]),
-                                         _ptr(o["norms"]), _ptr(o["joints_mm"]), R, B, float(laplace_b), float(th45_alpha), int(inv_norm),
-                                         float(image_size), _stream()), "mhe_mano_joints_f32")
+    launch("mhe_mano_joints_f32", th45, det, crop_uv, vis, tables, o["z"], o["xyz"], o["uv"], o["terms"], o["log_p"], o["norms"], o["joints_mm"], R, B,
+           float(laplace_b), float(th45_alpha), int(inv_norm), float(image_size))
     return o
 
 
@@ -397,14 +451,11 @@ def mano_joints_bwd(th45, det, tables, crop_uv, vis, g_log_p, N, laplace_b=0.03,
     g_th45 = torch.empty(R, 45, device=th45.device, dtype=torch.float32)
     g_rows = torch.empty(R, 16, device=th45.device, dtype=torch.float32)
     if mods is None:
-        check(_lib.lib().mhe_mano_joints_bwd_f32(_ptr(th45), _ptr(det), _ptr(crop_uv), _ptr(vis), _ptr(tables), _ptr(g_log_p),
-                                                 _ptr(g_th45), _ptr(g_rows), R, B, float(laplace_b), float(th45_alpha), 1.0 / N,
-                                                 _stream()), "mhe_mano_joints_bwd_f32")
+        launch("mhe_mano_joints_bwd_f32", th45, det, crop_uv, vis, tables, g_log_p, g_th45, g_rows, R, B, float(laplace_b), float(th45_alpha), 1.0 / N)
     else:
         bits = int(mods) if isinstance(mods, int) else mods_bits(mods)
-        check(_lib.lib().mhe_mano_joints_mods_bwd_f32(_ptr(th45), _ptr(det), _ptr(crop_uv), _ptr(vis), _ptr(pose3d), _ptr(tables),
-                                                      _ptr(g_log_p), _ptr(g_th45), _ptr(g_rows), R, B, bits, float(laplace_b),
-                                                      float(laplace_b_3d), float(th45_alpha), 1.0 / N, _stream()), "mhe_mano_joints_mods_bwd_f32")
+        launch("mhe_mano_joints_mods_bwd_f32", th45, det, crop_uv, vis, pose3d, tables, g_log_p, g_th45, g_rows, R, B, bits, float(laplace_b), float(laplace_b_3d),
+               float(th45_alpha), 1.0 / N)
     return g_th45, sum_over_hypotheses(g_rows, N, B)
 
 
@@ -414,8 +465,7 @@ def sum_over_hypotheses(rows, N, B, out=None, accumulate=False, out_stride=0):
     _chk(rows, torch.float32, "sum_over_hypotheses.rows", (N * B, Cc))
     if out is None:
         out = torch.empty(B, Cc, device=rows.device, dtype=torch.float32)
-    check(_lib.lib().mhe_sum_over_hypotheses_f32(_ptr(rows), C.c_void_p(out.data_ptr()), N, B, Cc, int(accumulate), int(out_stride), _stream()),
-          "mhe_sum_over_hypotheses_f32")
+    launch("mhe_sum_over_hypotheses_f32", rows, out, N, B, Cc, int(accumulate), int(out_stride))
     return out
 
 
@@ -424,7 +474,7 @@ def mano_verts(z, tables, mm=False):
     _chk(z, torch.float32, "mano_verts.z", (R, 61))
     verts = torch.empty(R, 778, 3, device=z.device, dtype=torch.float32)
     ws = torch.empty(_lib.lib().mhe_mano_verts_workspace_floats(R), device=z.device, dtype=torch.float32)
-    check(_lib.lib().mhe_mano_verts_f32(_ptr(z), _ptr(tables), _ptr(verts), _ptr(ws), R, int(mm), _stream()), "mhe_mano_verts_f32")
+    launch("mhe_mano_verts_f32", z, tables, verts, ws, R, int(mm))
     return verts
 
 
@@ -432,7 +482,7 @@ def mano_regress_joints(verts, tables):
     R = verts.shape[0]
     _chk(verts, torch.float32, "regress.verts", (R, 778, 3))
     j = torch.empty(R, 21, 3, device=verts.device, dtype=torch.float32)
-    check(_lib.lib().mhe_mano_regress_joints_f32(_ptr(verts), _ptr(tables), _ptr(j), R, _stream()), "mhe_mano_regress_joints_f32")
+    launch("mhe_mano_regress_joints_f32", verts, tables, j, R)
     return j
 
 
@@ -442,8 +492,7 @@ def elbo_reduce(log_p_rows, log_q_rows, N, B):
     if log_q_rows is not None:
         _chk(log_q_rows, torch.float32, "elbo.log_q_rows", (N * B,))
     q, h, lp = (torch.empty(B, device=dev, dtype=torch.float32) for _ in range(3))
-    check(_lib.lib().mhe_elbo_reduce_f32(_ptr(log_p_rows), _ptr(log_q_rows), _ptr(q), _ptr(h), _ptr(lp), N, B, _stream()),
-          "mhe_elbo_reduce_f32")
+    launch("mhe_elbo_reduce_f32", log_p_rows, log_q_rows, q, h, lp, N, B)
     return q, h, lp
 
 
@@ -453,8 +502,7 @@ def topk_gather(score, rows, N, B, Q):
     _chk(score, torch.float32, "topk.score", (N * B,)); _chk(rows, torch.float32, "topk.rows", (N * B, D))
     idx = torch.empty(Q, B, device=rows.device, dtype=torch.int32)
     out = torch.empty(Q * B, D, device=rows.device, dtype=torch.float32)
-    check(_lib.lib().mhe_topk_gather_f32(_ptr(score), _ptr(rows), _ptr(idx), _ptr(out), N, B, Q, D, _stream()),
-          "mhe_topk_gather_f32")
+    launch("mhe_topk_gather_f32", score, rows, idx, out, N, B, Q, D)
     return idx, out
 
 
@@ -464,8 +512,7 @@ def metrics(xyz, uv, pose3d, scale, crop_uv, vis):
     _chk(pose3d, torch.float32, "metrics.pose3d", (B, 63)); _chk(scale, torch.float32, "metrics.scale", (B,))
     _chk(crop_uv, torch.float32, "metrics.crop_uv", (B, 42)); _chk(vis, torch.float32, "metrics.vis", (B, 21))
     out = torch.empty(14, B, device=xyz.device, dtype=torch.float32)
-    check(_lib.lib().mhe_metrics_f32(_ptr(xyz), _ptr(uv), _ptr(pose3d), _ptr(scale), _ptr(crop_uv), _ptr(vis), _ptr(out),
-                                     N, B, _stream()), "mhe_metrics_f32")
+    launch("mhe_metrics_f32", xyz, uv, pose3d, scale, crop_uv, vis, out, N, B)
     return out
 
 
@@ -478,8 +525,7 @@ def metrics_split(xyz_err, xyz_spread, uv, pose3d, scale, crop_uv, vis):
     _chk(pose3d, torch.float32, "metrics_split.pose3d", (B, 63)); _chk(scale, torch.float32, "metrics_split.scale", (B,))
     _chk(crop_uv, torch.float32, "metrics_split.crop_uv", (B, 42)); _chk(vis, torch.float32, "metrics_split.vis", (B, 21))
     out = torch.empty(14, B, device=xyz_err.device, dtype=torch.float32)
-    check(_lib.lib().mhe_metrics_split_f32(_ptr(xyz_err), _ptr(xyz_spread), _ptr(uv), _ptr(pose3d), _ptr(scale), _ptr(crop_uv), _ptr(vis),
-                                           _ptr(out), N, B, _stream()), "mhe_metrics_split_f32")
+    launch("mhe_metrics_split_f32", xyz_err, xyz_spread, uv, pose3d, scale, crop_uv, vis, out, N, B)
     return out
 
 
@@ -507,8 +553,7 @@ def procrustes_align(pred, target, want_transform=False):
     ws = torch.empty(nws, device=pred.device, dtype=torch.float32)
     R = torch.empty(N, B, 3, 3, device=pred.device, dtype=torch.float32) if want_transform else None
     s = torch.empty(N, B, device=pred.device, dtype=torch.float32) if want_transform else None
-    check(L.mhe_procrustes_align_f32(_ptr(pred), _ptr(target), _ptr(out), _ptr(R), _ptr(s), _ptr(ws), nws, N, B, P, _stream()),
-          "mhe_procrustes_align_f32")
+    launch("mhe_procrustes_align_f32", pred, target, out, R, s, ws, nws, N, B, P)
     return (out, R, s) if want_transform else out
 
 
@@ -540,39 +585,26 @@ def conv2d_nhwc(x, w, KH, KW, stride, pad, in_scale=None, in_shift=None, relu_in
             raise ValueError("conv2d_nhwc: mask= is the plain data-gradient form (no affine / statistics / relu; out_shift = a per-channel constant)")
         _chk(mask, dt, "conv.mask", (B, Ho, Wo, Cout))
         if out_shift is not None:        # y = (conv + out_shift + residual) [mask > 0], one consumer's sums at most
-            if bn is not None and len(bn) > 1:
-                raise ValueError("conv2d_nhwc: out_shift= with mask= takes one bn consumer")
-            by, bmi, bst = (list(bn or []) + [(None, None, None)])[0]
-            if by is not None:
-                _chk(by, dt, "conv.bn_y", (B, Ho, Wo, Cout)); _chk(bmi, torch.float32, "conv.bn_mean_invstd", (2, Cout))
-                _chk_stats(bst, "conv.bn_stats", Cout)
+            ext = _bn_consumers(bn, 1, dt, y.shape, Cout, "conv", only_one="conv2d_nhwc: out_shift= with mask= takes one bn consumer")
             cin2 = 0
             if xcat is not None:         # the operand's K range continued on a second tensor: w is [Cout][Cin + cin2]
                 cin2 = xcat.shape[-1]
                 _chk(xcat, dt, "conv.xcat", (B, H, W, cin2))
                 if tuple(w.shape) != (Cout, Cin + cin2):
                     raise ValueError(f"conv2d_nhwc: xcat= needs w [{Cout}, {Cin + cin2}], got {tuple(w.shape)}")
-            with _dg_timed(d, x, y, w, residual, mask, None, [by], "cat" if xcat is not None else "bias", xcat):
-                check(_lib.lib().mhe_conv2d_masked_bias_nhwc(C.byref(d), _ptr(x), _ptr(xcat), int(cin2), _ptr(w), _ptr(y), _ptr(residual), _ptr(mask),
-                                                             _ptr(out_shift), _ptr(by), _ptr(bmi), _ptr(bst), _stream()), "mhe_conv2d_masked_bias_nhwc")
+            with _dg_timed(d, x, y, w, residual, mask, None, ext[:1], "cat" if xcat is not None else "bias", xcat):
+                launch("mhe_conv2d_masked_bias_nhwc", C.byref(d), x, xcat, int(cin2), w, y, residual, mask, out_shift, *ext)
             return y
         if xcat is not None:
             raise ValueError("conv2d_nhwc: xcat= comes with mask= and out_shift=")
-        ext = []
-        for by, bmi, bst in (list(bn or []) + [(None, None, None)] * 2)[:2]:
-            if by is not None:
-                _chk(by, dt, "conv.bn_y", (B, Ho, Wo, Cout)); _chk(bmi, torch.float32, "conv.bn_mean_invstd", (2, Cout))
-                _chk_stats(bst, "conv.bn_stats", Cout)
-            ext += [_ptr(by), _ptr(bmi), _ptr(bst)]
+        ext = _bn_consumers(bn, 2, dt, y.shape, Cout, "conv")
         if mask_bits is not None:        # the gate also as bits [pixel][Cout / 8] (bottleneck_tail want_bits=): read instead of `mask` where the kernel can
             _chk(mask_bits, torch.uint8, "conv.mask_bits", (B, Ho, Wo, Cout // 8))
             with _dg_timed(d, x, y, w, residual, mask, mask_bits, [b[0] for b in (bn or [])], "bits"):
-                check(_lib.lib().mhe_conv2d_masked_bits_nhwc(C.byref(d), _ptr(x), _ptr(w), _ptr(y), _ptr(residual), _ptr(mask), _ptr(mask_bits), *ext, _stream()),
-                      "mhe_conv2d_masked_bits_nhwc")
+                launch("mhe_conv2d_masked_bits_nhwc", C.byref(d), x, w, y, residual, mask, mask_bits, *ext)
             return y
         with _dg_timed(d, x, y, w, residual, mask, None, [b[0] for b in (bn or [])], ""):
-            check(_lib.lib().mhe_conv2d_masked_nhwc(C.byref(d), _ptr(x), _ptr(w), _ptr(y), _ptr(residual), _ptr(mask), *ext, _stream()),
-                  "mhe_conv2d_masked_nhwc")
+            launch("mhe_conv2d_masked_nhwc", C.byref(d), x, w, y, residual, mask, *ext)
         return y
     if bn:
         raise ValueError("conv2d_nhwc: bn= needs mask= (data-gradient form)")
@@ -583,21 +615,12 @@ def conv2d_nhwc(x, w, KH, KW, stride, pad, in_scale=None, in_shift=None, relu_in
         _chk(xcat, dt, "conv.xcat", (B, H, W, cin2))
         if tuple(w.shape) != (Cout, Cin + cin2):
             raise ValueError(f"conv2d_nhwc: xcat= needs w [{Cout}, {Cin + cin2}], got {tuple(w.shape)}")
-        check(_lib.lib().mhe_conv1x1_cat_bias_nhwc(C.byref(d), _ptr(x), _ptr(xcat), int(cin2), _ptr(w), _ptr(y), _ptr(residual), _ptr(out_shift), _stream()),
-              "mhe_conv1x1_cat_bias_nhwc")
+        launch("mhe_conv1x1_cat_bias_nhwc", C.byref(d), x, xcat, int(cin2), w, y, residual, out_shift)
         return y
-    if TIMING:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(_lib.lib().mhe_conv2d_nhwc(C.byref(d), _ptr(x), _ptr(w), _ptr(y), _ptr(in_scale), _ptr(in_shift),
-                                     _ptr(out_scale), _ptr(out_shift), _ptr(residual), _ptr(stats), _stream()),
-          "mhe_conv2d_nhwc")
-    if TIMING:
-        ev1.record()
-        es = x.element_size()      # algorithmic HBM bytes: input once, output once, weights once (+ residual)
-        nbytes = es * (x.numel() + y.numel() + w.numel() + (residual.numel() if residual is not None else 0))
-        KERNEL_TIMES.append((_conv_kernel_name(d, dt, 1 if in_scale is not None else 3 if residual is not None else 0),
-                             2.0 * B * Ho * Wo * Cout * KH * KW * Cin, ev0, ev1, nbytes))
+    # (algorithmic HBM bytes: input once, output once, weights once (+ residual))
+    with _Timed(lambda: (_conv_kernel_name(d, dt, 1 if in_scale is not None else 3 if residual is not None else 0), 2.0 * B * Ho * Wo * Cout * KH * KW * Cin,
+                         x.element_size() * (x.numel() + y.numel() + w.numel() + (residual.numel() if residual is not None else 0)))):
+        launch("mhe_conv2d_nhwc", C.byref(d), x, w, y, in_scale, in_shift, out_scale, out_shift, residual, stats)
     return y
 
 
@@ -609,14 +632,9 @@ def conv1x1_stats(x, w, in_scale, in_shift, stats):
     _chk(in_scale, torch.float32, "conv_stats.in_scale", (Cin,)); _chk(in_shift, torch.float32, "conv_stats.in_shift", (Cin,))
     _chk_stats(stats, "conv_stats.stats", Cout)
     d = ConvDesc(B, H, W, Cin, Cout, 1, 1, 1, 0, BF16, 1, 0, 0, 0)
-    if TIMING:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(_lib.lib().mhe_conv1x1_stats_nhwc(C.byref(d), _ptr(x), _ptr(w), _ptr(in_scale), _ptr(in_shift), _ptr(stats), _stream()), "mhe_conv1x1_stats_nhwc")
-    if TIMING:
-        ev1.record()
-        name = "mhe::conv::conv_wide_kernel<128, 4, true>" if Cin == 256 else "mhe::conv::conv1x1_stream_kernel<%d, 256, true, false>" % (Cin // 64)
-        KERNEL_TIMES.append((name, 2.0 * B * H * W * Cout * Cin, ev0, ev1, 2 * (x.numel() + w.numel())))
+    name = "mhe::conv::conv_wide_kernel<128, 4, true>" if Cin == 256 else "mhe::conv::conv1x1_stream_kernel<%d, 256, true, false>" % (Cin // 64)
+    with _Timed(lambda: (name, 2.0 * B * H * W * Cout * Cin, 2 * (x.numel() + w.numel()))):
+        launch("mhe_conv1x1_stats_nhwc", C.byref(d), x, w, in_scale, in_shift, stats)
     return stats
 
 
@@ -639,21 +657,15 @@ def conv1x1_gram_bn(x, in_scale, in_shift, w, bn_weight, bn_bias, running_mean, 
     gram, ws = bufs
     L = _lib.lib()
     _chk(gram, STAT_DTYPE, "gram.accumulators", (L.mhe_gram_stats_words(Cb),))
-    if TIMING:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
     if a_out is not None:        # also relu(x * in_scale + in_shift) itself, as the matrix cores multiplied it
         _chk(a_out, torch.bfloat16, "gram.a_out", (B, H, W, Cb))
-    check(L.mhe_conv1x1_gram_store_nhwc(_ptr(x), _ptr(in_scale), _ptr(in_shift), 1, _ptr(gram), _ptr(a_out), B * H * W, Cb, _stream()), "mhe_conv1x1_gram_store_nhwc")
-    if TIMING:
-        ev1.record()
-        KERNEL_TIMES.append(("mhe::conv::gram_kernel<%d>" % Cb, 2.0 * B * H * W * Cb * Cb, ev0, ev1, 2 * x.numel()))
+    with _Timed(lambda: ("mhe::conv::gram_kernel<%d>" % Cb, 2.0 * B * H * W * Cb * Cb, 2 * x.numel())):
+        launch("mhe_conv1x1_gram_store_nhwc", x, in_scale, in_shift, 1, gram, a_out, B * H * W, Cb)
     scale = torch.empty(Cn, device=x.device, dtype=torch.float32)
     shift = torch.empty_like(scale)
     mi = torch.empty(2, Cn, device=x.device, dtype=torch.float32) if want_mean_invstd else None
-    check(L.mhe_gram_bn_finalize(_ptr(gram), _ptr(ws), _ptr(w), _ptr(bn_weight), _ptr(bn_bias), _ptr(running_mean), _ptr(running_var), _ptr(scale),
-                                 _ptr(shift), _ptr(mi), Cn, Cb, float(B * H * W), float(momentum), float(eps), _ptr(num_batches_tracked), _stream()),
-          "mhe_gram_bn_finalize")
+    launch("mhe_gram_bn_finalize", gram, ws, w, bn_weight, bn_bias, running_mean, running_var, scale, shift, mi, Cn, Cb, float(B * H * W), float(momentum),
+           float(eps), num_batches_tracked)
     return (scale, shift, mi) if want_mean_invstd else (scale, shift)
 
 
@@ -671,7 +683,7 @@ def conv3_bn_fold(D, w, gram_totals, rev_stats, gamma, mean_invstd, count, dgamm
         s_ptr, ld_s = C.c_void_p(w_dg.data_ptr() + 2 * Cn), Cn + Cb
     else:
         _chk(S, torch.bfloat16, "fold.S", (Cb, Cb))
-        s_ptr, ld_s = _ptr(S), Cb
+        s_ptr, ld_s = S, Cb
     _chk(D, torch.float32, "fold.D", (Cn, Cb)); _chk(w, torch.bfloat16, "fold.w", (Cn, Cb)); _chk(gram_totals, torch.float64, "fold.gram")
     _chk_stats(rev_stats, "fold.rev_stats", Cn); _chk(gamma, torch.float32, "fold.gamma", (Cn,))
     _chk(mean_invstd, torch.float32, "fold.mean_invstd", (2, Cn)); _chk(dgamma, torch.float32, "fold.dgamma", (Cn,)); _chk(dbeta, torch.float32, "fold.dbeta", (Cn,))
@@ -679,9 +691,8 @@ def conv3_bn_fold(D, w, gram_totals, rev_stats, gamma, mean_invstd, count, dgamm
     _chk(c0, torch.float32, "fold.c0", (Cb,)); _chk(coef_ws, torch.float32, "fold.coef_ws")
     if gram_totals.numel() < Cb * Cb + Cb or dW.numel() < Cn * Cb or w_dg.shape[0] != Cb or w_dg.shape[1] < Cn or coef_ws.numel() < 2 * Cn:
         raise ValueError("conv3_bn_fold: operand sizes")
-    check(_lib.lib().mhe_conv3_bn_fold(_ptr(D), _ptr(w), _ptr(gram_totals), _ptr(rev_stats), _ptr(gamma), _ptr(mean_invstd), float(count), _ptr(dgamma),
-                                       _ptr(dbeta), _ptr(dW), _ptr(w_dg), int(w_dg.shape[1]), s_ptr, int(ld_s), _ptr(c0), _ptr(coef_ws), Cn, Cb, _stream()),
-          "mhe_conv3_bn_fold")
+    launch("mhe_conv3_bn_fold", D, w, gram_totals, rev_stats, gamma, mean_invstd, float(count), dgamma, dbeta, dW, w_dg, int(w_dg.shape[1]), s_ptr, int(ld_s), c0,
+           coef_ws, Cn, Cb)
 
 
 def conv3x3_halo_supported(B, H, W, Cin, Cout):
@@ -695,7 +706,7 @@ def conv3x3_halo_pack(w):
     if K % 9 or (K // 9) % 64 or Cout % 128:
         raise ValueError(f"conv3x3_halo_pack: weight rows [{Cout}][{K}] are not 9 x (a multiple of 64) wide / a multiple of 128 many")
     out = torch.empty_like(w)
-    check(_lib.lib().mhe_conv3x3_halo_pack_bf16(_ptr(w), _ptr(out), int(Cout), int(K // 9), _stream()), "mhe_conv3x3_halo_pack_bf16")
+    launch("mhe_conv3x3_halo_pack_bf16", w, out, int(Cout), int(K // 9))
     return out
 
 
@@ -714,19 +725,10 @@ def conv3x3_halo(x, w_halo, in_scale=None, in_shift=None, relu_in=False, a_out=N
     for t, name, shape in ((a_out, "a_out", tuple(x.shape)), (residual, "residual", tuple(y.shape)), (mask, "mask", tuple(y.shape))):
         if t is not None:
             _chk(t, torch.bfloat16, "halo." + name, shape)
-    by, bmi, bst = (None, None, None) if bn is None else bn
-    if by is not None:
-        _chk(by, torch.bfloat16, "halo.bn_y", tuple(y.shape)); _chk(bmi, torch.float32, "halo.bn_mi", (2, Cout)); _chk_stats(bst, "halo.bn_stats", Cout)
-    if TIMING:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(_lib.lib().mhe_conv3x3_halo_nhwc(B, H, W, Cin, Cout, _ptr(x), _ptr(w_halo), _ptr(y), _ptr(in_scale), _ptr(in_shift), int(bool(relu_in)),
-                                           _ptr(a_out), _ptr(stats), _ptr(residual), _ptr(mask), _ptr(by), _ptr(bmi), _ptr(bst), _stream()),
-          "mhe_conv3x3_halo_nhwc")
-    if TIMING:
-        ev1.record()
-        KERNEL_TIMES.append(("mhe::conv::conv_halo_kernel<%d, %s>" % (W, "true" if mask is not None else "false"), 2.0 * B * H * W * Cout * 9 * Cin, ev0, ev1,
-                             2 * (x.numel() + y.numel() + w_halo.numel())))
+    ext = _bn_consumers(None if bn is None else [bn], 1, torch.bfloat16, y.shape, Cout, "halo")
+    with _Timed(lambda: ("mhe::conv::conv_halo_kernel<%d, %s>" % (W, "true" if mask is not None else "false"), 2.0 * B * H * W * Cout * 9 * Cin,
+                         2 * (x.numel() + y.numel() + w_halo.numel()))):
+        launch("mhe_conv3x3_halo_nhwc", B, H, W, Cin, Cout, x, w_halo, y, in_scale, in_shift, int(bool(relu_in)), a_out, stats, residual, mask, *ext)
     return y
 
 
@@ -742,11 +744,8 @@ def conv3x3_halo_dgrad_bn(g, y_raw, coef, w_halo, mask, gy_out=None, residual=No
         _chk(gy_out, torch.bfloat16, "halo_dg.gy_out", tuple(g.shape))
     if residual is not None:
         _chk(residual, torch.bfloat16, "halo_dg.residual", tuple(gx.shape))
-    by, bmi, bst = (None, None, None) if bn is None else bn
-    if by is not None:
-        _chk(by, torch.bfloat16, "halo_dg.bn_y", tuple(gx.shape)); _chk(bmi, torch.float32, "halo_dg.bn_mi", (2, Cout)); _chk_stats(bst, "halo_dg.bn_stats", Cout)
-    check(_lib.lib().mhe_conv3x3_halo_dgrad_bn_nhwc(B, H, W, Cin, Cout, _ptr(g), _ptr(y_raw), _ptr(coef), _ptr(w_halo), _ptr(gx), _ptr(gy_out), _ptr(residual),
-                                                    _ptr(mask), _ptr(by), _ptr(bmi), _ptr(bst), _stream()), "mhe_conv3x3_halo_dgrad_bn_nhwc")
+    ext = _bn_consumers(None if bn is None else [bn], 1, torch.bfloat16, gx.shape, Cout, "halo_dg")
+    launch("mhe_conv3x3_halo_dgrad_bn_nhwc", B, H, W, Cin, Cout, g, y_raw, coef, w_halo, gx, gy_out, residual, mask, *ext)
     return gx
 
 
@@ -776,20 +775,13 @@ def bottleneck_tail(y2, bn2, w3, bn3, identity, id_aff, w1, stats=None, want_bit
     # want_bits: also [a > 0] as bits, byte [pixel][channel / 8] - the gate the reverse pass reads instead of `a` (conv2d_nhwc mask_bits=)
     bits = torch.empty(B, H, W, Cw // 8, device=y2.device, dtype=torch.uint8) if want_bits else None
     d = ConvDesc(B, H, W, Cw, Cout, 1, 1, 1, 0, BF16, 1, 0, 0, 0)
-    if TIMING:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    ida = (_ptr(id_aff[0] if id_aff is not None else None), _ptr(id_aff[1] if id_aff is not None else None))
-    if quarter:
-        check(_lib.lib().mhe_bottleneck_tail_quarter_nhwc(C.byref(d), Cb, _ptr(y2), _ptr(bn2[0]), _ptr(bn2[1]), _ptr(w3), _ptr(bn3[0]), _ptr(bn3[1]), _ptr(identity),
-                                                          *ida, _ptr(w1), _ptr(a), _ptr(y1), _ptr(stats), _stream()), "mhe_bottleneck_tail_quarter_nhwc")
-    else:
-        check(_lib.lib().mhe_bottleneck_tail_bits_nhwc(C.byref(d), Cb, _ptr(y2), _ptr(bn2[0]), _ptr(bn2[1]), _ptr(w3), _ptr(bn3[0]), _ptr(bn3[1]), _ptr(identity),
-                                                       *ida, _ptr(w1), _ptr(a), _ptr(bits), _ptr(y1), _ptr(stats), _stream()), "mhe_bottleneck_tail_bits_nhwc")
-    if TIMING:
-        ev1.record()
-        nbytes = 2 * (y2.numel() + identity.numel() + a.numel() + y1.numel() + w3.numel() + w1.numel())
-        KERNEL_TIMES.append(("mhe::conv::bottleneck_tail%s_kernel<%d, %d>" % ("_quarter" if quarter else "", Cb, Cout), 2.0 * B * H * W * Cw * (Cb + Cout), ev0, ev1, nbytes))
+    ida = id_aff if id_aff is not None else (None, None)
+    with _Timed(lambda: ("mhe::conv::bottleneck_tail%s_kernel<%d, %d>" % ("_quarter" if quarter else "", Cb, Cout), 2.0 * B * H * W * Cw * (Cb + Cout),
+                         2 * (y2.numel() + identity.numel() + a.numel() + y1.numel() + w3.numel() + w1.numel()))):
+        if quarter:
+            launch("mhe_bottleneck_tail_quarter_nhwc", C.byref(d), Cb, y2, bn2[0], bn2[1], w3, bn3[0], bn3[1], identity, *ida, w1, a, y1, stats)
+        else:
+            launch("mhe_bottleneck_tail_bits_nhwc", C.byref(d), Cb, y2, bn2[0], bn2[1], w3, bn3[0], bn3[1], identity, *ida, w1, a, bits, y1, stats)
     return (a, y1, bits) if want_bits else (a, y1)
 
 
@@ -803,7 +795,7 @@ def linear_bf16_f32out(x, w, bias=None, out=None):
     y = out if out is not None else torch.empty(R, N, device=x.device, dtype=torch.float32)
     _chk(y, torch.float32, "linear_bf16.out", (R, N))
     d = ConvDesc(R, 1, 1, K, N, 1, 1, 1, 0, BF16, 0, 0, 0)
-    check(_lib.lib().mhe_conv2d_f32out_nhwc(C.byref(d), _ptr(x), _ptr(w), _ptr(y), _ptr(bias), _stream()), "mhe_conv2d_f32out_nhwc")
+    launch("mhe_conv2d_f32out_nhwc", C.byref(d), x, w, y, bias)
     return y
 
 
@@ -820,15 +812,9 @@ def conv3x3s2_dgrad(gy, w4, residual=None, mask=None, bn=None, tile=0):
     for t, name in ((residual, "residual"), (mask, "mask")):
         if t is not None:
             _chk(t, dt, "dgrad_s2." + name, dx.shape)
-    ext = []
-    for by, bmi, bst in (list(bn or []) + [(None, None, None)] * 2)[:2]:
-        if by is not None:
-            _chk(by, dt, "dgrad_s2.bn_y", dx.shape); _chk(bmi, torch.float32, "dgrad_s2.bn_mean_invstd", (2, Cin))
-            _chk_stats(bst, "dgrad_s2.bn_stats", Cin)
-        ext += [_ptr(by), _ptr(bmi), _ptr(bst)]
+    ext = _bn_consumers(bn, 2, dt, dx.shape, Cin, "dgrad_s2")
     wp = (C.c_void_p * 4)(*[w.data_ptr() for w in w4])
-    check(_lib.lib().mhe_conv3x3s2_dgrad_nhwc(B, Ho, Wo, Cout, Cin, dtype_code(dt), _ptr(gy), wp, _ptr(dx), _ptr(residual), _ptr(mask), *ext, int(tile), _stream()),
-          "mhe_conv3x3s2_dgrad_nhwc")
+    launch("mhe_conv3x3s2_dgrad_nhwc", B, Ho, Wo, Cout, Cin, dtype_code(dt), gy, wp, dx, residual, mask, *ext, int(tile))
     return dx
 
 
@@ -851,18 +837,10 @@ def conv1x1_residual_in(x, x2, w, in_scale, in_shift, x2_scale=None, x2_shift=No
         _chk_stats(stats, "conv_res.stats", Cout)
     y = torch.empty(B, H, W, Cout, device=x.device, dtype=dt)
     d = ConvDesc(B, H, W, Cin, Cout, 1, 1, 1, 0, dtype_code(dt), 1, 0, int(tile))
-    if TIMING:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    entry = "mhe_conv1x1_residual_in_quarter_nhwc" if quarter else "mhe_conv1x1_residual_in_nhwc"
-    check(getattr(_lib.lib(), entry)(C.byref(d), _ptr(x), _ptr(x2), _ptr(w), _ptr(y), _ptr(in_scale), _ptr(in_shift),
-                                     _ptr(x2_scale), _ptr(x2_shift), _ptr(a_out), _ptr(stats), _stream()), entry)
-    if TIMING:
-        ev1.record()
-        es = x.element_size()
-        nbytes = es * (2 * x.numel() + y.numel() + w.numel() + (a_out.numel() if a_out is not None else 0))
-        name = "mhe::conv::conv_tail_quarter_kernel" if quarter else _conv_kernel_name(d, dt, 2)
-        KERNEL_TIMES.append((name, 2.0 * B * H * W * Cout * Cin, ev0, ev1, nbytes))
+    with _Timed(lambda: ("mhe::conv::conv_tail_quarter_kernel" if quarter else _conv_kernel_name(d, dt, 2), 2.0 * B * H * W * Cout * Cin,
+                         x.element_size() * (2 * x.numel() + y.numel() + w.numel() + (a_out.numel() if a_out is not None else 0)))):
+        launch("mhe_conv1x1_residual_in_quarter_nhwc" if quarter else "mhe_conv1x1_residual_in_nhwc", C.byref(d), x, x2, w, y, in_scale, in_shift, x2_scale,
+               x2_shift, a_out, stats)
     return y
 
 
@@ -879,14 +857,9 @@ def conv1x1_dgrad_bn_apply(g, y_raw, coef, w_dg, a_out, mask, bn=None, zeros=Non
         zeros = torch.zeros(Cin, device=g.device, dtype=torch.float32)
     _chk(zeros, torch.float32, "dgrad_apply.zeros", (Cin,))
     out = torch.empty(B, H, W, Cout, device=g.device, dtype=dt)
-    by, bmi, bst = bn[0] if bn else (None, None, None)
-    if by is not None:
-        _chk(by, dt, "dgrad_apply.bn_y", out.shape); _chk(bmi, torch.float32, "dgrad_apply.bn_mean_invstd", (2, Cout))
-        _chk_stats(bst, "dgrad_apply.bn_stats", Cout)
+    ext = _bn_consumers(bn, 1, dt, out.shape, Cout, "dgrad_apply")
     d = ConvDesc(B, H, W, Cin, Cout, 1, 1, 1, 0, dtype_code(dt), 0, 0, int(tile))
-    check(_lib.lib().mhe_conv1x1_residual_in_masked_nhwc(C.byref(d), _ptr(g), _ptr(y_raw), _ptr(w_dg), _ptr(out), _ptr(coef[0]), _ptr(coef[2]),
-                                                         _ptr(coef[1]), _ptr(zeros), _ptr(a_out), None, _ptr(mask), _ptr(by), _ptr(bmi), _ptr(bst),
-                                                         _stream()), "mhe_conv1x1_residual_in_masked_nhwc")
+    launch("mhe_conv1x1_residual_in_masked_nhwc", C.byref(d), g, y_raw, w_dg, out, coef[0], coef[2], coef[1], zeros, a_out, None, mask, *ext)
     return out
 
 
@@ -900,15 +873,9 @@ def stem_conv7x7s2(x, w, dtype, stats=None):
     y = torch.empty(B, Ho, Wo, 64, device=x.device, dtype=dtype)
     if stats is not None:
         _chk_stats(stats, "stem.stats", 64)
-    if TIMING:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(_lib.lib().mhe_stem_conv7x7s2(_ptr(x), _ptr(w), _ptr(y), _ptr(stats), B, H, W, dtype_code(dtype), _stream()),
-          "mhe_stem_conv7x7s2")
-    if TIMING:
-        ev1.record()
-        KERNEL_TIMES.append(("mhe::conv::stem_kernel<%s>" % ("float" if dtype == torch.float32 else "unsigned short"),
-                             2.0 * B * Ho * Wo * 64 * 147, ev0, ev1, 4 * x.numel() + y.element_size() * y.numel()))
+    with _Timed(lambda: ("mhe::conv::stem_kernel<%s>" % ("float" if dtype == torch.float32 else "unsigned short"), 2.0 * B * Ho * Wo * 64 * 147,
+                         4 * x.numel() + y.element_size() * y.numel())):
+        launch("mhe_stem_conv7x7s2", x, w, y, stats, B, H, W, dtype_code(dtype))
     return y
 
 
@@ -926,13 +893,8 @@ def stem_conv7x7s2_pool(x, w, bn_gamma, stats=None):
     if stats is not None:
         _chk_stats(stats, "stem_pool.stats", 64)
     y = torch.empty(B, 64, 64, 64, device=x.device, dtype=torch.bfloat16)
-    if TIMING:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(_lib.lib().mhe_stem_conv7x7s2_pool(_ptr(x), _ptr(w), _ptr(bn_gamma), _ptr(y), _ptr(stats), B, H, W, _stream()), "mhe_stem_conv7x7s2_pool")
-    if TIMING:
-        ev1.record()
-        KERNEL_TIMES.append(("mhe::conv::stem_pool_kernel", 2.0 * B * 128 * 128 * 64 * 147, ev0, ev1, 4 * x.numel() + 2 * y.numel()))
+    with _Timed(lambda: ("mhe::conv::stem_pool_kernel", 2.0 * B * 128 * 128 * 64 * 147, 4 * x.numel() + 2 * y.numel())):
+        launch("mhe_stem_conv7x7s2_pool", x, w, bn_gamma, y, stats, B, H, W)
     return y
 
 
@@ -947,13 +909,10 @@ def bn_finalize(stats, gamma, beta, running_mean, running_var, count, momentum=0
     if clear or num_batches_tracked is not None:
         if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or not num_batches_tracked.is_cuda):
             raise _lib.MheError("bn_finalize.num_batches_tracked: int64 device tensor expected")
-        check(_lib.lib().mhe_bn_finalize_step(_ptr(stats), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), _ptr(scale), _ptr(shift),
-                                              _ptr(mi), Cn, float(count), float(momentum), float(eps), int(clear), _ptr(num_batches_tracked), _stream()),
-              "mhe_bn_finalize_step")
+        launch("mhe_bn_finalize_step", stats, gamma, beta, running_mean, running_var, scale, shift, mi, Cn, float(count), float(momentum), float(eps), int(clear),
+               num_batches_tracked)
     else:
-        check(_lib.lib().mhe_bn_finalize(_ptr(stats), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
-                                         _ptr(scale), _ptr(shift), _ptr(mi), Cn, float(count), float(momentum), float(eps), _stream()),
-              "mhe_bn_finalize")
+        launch("mhe_bn_finalize", stats, gamma, beta, running_mean, running_var, scale, shift, mi, Cn, float(count), float(momentum), float(eps))
     return (scale, shift, mi) if want_mean_invstd else (scale, shift)
 
 
@@ -969,8 +928,8 @@ def bn_finalize_pair(unit0, unit1, momentum=0.1, eps=1e-5, clear=True):
         scale = torch.empty(Cn, device=gamma.device, dtype=torch.float32)
         shift = torch.empty_like(scale)
         outs.append((scale, shift))
-        args += [_ptr(stats), _ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar), _ptr(scale), _ptr(shift), None, Cn, float(count), _ptr(nbt)]
-    check(_lib.lib().mhe_bn_finalize_pair_step(*args, float(momentum), float(eps), int(clear), _stream()), "mhe_bn_finalize_pair_step")
+        args += [stats, gamma, beta, rmean, rvar, scale, shift, None, Cn, float(count), nbt]
+    launch("mhe_bn_finalize_pair_step", *args, float(momentum), float(eps), int(clear))
     return outs[0], outs[1]
 
 
@@ -978,9 +937,9 @@ def bn_act(x, scale, shift, res=None, res_scale=None, res_shift=None, relu=True,
     Cn = x.shape[-1]
     P = x.numel() // Cn
     y = out if out is not None else torch.empty_like(x)
-    with _Timed(lambda: "mhe::conv::bn_act_kernel<%s>" % ("float" if x.dtype == torch.float32 else "unsigned short"), 0.0, x.element_size() * x.numel() * (2 + (res is not None))):
-        check(_lib.lib().mhe_bn_act_nhwc(_ptr(x), _ptr(scale), _ptr(shift), _ptr(res), _ptr(res_scale), _ptr(res_shift),
-                                         _ptr(y), P, Cn, int(relu), dtype_code(x.dtype), _stream()), "mhe_bn_act_nhwc")
+    with _Timed(lambda: ("mhe::conv::bn_act_kernel<%s>" % ("float" if x.dtype == torch.float32 else "unsigned short"), 0.0,
+                         x.element_size() * x.numel() * (2 + (res is not None)))):
+        launch("mhe_bn_act_nhwc", x, scale, shift, res, res_scale, res_shift, y, P, Cn, int(relu), dtype_code(x.dtype))
     return y
 
 
@@ -988,15 +947,14 @@ def maxpool3x3s2(x, scale=None, shift=None):
     B, H, W, Cn = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty(B, Ho, Wo, Cn, device=x.device, dtype=x.dtype)
-    check(_lib.lib().mhe_maxpool3x3s2_nhwc(_ptr(x), _ptr(scale), _ptr(shift), _ptr(y), B, H, W, Cn, dtype_code(x.dtype),
-                                           _stream()), "mhe_maxpool3x3s2_nhwc")
+    launch("mhe_maxpool3x3s2_nhwc", x, scale, shift, y, B, H, W, Cn, dtype_code(x.dtype))
     return y
 
 
 def avgpool(x):
     B, H, W, Cn = x.shape
     y = torch.empty(B, Cn, device=x.device, dtype=torch.float32)
-    check(_lib.lib().mhe_avgpool_nhwc(_ptr(x), _ptr(y), B, H * W, Cn, dtype_code(x.dtype), _stream()), "mhe_avgpool_nhwc")
+    launch("mhe_avgpool_nhwc", x, y, B, H * W, Cn, dtype_code(x.dtype))
     return y
 
 
@@ -1009,8 +967,7 @@ def bn_act_avgpool(x, scale, shift, res=None, rscale=None, rshift=None, relu=Tru
     if rscale is not None:
         _chk(rscale, torch.float32, "bn_act_avgpool.rscale", (Cn,)); _chk(rshift, torch.float32, "bn_act_avgpool.rshift", (Cn,))
     y = torch.empty(B, Cn, device=x.device, dtype=torch.float32)
-    check(_lib.lib().mhe_bn_act_avgpool_nhwc(_ptr(x), _ptr(scale), _ptr(shift), _ptr(res), _ptr(rscale), _ptr(rshift), _ptr(y), B, H * W, Cn, int(relu),
-                                             dtype_code(x.dtype), _stream()), "mhe_bn_act_avgpool_nhwc")
+    launch("mhe_bn_act_avgpool_nhwc", x, scale, shift, res, rscale, rshift, y, B, H * W, Cn, int(relu), dtype_code(x.dtype))
     return y
 
 
@@ -1022,24 +979,14 @@ def nchw_to_nhwc(x, dtype=torch.float32, cpad=None):
     Cp = (Cn + ce - 1) // ce * ce if cpad is None else int(cpad)
     y = torch.empty(B, H, W, Cp, device=x.device, dtype=dtype)
     if cpad is None:
-        check(_lib.lib().mhe_nchw_to_nhwc(_ptr(x), _ptr(y), B, Cn, H, W, dtype_code(dtype), _stream()), "mhe_nchw_to_nhwc")
+        launch("mhe_nchw_to_nhwc", x, y, B, Cn, H, W, dtype_code(dtype))
     else:
-        check(_lib.lib().mhe_nchw_to_nhwc_pad(_ptr(x), _ptr(y), B, Cn, Cp, H, W, dtype_code(dtype), _stream()), "mhe_nchw_to_nhwc_pad")
+        launch("mhe_nchw_to_nhwc_pad", x, y, B, Cn, Cp, H, W, dtype_code(dtype))
     return y
 
 
 # ---- train-step (reverse) kernels ---------------------------------------------------------------------
-_WGRAD_WS = {}          # per device: one workspace for the partial slabs of the pixel-range split, grown to the largest layer
-_WGRAD_WS_RETIRED = []  # superseded workspaces stay alive: a captured HIP graph (train.GraphedStep) may have baked their address in
-
-
-def _wgrad_ws(device, need):
-    ws = _WGRAD_WS.get(device)
-    if ws is None or ws.numel() < need:
-        if ws is not None:
-            _WGRAD_WS_RETIRED.append(ws)
-        ws = _WGRAD_WS[device] = torch.empty(need, device=device, dtype=torch.float32)
-    return ws
+_wgrad_ws = _grow_only_workspace()      # the partial slabs of the pixel-range split, grown to the largest layer
 WGRAD_SLABS = True      # False: f32 atomics into dw (the form without a workspace)
 
 
@@ -1058,39 +1005,19 @@ def _wgrad_kernel_name(d, Ho=0, Wo=0, nbatch=1):
     return "mhe::wgrad::wgrad_kernel<%s, %d, %d>" % ("float" if d.dtype == F32 else "unsigned short", bm, bn)
 
 
-class _Timed:
-    """HIP events on the launch stream around one launch, appended to KERNEL_TIMES while TIMING is on (bench.py's live roofline pass)"""
-    def __init__(self, name_fn, flops, nbytes):
-        self.on = TIMING and name_fn is not None
-        if self.on:
-            self.name, self.flops, self.nbytes = name_fn(), flops, nbytes
-            self.ev0, self.ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def __enter__(self):
-        if self.on:
-            self.ev0.record()
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            self.ev1.record()
-            KERNEL_TIMES.append((self.name, self.flops, self.ev0, self.ev1, self.nbytes))
-        return False
-
-
 def _dg_timed(d, x, y, w, residual, mask, mask_bits, bn_ys, tag, xcat=None):
     """tools/train_lines.py: a data-gradient launch under a descriptive name with the bytes it has to move (operand, result, weights,
     residual, the gate - as bits where the kernel reads bits - and the raw tensors of the BatchNorm-reverse sums that are not the gate)"""
     if not (TIMING and TIMING_DG):
-        return _Timed(None, 0.0, 0)
+        return _Timed(None)
     es = x.element_size()
     nb = es * (x.numel() + y.numel() + w.numel() + (residual.numel() if residual is not None else 0) + (xcat.numel() if xcat is not None else 0))
     nb += mask_bits.numel() if mask_bits is not None else es * mask.numel()
     nb += sum(es * b.numel() for b in bn_ys if b is not None and b.data_ptr() != mask.data_ptr())
     name = "dgrad %dx%d s%d %d->%d @%dx%d%s%s bn%d %s" % (d.KH, d.KW, d.stride, d.Cin, d.Cout, y.shape[1], y.shape[2], " +res" if residual is not None else "",
                                                       " half" if d.res_half else "", sum(b is not None for b in bn_ys), tag)
-    t = _Timed(lambda: name, 2.0 * y.shape[0] * y.shape[1] * y.shape[2] * d.Cout * d.KH * d.KW * (d.Cin + (xcat.shape[-1] if xcat is not None else 0)), nb)
-    return t
+    flops = 2.0 * y.shape[0] * y.shape[1] * y.shape[2] * d.Cout * d.KH * d.KW * (d.Cin + (xcat.shape[-1] if xcat is not None else 0))
+    return _Timed(lambda: (name, flops, nb))
 
 
 def conv_wgrad(x, gy, KH, KW, stride, pad, dw, ldw=0):
@@ -1106,12 +1033,12 @@ def conv_wgrad(x, gy, KH, KW, stride, pad, dw, ldw=0):
     L = _lib.lib()
     need = L.mhe_conv_wgrad_workspace_floats(C.byref(d)) if WGRAD_SLABS else 0
     # (timed: the kernel + its slab reducer; algorithmic bytes: both operands once + the gradient)
-    with _Timed(lambda: _wgrad_kernel_name(d), 2.0 * B * Ho * Wo * Cout * KH * KW * Cin, x.element_size() * (x.numel() + gy.numel()) + 4 * Cout * KH * KW * Cin):
+    with _Timed(lambda: (_wgrad_kernel_name(d), 2.0 * B * Ho * Wo * Cout * KH * KW * Cin, x.element_size() * (x.numel() + gy.numel()) + 4 * Cout * KH * KW * Cin)):
         if need:
             ws = _wgrad_ws(x.device, need)
-            check(L.mhe_conv_wgrad_ws_nhwc(C.byref(d), _ptr(x), _ptr(gy), _ptr(dw), int(ldw), _ptr(ws), ws.numel(), _stream()), "mhe_conv_wgrad_ws_nhwc")
+            launch("mhe_conv_wgrad_ws_nhwc", C.byref(d), x, gy, dw, int(ldw), ws, ws.numel())
         else:
-            check(L.mhe_conv_wgrad_nhwc(C.byref(d), _ptr(x), _ptr(gy), _ptr(dw), int(ldw), _stream()), "mhe_conv_wgrad_nhwc")
+            launch("mhe_conv_wgrad_nhwc", C.byref(d), x, gy, dw, int(ldw))
     return dw
 
 
@@ -1151,11 +1078,11 @@ def conv_wgrad_multi(items):
     L = _lib.lib()
     need = L.mhe_conv_wgrad_multi_workspace_floats(C.byref(arr), n)
     ws = _wgrad_ws(items[0][0].device, need) if need else None
-    def name():
+    def what():
         k = _wgrad_kernel_name(arr[0].d)
-        return k.replace("wgrad_dma_kernel", "wgrad_dma_multi_kernel") if n > 1 else k
-    with _Timed(name, flops, nbytes):
-        check(L.mhe_conv_wgrad_multi_nhwc(C.byref(arr), n, _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "mhe_conv_wgrad_multi_nhwc")
+        return k.replace("wgrad_dma_kernel", "wgrad_dma_multi_kernel") if n > 1 else k, flops, nbytes
+    with _Timed(what):
+        launch("mhe_conv_wgrad_multi_nhwc", C.byref(arr), n, ws, ws.numel() if ws is not None else 0)
 
 
 def conv_wgrad_batched(x, gy, dw, dw_batch_stride, nbatch, x_batch_stride=None, gy_batch_stride=None):
@@ -1172,9 +1099,8 @@ def conv_wgrad_batched(x, gy, dw, dw_batch_stride, nbatch, x_batch_stride=None, 
     L = _lib.lib()
     need = L.mhe_conv_wgrad_batched_workspace_floats(C.byref(d), nbatch) if WGRAD_SLABS else 0
     ws = _wgrad_ws(x.device, need) if need else None
-    with _Timed(lambda: _wgrad_kernel_name(d, 0, 0, nbatch), 2.0 * nbatch * R * N * K, nbatch * (2 * R * (K + N) + 4 * N * K)):
-        check(L.mhe_conv_wgrad_batched_nhwc(C.byref(d), nbatch, _ptr(x), xs, _ptr(gy), gs, _ptr(dw), int(dw_batch_stride), 0, _ptr(ws),
-                                            ws.numel() if ws is not None else 0, _stream()), "mhe_conv_wgrad_batched_nhwc")
+    with _Timed(lambda: (_wgrad_kernel_name(d, 0, 0, nbatch), 2.0 * nbatch * R * N * K, nbatch * (2 * R * (K + N) + 4 * N * K))):
+        launch("mhe_conv_wgrad_batched_nhwc", C.byref(d), nbatch, x, xs, gy, gs, dw, int(dw_batch_stride), 0, ws, ws.numel() if ws is not None else 0)
     return dw
 
 
@@ -1193,9 +1119,9 @@ def conv_wgrad_rect(x, gy, KH, KW, stride_h, stride_w, pad_h, pad_w, dw):
     ws = None
     if need:
         ws = _wgrad_ws(x.device, need)
-    with _Timed(lambda: _wgrad_kernel_name(d, Ho, Wo), 2.0 * B * Ho * Wo * Cout * KH * KW * Cin, x.element_size() * (x.numel() + gy.numel()) + 4 * Cout * KH * KW * Cin):
-        check(L.mhe_conv_wgrad_rect_nhwc(C.byref(d), stride_w, pad_w, Ho, Wo, _ptr(x), _ptr(gy), _ptr(dw), 0, _ptr(ws), ws.numel() if ws is not None else 0,
-                                         _stream()), "mhe_conv_wgrad_rect_nhwc")
+    with _Timed(lambda: (_wgrad_kernel_name(d, Ho, Wo), 2.0 * B * Ho * Wo * Cout * KH * KW * Cin,
+                         x.element_size() * (x.numel() + gy.numel()) + 4 * Cout * KH * KW * Cin)):
+        launch("mhe_conv_wgrad_rect_nhwc", C.byref(d), stride_w, pad_w, Ho, Wo, x, gy, dw, 0, ws, ws.numel() if ws is not None else 0)
     return dw
 
 
@@ -1205,8 +1131,7 @@ def linear_wgrad(x, gy, dw):
     return conv_wgrad(x.view(R, 1, 1, K), gy.view(R, 1, 1, gy.shape[1]), 1, 1, 1, 0, dw)
 
 
-_COLSUM_WS = {}
-_COLSUM_WS_RETIRED = []     # (a captured HIP graph may have baked a superseded workspace's address in: keep them alive, as _WGRAD_WS_RETIRED)
+_colsum_ws = _grow_only_workspace()
 
 
 def colsum(rows, out, group_width=0, group_stride=0):
@@ -1219,15 +1144,8 @@ def colsum(rows, out, group_width=0, group_stride=0):
         raise _lib.MheError(f"colsum.out: {out.numel()} floats cannot hold {Cc} columns")
     L = _lib.lib()
     need = L.mhe_colsum_workspace_floats(R, Cc)
-    ws = None
-    if need:
-        ws = _COLSUM_WS.get(rows.device)
-        if ws is None or ws.numel() < need:
-            if ws is not None:
-                _COLSUM_WS_RETIRED.append(ws)
-            ws = _COLSUM_WS[rows.device] = torch.empty(need, device=rows.device, dtype=torch.float32)
-    check(L.mhe_colsum_ws_f32(_ptr(rows), _ptr(out), R, Cc, dtype_code(rows.dtype), int(group_width), int(group_stride), _ptr(ws),
-                              ws.numel() if ws is not None else 0, _stream()), "mhe_colsum_ws_f32")
+    ws = _colsum_ws(rows.device, need) if need else None
+    launch("mhe_colsum_ws_f32", rows, out, R, Cc, dtype_code(rows.dtype), int(group_width), int(group_stride), ws, ws.numel() if ws is not None else 0)
     return out
 
 
@@ -1238,7 +1156,7 @@ def gather(src, idx, dst, idx2=None):
         _chk(idx2, torch.int32, "gather.idx2", idx.shape)
     if dst.numel() != idx.numel() or dst.dtype not in (torch.float32, torch.bfloat16) or not dst.is_contiguous():
         raise ValueError("gather.dst: contiguous f32/bf16 tensor with idx.numel() elements expected")
-    check(_lib.lib().mhe_gather_f32(_ptr(src), _ptr(idx), _ptr(idx2), _ptr(dst), idx.numel(), dtype_code(dst.dtype), _stream()), "mhe_gather_f32")
+    launch("mhe_gather_f32", src, idx, idx2, dst, idx.numel(), dtype_code(dst.dtype))
     return dst
 
 
@@ -1276,14 +1194,14 @@ def gather_affine8(src, base_stride, mask, dst):
     _chk(src, torch.float32, "gather.src"); _chk(base_stride, torch.int32, "gather.base_stride", (n8, 2)); _chk(mask, torch.uint8, "gather.mask", (n8,))
     if dst.numel() != 8 * n8 or dst.dtype != torch.bfloat16 or not dst.is_contiguous():
         raise ValueError("gather_affine8.dst: contiguous bf16 tensor of 8 x mask.numel() elements expected")
-    check(_lib.lib().mhe_gather_affine8_bf16(_ptr(src), _ptr(base_stride), _ptr(mask), _ptr(dst), 8 * n8, _stream()), "mhe_gather_affine8_bf16")
+    launch("mhe_gather_affine8_bf16", src, base_stride, mask, dst, 8 * n8)
     return dst
 
 
 def flow_mask_pad(x, mask_row, out):
     R, dim = x.shape
     _chk(x, torch.float32, "mask_pad.x"); _chk(mask_row, torch.float32, "mask_pad.mask", (dim,)); _chk(out, torch.float32, "mask_pad.out", (R, 64))
-    check(_lib.lib().mhe_flow_mask_pad_f32(_ptr(x), _ptr(mask_row), _ptr(out), R, dim, _stream()), "mhe_flow_mask_pad_f32")
+    launch("mhe_flow_mask_pad_f32", x, mask_row, out, R, dim)
     return out
 
 
@@ -1294,7 +1212,7 @@ def flow_mask_pad_mixed(x, mask_row, out_f32=None, out_bf16=None):
         _chk(out_f32, torch.float32, "mask_pad.out", (R, 64))
     if out_bf16 is not None:
         _chk(out_bf16, torch.bfloat16, "mask_pad.out_bf16", (R, 64))
-    check(_lib.lib().mhe_flow_mask_pad_mixed(_ptr(x), _ptr(mask_row), _ptr(out_f32), _ptr(out_bf16), R, dim, _stream()), "mhe_flow_mask_pad_mixed")
+    launch("mhe_flow_mask_pad_mixed", x, mask_row, out_f32, out_bf16, R, dim)
 
 
 def flow_lrelu_bwd_sum(g, h, N, B, sum_out, sum_stride, out_f32=None, out_bf16=None, slope=0.01, sum_out_t=None):
@@ -1306,29 +1224,28 @@ def flow_lrelu_bwd_sum(g, h, N, B, sum_out, sum_stride, out_f32=None, out_bf16=N
         _chk(out_f32, torch.float32, "lrelu_bwd_sum.out_f32", (R, H))
     if out_bf16 is not None:
         _chk(out_bf16, torch.bfloat16, "lrelu_bwd_sum.out_bf16", (R, H))
-    check(_lib.lib().mhe_flow_lrelu_bwd_sum(_ptr(g), dtype_code(g.dtype), _ptr(h), dtype_code(h.dtype), _ptr(out_f32), _ptr(out_bf16),
-                                            C.c_void_p(sum_out.data_ptr()), int(sum_stride), C.c_void_p(0 if sum_out_t is None else sum_out_t.data_ptr()),
-                                            N, B, H, float(slope), _stream()), "mhe_flow_lrelu_bwd_sum")
+    launch("mhe_flow_lrelu_bwd_sum", g, dtype_code(g.dtype), h, dtype_code(h.dtype), out_f32, out_bf16, sum_out, int(sum_stride),
+           0 if sum_out_t is None else sum_out_t, N, B, H, float(slope))
 
 
 def flow_cond_lrelu(P, cond_slice, cond_stride, B):
     """P[r] = leaky_relu(P[r] + cond_slice[(r % B) * cond_stride : +H]) in place; cond_slice = view starting at the net/layer's column"""
     R, H = P.shape
     _chk(P, torch.float32, "cond_lrelu.P")
-    check(_lib.lib().mhe_flow_cond_lrelu_f32(_ptr(P), cond_slice.data_ptr(), int(cond_stride), R, B, H, _stream()), "mhe_flow_cond_lrelu_f32")
+    launch("mhe_flow_cond_lrelu_f32", P, cond_slice, int(cond_stride), R, B, H)
     return P
 
 
 def flow_lrelu_bwd(G, Hact, slope=0.01):
     _chk(G, torch.float32, "lrelu_bwd.G"); _chk(Hact, torch.float32, "lrelu_bwd.H", G.shape)
-    check(_lib.lib().mhe_flow_lrelu_bwd_f32(_ptr(G), _ptr(Hact), G.numel(), float(slope), _stream()), "mhe_flow_lrelu_bwd_f32")
+    launch("mhe_flow_lrelu_bwd_f32", G, Hact, G.numel(), float(slope))
     return G
 
 
 def add(a, b, out=None):
     _chk(a, torch.float32, "add.a"); _chk(b, torch.float32, "add.b", a.shape)
     out = a if out is None else out
-    check(_lib.lib().mhe_add_f32(_ptr(a), _ptr(b), _ptr(out), a.numel(), _stream()), "mhe_add_f32")
+    launch("mhe_add_f32", a, b, out, a.numel())
     return out
 
 
@@ -1344,10 +1261,8 @@ def flow_couple_bwd(x_out, Os, Ot, mask_row, g_out, g_log_p, q_weight, B, x_in, 
     # the kernel's own column sums are f32 atomics from every 64-row workgroup: order-dependent beyond one workgroup - there the sums are
     # taken from the written GOs / GOt rows in a fixed order instead (two more launches on a fallback path)
     in_kernel = db_s is not None and R <= 64
-    check(_lib.lib().mhe_flow_couple_bwd_mixed(_ptr(x_out), _ptr(Os), _ptr(Ot), _ptr(mask_row), _ptr(g_out), _ptr(g_log_p),
-                                               float(q_weight), _ptr(x_in), _ptr(GOs), _ptr(GOt), _ptr(g_part), _ptr(GOs_bf16), _ptr(GOt_bf16),
-                                               _ptr(db_s if in_kernel else None), _ptr(db_t if in_kernel else None), R, B, dim, _stream()),
-          "mhe_flow_couple_bwd_mixed")
+    launch("mhe_flow_couple_bwd_mixed", x_out, Os, Ot, mask_row, g_out, g_log_p, float(q_weight), x_in, GOs, GOt, g_part, GOs_bf16, GOt_bf16,
+           db_s if in_kernel else None, db_t if in_kernel else None, R, B, dim)
     if db_s is not None and not in_kernel:
         colsum(GOs, db_s); colsum(GOt, db_t)
 
@@ -1399,10 +1314,8 @@ def flow_reverse_chain(x_out, g_x, g_logp, q_weight, mask, o_pre, sign_bits, w2F
     rows = _DB2_ROWS.get((x_out.device, B, nets))
     if rows is None:
         rows = _DB2_ROWS[(x_out.device, B, nets)] = torch.empty(B, nets * 64, device=x_out.device, dtype=torch.float32)
-    check(_lib.lib().mhe_flow_reverse_chain_bf16(_ptr(x_out), _ptr(g_x), _ptr(g_logp), float(q_weight), _ptr(mask), _ptr(o_pre), _ptr(sign_bits), _ptr(w2F),
-                                                 _ptr(w1F), _ptr(w0F), int(w_net_stride), _ptr(GOb), _ptr(G2b), _ptr(G1b), _ptr(XPb), _ptr(Gc),
-                                                 Gc.shape[1], _ptr(rows), _ptr(z0), R, B, dim, hidden, nets // 2, _stream()),
-          "mhe_flow_reverse_chain_bf16")
+    launch("mhe_flow_reverse_chain_bf16", x_out, g_x, g_logp, float(q_weight), mask, o_pre, sign_bits, w2F, w1F, w0F, int(w_net_stride), GOb, G2b, G1b, XPb, Gc,
+           Gc.shape[1], rows, z0, R, B, dim, hidden, nets // 2)
     # db2 (+ net * db_net_stride) += the sum over images of the kernel's per-image rows, in a fixed order
     colsum(rows, db2, group_width=64, group_stride=db_net_stride)
 
@@ -1418,14 +1331,13 @@ def pack_transpose_bf16(src, out=None, outT=None, want_rows=True):
     if out is not None:
         _chk(out, torch.bfloat16, "pack_transpose.out", (R, Cc))
     _chk(outT, torch.bfloat16, "pack_transpose.outT", (Cc, R))
-    check(_lib.lib().mhe_pack_transpose_bf16(_ptr(src), src.stride(0), _ptr(out), _ptr(outT), R, Cc, _stream()), "mhe_pack_transpose_bf16")
+    launch("mhe_pack_transpose_bf16", src, src.stride(0), out, outT, R, Cc)
     return out, outT
 
 
 def flow_couple_accum(g_part, GXs, GXt, mask_row, g_in):
     R, dim = g_part.shape
-    check(_lib.lib().mhe_flow_couple_accum_f32(_ptr(g_part), _ptr(GXs), _ptr(GXt), _ptr(mask_row), _ptr(g_in), R, dim, _stream()),
-          "mhe_flow_couple_accum_f32")
+    launch("mhe_flow_couple_accum_f32", g_part, GXs, GXt, mask_row, g_in, R, dim)
     return g_in
 
 
@@ -1433,7 +1345,7 @@ def bn_mean_invstd(stats, count, eps=1e-5):
     Cc = stats.shape[-1]
     _chk_stats(stats, "bn_mean_invstd.stats", Cc)
     mi = torch.empty(2, Cc, device=stats.device, dtype=torch.float32)
-    check(_lib.lib().mhe_bn_mean_invstd(_ptr(stats), _ptr(mi), Cc, float(count), float(eps), _stream()), "mhe_bn_mean_invstd")
+    launch("mhe_bn_mean_invstd", stats, mi, Cc, float(count), float(eps))
     return mi
 
 
@@ -1448,17 +1360,17 @@ def bn_backward(g, a, y, mean_invstd, gamma, stats, dgamma, dbeta, want_masked=F
         _chk(a, dt, "bn_bwd.a", y.shape)
     _chk_stats(stats, "bn_bwd.stats", Cc); _chk(mean_invstd, torch.float32, "bn_bwd.mean_invstd", (2, Cc))
     _chk(gamma, torch.float32, "bn_bwd.gamma", (Cc,)); _chk(dgamma, torch.float32, "bn_bwd.dgamma", (Cc,)); _chk(dbeta, torch.float32, "bn_bwd.dbeta", (Cc,))
-    L = _lib.lib()
     if not reduced:
-        check(L.mhe_bn_bwd_reduce_nhwc(_ptr(g), _ptr(a), _ptr(y), _ptr(mean_invstd), _ptr(stats), P, Cc, dtype_code(dt), _stream()), "mhe_bn_bwd_reduce_nhwc")
+        launch("mhe_bn_bwd_reduce_nhwc", g, a, y, mean_invstd, stats, P, Cc, dtype_code(dt))
     coef = torch.empty(3, Cc, device=y.device, dtype=torch.float32)
-    check(L.mhe_bn_bwd_finalize(_ptr(stats), _ptr(gamma), _ptr(mean_invstd), _ptr(dgamma), _ptr(dbeta), _ptr(coef), Cc, float(P), _stream()), "mhe_bn_bwd_finalize")
+    launch("mhe_bn_bwd_finalize", stats, gamma, mean_invstd, dgamma, dbeta, coef, Cc, float(P))
     if coef_only:              # the consumer applies gy = k2 g + k1 y + k0 itself (conv1x1_dgrad_bn_apply)
         return coef
     gy = out if out is not None else torch.empty_like(y)
     gm = torch.empty_like(y) if want_masked else None
-    with _Timed(lambda: "mhe::tb::bn_bwd_apply_wide_kernel<%s, %d>" % ("float" if dt == torch.float32 else "unsigned short", 4 if y.numel() * y.element_size() <= (80 << 20) else 1), 0.0, y.element_size() * y.numel() * (3 + (a is not None) + (gm is not None))):
-        check(L.mhe_bn_bwd_apply_nhwc(_ptr(g), _ptr(a), _ptr(y), _ptr(coef), _ptr(gy), _ptr(gm), P, Cc, dtype_code(dt), _stream()), "mhe_bn_bwd_apply_nhwc")
+    with _Timed(lambda: ("mhe::tb::bn_bwd_apply_wide_kernel<%s, %d>" % ("float" if dt == torch.float32 else "unsigned short", 4 if y.numel() * y.element_size() <= (80 << 20) else 1),
+                         0.0, y.element_size() * y.numel() * (3 + (a is not None) + (gm is not None)))):
+        launch("mhe_bn_bwd_apply_nhwc", g, a, y, coef, gy, gm, P, Cc, dtype_code(dt))
     return (gy, gm) if want_masked else gy
 
 
@@ -1468,8 +1380,7 @@ def bn_bwd_coef(stats, gamma, mean_invstd, dgamma, dbeta, count):
     _chk_stats(stats, "bn_bwd.stats", Cc); _chk(mean_invstd, torch.float32, "bn_bwd.mean_invstd", (2, Cc))
     _chk(gamma, torch.float32, "bn_bwd.gamma", (Cc,)); _chk(dgamma, torch.float32, "bn_bwd.dgamma", (Cc,)); _chk(dbeta, torch.float32, "bn_bwd.dbeta", (Cc,))
     coef = torch.empty(3, Cc, device=stats.device, dtype=torch.float32)
-    check(_lib.lib().mhe_bn_bwd_finalize(_ptr(stats), _ptr(gamma), _ptr(mean_invstd), _ptr(dgamma), _ptr(dbeta), _ptr(coef), Cc, float(count), _stream()),
-          "mhe_bn_bwd_finalize")
+    launch("mhe_bn_bwd_finalize", stats, gamma, mean_invstd, dgamma, dbeta, coef, Cc, float(count))
     return coef
 
 
@@ -1482,8 +1393,7 @@ def maxpool3x3s2_idx_win(x, scale, shift):
     xwin = torch.empty_like(y)
     idx = torch.empty(B, Ho, Wo, Cc, device=x.device, dtype=torch.uint8)
     _chk(x, x.dtype, "maxpool_idx.x"); _chk(scale, torch.float32, "maxpool_idx.scale", (Cc,)); _chk(shift, torch.float32, "maxpool_idx.shift", (Cc,))
-    check(_lib.lib().mhe_maxpool3x3s2_idx_affine_win_nhwc(_ptr(x), _ptr(scale), _ptr(shift), _ptr(y), _ptr(idx), _ptr(xwin), B, H, W, Cc, dtype_code(x.dtype),
-                                                          _stream()), "mhe_maxpool3x3s2_idx_affine_win_nhwc")
+    launch("mhe_maxpool3x3s2_idx_affine_win_nhwc", x, scale, shift, y, idx, xwin, B, H, W, Cc, dtype_code(x.dtype))
     return y, idx, xwin
 
 
@@ -1494,8 +1404,7 @@ def pooled_bn_sums(g, pooled, xwin, mean_invstd, stats):
     dt = g.dtype
     _chk(g, dt, "pooled_bn_sums.g"); _chk(pooled, dt, "pooled_bn_sums.pooled", g.shape); _chk(xwin, dt, "pooled_bn_sums.xwin", g.shape)
     _chk(mean_invstd, torch.float32, "pooled_bn_sums.mean_invstd", (2, Cc)); _chk_stats(stats, "pooled_bn_sums.stats", Cc)
-    check(_lib.lib().mhe_pooled_bn_sums_nhwc(_ptr(g), _ptr(pooled), _ptr(xwin), _ptr(mean_invstd), _ptr(stats), g.numel() // Cc, Cc, dtype_code(dt), _stream()),
-          "mhe_pooled_bn_sums_nhwc")
+    launch("mhe_pooled_bn_sums_nhwc", g, pooled, xwin, mean_invstd, stats, g.numel() // Cc, Cc, dtype_code(dt))
     return stats
 
 
@@ -1509,10 +1418,9 @@ def maxpool3x3s2_idx(x, scale=None, shift=None):
     _chk(x, x.dtype, "maxpool_idx.x")
     if scale is not None:
         _chk(scale, torch.float32, "maxpool_idx.scale", (Cc,)); _chk(shift, torch.float32, "maxpool_idx.shift", (Cc,))
-        check(_lib.lib().mhe_maxpool3x3s2_idx_affine_nhwc(_ptr(x), _ptr(scale), _ptr(shift), _ptr(y), _ptr(idx), B, H, W, Cc, dtype_code(x.dtype), _stream()),
-              "mhe_maxpool3x3s2_idx_affine_nhwc")
+        launch("mhe_maxpool3x3s2_idx_affine_nhwc", x, scale, shift, y, idx, B, H, W, Cc, dtype_code(x.dtype))
         return y, idx
-    check(_lib.lib().mhe_maxpool3x3s2_idx_nhwc(_ptr(x), _ptr(y), _ptr(idx), B, H, W, Cc, dtype_code(x.dtype), _stream()), "mhe_maxpool3x3s2_idx_nhwc")
+    launch("mhe_maxpool3x3s2_idx_nhwc", x, y, idx, B, H, W, Cc, dtype_code(x.dtype))
     return y, idx
 
 
@@ -1529,8 +1437,7 @@ def maxpool3x3s2_bwd_bn(gy, idx, y, scale, shift, mean_invstd, stats, want_gx=Tr
     _chk(scale, torch.float32, "maxpool_bwd_bn.scale", (Cc,)); _chk(shift, torch.float32, "maxpool_bwd_bn.shift", (Cc,))
     _chk(mean_invstd, torch.float32, "maxpool_bwd_bn.mean_invstd", (2, Cc)); _chk_stats(stats, "maxpool_bwd_bn.stats", Cc)
     gx = torch.empty_like(y) if want_gx else None
-    check(_lib.lib().mhe_maxpool3x3s2_bwd_bn_nhwc(_ptr(gy), _ptr(idx), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean_invstd), _ptr(stats), _ptr(gx),
-                                                  B, H, W, Cc, dtype_code(dt), _stream()), "mhe_maxpool3x3s2_bwd_bn_nhwc")
+    launch("mhe_maxpool3x3s2_bwd_bn_nhwc", gy, idx, y, scale, shift, mean_invstd, stats, gx, B, H, W, Cc, dtype_code(dt))
     return gx
 
 
@@ -1544,8 +1451,7 @@ def maxpool3x3s2_bwd_bn_apply(gy, idx, y, scale, shift, mean_invstd, coef):
     _chk(scale, torch.float32, "maxpool_bwd_apply.scale", (Cc,)); _chk(shift, torch.float32, "maxpool_bwd_apply.shift", (Cc,))
     _chk(mean_invstd, torch.float32, "maxpool_bwd_apply.mean_invstd", (2, Cc)); _chk(coef, torch.float32, "maxpool_bwd_apply.coef", (3, Cc))
     out = torch.empty_like(y)
-    check(_lib.lib().mhe_maxpool3x3s2_bwd_bn_apply_nhwc(_ptr(gy), _ptr(idx), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean_invstd), _ptr(coef), _ptr(out),
-                                                        B, H, W, Cc, dtype_code(dt), _stream()), "mhe_maxpool3x3s2_bwd_bn_apply_nhwc")
+    launch("mhe_maxpool3x3s2_bwd_bn_apply_nhwc", gy, idx, y, scale, shift, mean_invstd, coef, out, B, H, W, Cc, dtype_code(dt))
     return out
 
 
@@ -1553,7 +1459,7 @@ def maxpool3x3s2_bwd(gy, idx, H, W):
     B, Ho, Wo, Cc = gy.shape
     _chk(gy, gy.dtype, "maxpool_bwd.gy"); _chk(idx, torch.uint8, "maxpool_bwd.idx", gy.shape)
     gx = torch.empty(B, H, W, Cc, device=gy.device, dtype=gy.dtype)
-    check(_lib.lib().mhe_maxpool3x3s2_bwd_nhwc(_ptr(gy), _ptr(idx), _ptr(gx), B, H, W, Cc, dtype_code(gy.dtype), _stream()), "mhe_maxpool3x3s2_bwd_nhwc")
+    launch("mhe_maxpool3x3s2_bwd_nhwc", gy, idx, gx, B, H, W, Cc, dtype_code(gy.dtype))
     return gx
 
 
@@ -1566,7 +1472,7 @@ def avgpool_bwd(g, HW, dtype, mask=None):
         _chk(mask, dtype, "avgpool_bwd.mask")
         if mask.numel() != gx.numel():
             raise ValueError("avgpool_bwd.mask: wrong size")
-    check(_lib.lib().mhe_avgpool_bwd_nhwc(_ptr(g), _ptr(mask), _ptr(gx), B, HW, Cc, dtype_code(dtype), _stream()), "mhe_avgpool_bwd_nhwc")
+    launch("mhe_avgpool_bwd_nhwc", g, mask, gx, B, HW, Cc, dtype_code(dtype))
     return gx
 
 
@@ -1579,7 +1485,7 @@ def upsample2(g, H, W, base=None):
     if base is not None:
         _chk(base, g.dtype, "upsample2.base", (B, H, W, Cc))
     out = torch.empty(B, H, W, Cc, device=g.device, dtype=g.dtype)
-    check(_lib.lib().mhe_upsample2_nhwc(_ptr(g), _ptr(base), _ptr(out), B, H, W, Cc, dtype_code(g.dtype), _stream()), "mhe_upsample2_nhwc")
+    launch("mhe_upsample2_nhwc", g, base, out, B, H, W, Cc, dtype_code(g.dtype))
     return out
 
 
@@ -1592,21 +1498,20 @@ def sqnorm(g, out):
     ws = _SQ_WS.get(g.device)
     if ws is None:
         ws = _SQ_WS[g.device] = torch.empty(_lib.lib().mhe_sqnorm_workspace_floats(), device=g.device, dtype=torch.float32)
-    check(_lib.lib().mhe_sqnorm_f32(_ptr(g), g.numel(), _ptr(ws), _ptr(out), _stream()), "mhe_sqnorm_f32")
+    launch("mhe_sqnorm_f32", g, g.numel(), ws, out)
     return out
 
 
 def train_tick(step, sq):
     _chk(step, torch.int32, "tick.step", (1,)); _chk(sq, torch.float32, "tick.sqnorm", (1,))
-    check(_lib.lib().mhe_train_tick(_ptr(step), _ptr(sq), _stream()), "mhe_train_tick")
+    launch("mhe_train_tick", step, sq)
 
 
 def adam_step(p, g, m, v, sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, max_norm=1.0, grad_scale=1.0):
     n = p.numel()
     for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _chk(t, torch.float32, "adam." + nm, (n,))
-    check(_lib.lib().mhe_adam_step_f32(_ptr(p), _ptr(g), _ptr(m), _ptr(v), n, _ptr(sq), _ptr(step), float(lr), float(beta1), float(beta2),
-                                       float(eps), float(max_norm), float(grad_scale), _stream()), "mhe_adam_step_f32")
+    launch("mhe_adam_step_f32", p, g, m, v, n, sq, step, float(lr), float(beta1), float(beta2), float(eps), float(max_norm), float(grad_scale))
 
 
 def flow_cond_lrelu_mixed(pre, cond_slice, cond_stride, B, out_f32=None, out_bf16=None):
@@ -1617,14 +1522,12 @@ def flow_cond_lrelu_mixed(pre, cond_slice, cond_stride, B, out_f32=None, out_bf1
         _chk(out_f32, torch.float32, "cond_lrelu_mixed.out_f32", (R, H))
     if out_bf16 is not None:
         _chk(out_bf16, torch.bfloat16, "cond_lrelu_mixed.out_bf16", (R, H))
-    check(_lib.lib().mhe_flow_cond_lrelu_mixed(_ptr(pre), dtype_code(pre.dtype), cond_slice.data_ptr(), int(cond_stride), _ptr(out_f32),
-                                               _ptr(out_bf16), R, B, H, _stream()), "mhe_flow_cond_lrelu_mixed")
+    launch("mhe_flow_cond_lrelu_mixed", pre, dtype_code(pre.dtype), cond_slice, int(cond_stride), out_f32, out_bf16, R, B, H)
 
 
 def flow_lrelu_bwd_mixed(g, h, out_f32=None, out_bf16=None, slope=0.01):
     _chk(g, g.dtype, "lrelu_bwd_mixed.g"); _chk(h, h.dtype, "lrelu_bwd_mixed.h", g.shape)
-    check(_lib.lib().mhe_flow_lrelu_bwd_mixed(_ptr(g), dtype_code(g.dtype), _ptr(h), dtype_code(h.dtype), _ptr(out_f32), _ptr(out_bf16),
-                                              g.numel(), float(slope), _stream()), "mhe_flow_lrelu_bwd_mixed")
+    launch("mhe_flow_lrelu_bwd_mixed", g, dtype_code(g.dtype), h, dtype_code(h.dtype), out_f32, out_bf16, g.numel(), float(slope))
 
 
 # ---- conditional Glow: the ActNorm + LU re-parameterisation on the device (csrc/glow_affine.hip) ---------------------------------------
@@ -1637,15 +1540,13 @@ def glow_affine(ptr_table, layers, features, eps, out=None):
         out.update({k: torch.zeros(layers, 64, device=dev) for k in ("c", "cinv")})
         out["const_parts"] = torch.zeros(layers, device=dev)
         out["ws"] = torch.zeros(int(_lib.lib().mhe_glow_affine_workspace_doubles(layers, features)), device=dev, dtype=torch.float64)
-    check(_lib.lib().mhe_glow_affine_f64(_ptr(ptr_table), layers, features, float(eps), _ptr(out["A"]), _ptr(out["c"]), _ptr(out["Ainv"]),
-                                         _ptr(out["AinvT"]), _ptr(out["cinv"]), _ptr(out["const_parts"]), _ptr(out["ws"]), _stream()), "mhe_glow_affine_f64")
+    launch("mhe_glow_affine_f64", ptr_table, layers, features, float(eps), out["A"], out["c"], out["Ainv"], out["AinvT"], out["cinv"], out["const_parts"], out["ws"])
     return out
 
 
 def glow_reparam_bwd(g_ainv_ptrs, g_cinv_ptrs, g_logp, layers, features, ws, grad_ptrs, q_sign=-1.0):
     """gradients of every layer's six small tensors, written through grad_ptrs (int64 [layers, 6] addresses): mhe_glow_reparam_bwd_f64"""
-    check(_lib.lib().mhe_glow_reparam_bwd_f64(_ptr(g_ainv_ptrs), _ptr(g_cinv_ptrs), _ptr(g_logp), 0 if g_logp is None else g_logp.numel(), float(q_sign),
-                                              layers, features, _ptr(ws), _ptr(grad_ptrs), _stream()), "mhe_glow_reparam_bwd_f64")
+    launch("mhe_glow_reparam_bwd_f64", g_ainv_ptrs, g_cinv_ptrs, g_logp, 0 if g_logp is None else g_logp.numel(), float(q_sign), layers, features, ws, grad_ptrs)
 
 
 def glow_affine_wide(ptr_table, layers, features, eps, out=None):
@@ -1657,9 +1558,8 @@ def glow_affine_wide(ptr_table, layers, features, eps, out=None):
         out.update({k: torch.empty(layers, Dp, device=dev) for k in ("c", "cinv")})
         out["const_parts"] = torch.empty(layers, device=dev)
         out["ws"] = torch.empty(int(_lib.lib().mhe_glow_affine_wide_workspace_doubles(layers, features)), device=dev, dtype=torch.float64)
-    check(_lib.lib().mhe_glow_affine_wide_f64(_ptr(ptr_table), layers, features, float(eps), _ptr(out["A"]), _ptr(out["c"]), _ptr(out["Ainv"]),
-                                              _ptr(out["AinvT"]), _ptr(out["cinv"]), _ptr(out["const_parts"]), _ptr(out["ws"]), _stream()),
-          "mhe_glow_affine_wide_f64")
+    launch("mhe_glow_affine_wide_f64", ptr_table, layers, features, float(eps), out["A"], out["c"], out["Ainv"], out["AinvT"], out["cinv"], out["const_parts"],
+           out["ws"])
     return out
 
 
@@ -1672,8 +1572,7 @@ def glow_affine_wide_bwd(g_ainv, g_cinv, g_logq, layers, features, ws):
         _chk(g_logq, torch.float32, "affine_wide_bwd.g_logq")
     L = _lib.lib()
     out = torch.empty(layers, int(L.mhe_glow_affine_wide_grad_doubles(layers, features)) // layers, device=g_ainv.device, dtype=torch.float64)
-    check(L.mhe_glow_affine_wide_bwd_f64(_ptr(g_ainv), _ptr(g_cinv), _ptr(g_logq), 0 if g_logq is None else g_logq.numel(), layers, features,
-                                         _ptr(ws), _ptr(out), _stream()), "mhe_glow_affine_wide_bwd_f64")
+    launch("mhe_glow_affine_wide_bwd_f64", g_ainv, g_cinv, g_logq, 0 if g_logq is None else g_logq.numel(), layers, features, ws, out)
     return out
 
 
@@ -1685,8 +1584,7 @@ def glow_coupling_inv_bwd_wide(v, prm, g_y, g_logq, dim, first, n_transform):
     if g_logq is not None:
         _chk(g_logq, torch.float32, "coupling_bwd.g_logq", (R,))
     g_v, g_prm = torch.empty_like(v), torch.empty_like(prm)
-    check(_lib.lib().mhe_glow_coupling_inv_bwd_wide_f32(_ptr(v), _ptr(prm), _ptr(g_y), _ptr(g_logq), _ptr(g_v), _ptr(g_prm), R, dim, first, n_transform,
-                                                        ld, ldp, _stream()), "mhe_glow_coupling_inv_bwd_wide_f32")
+    launch("mhe_glow_coupling_inv_bwd_wide_f32", v, prm, g_y, g_logq, g_v, g_prm, R, dim, first, n_transform, ld, ldp)
     return g_v, g_prm
 
 
@@ -1699,8 +1597,7 @@ def glow_coupling_fwd_bwd(v, prm, g_y, g_logp, dim, first, n_transform):
     if g_logp is not None:
         _chk(g_logp, torch.float32, "coupling_fwd_bwd.g_logp", (R,))
     g_v, g_prm = torch.empty_like(v), torch.empty_like(prm)
-    check(_lib.lib().mhe_glow_coupling_fwd_bwd_f32(_ptr(v), _ptr(prm), _ptr(g_y), _ptr(g_logp), _ptr(g_v), _ptr(g_prm), R, dim, first, n_transform,
-                                                   ld, ldp, _stream()), "mhe_glow_coupling_fwd_bwd_f32")
+    launch("mhe_glow_coupling_fwd_bwd_f32", v, prm, g_y, g_logp, g_v, g_prm, R, dim, first, n_transform, ld, ldp)
     return g_v, g_prm
 
 
@@ -1713,7 +1610,7 @@ def glow_base_density_bwd(z_padded, g_z, g_logp, dim):
     if g_logp is not None:
         _chk(g_logp, torch.float32, "base_density_bwd.g_logp", (R,))
     g_y = torch.empty_like(z_padded)
-    check(_lib.lib().mhe_glow_base_density_bwd_f32(_ptr(z_padded), _ptr(g_z), _ptr(g_logp), _ptr(g_y), R, dim, ld, _stream()), "mhe_glow_base_density_bwd_f32")
+    launch("mhe_glow_base_density_bwd_f32", z_padded, g_z, g_logp, g_y, R, dim, ld)
     return g_y
 
 
@@ -1731,11 +1628,9 @@ def glow_affine_density_bwd(g_a, g_c, g_logp, layers, features, ws):
     n = 0 if g_logp is None else g_logp.numel()
     out = torch.empty(layers, int(L.mhe_glow_affine_wide_grad_doubles(layers, features)) // layers, device=g_a.device, dtype=torch.float64)
     if features <= 64 and ws.numel() == L.mhe_glow_affine_workspace_doubles(layers, features):
-        check(L.mhe_glow_affine_density_bwd_f64(_ptr(g_a), _ptr(g_c), _ptr(g_logp), n, layers, features, _ptr(ws), _ptr(out), _stream()),
-              "mhe_glow_affine_density_bwd_f64")
+        launch("mhe_glow_affine_density_bwd_f64", g_a, g_c, g_logp, n, layers, features, ws, out)
     elif ws.numel() == L.mhe_glow_affine_wide_workspace_doubles(layers, features):
-        check(L.mhe_glow_affine_wide_density_bwd_f64(_ptr(g_a), _ptr(g_c), _ptr(g_logp), n, layers, features, _ptr(ws), _ptr(out), _stream()),
-              "mhe_glow_affine_wide_density_bwd_f64")
+        launch("mhe_glow_affine_wide_density_bwd_f64", g_a, g_c, g_logp, n, layers, features, ws, out)
     else:
         raise _lib.MheError(f"affine_density_bwd.ws: {ws.numel()} doubles is the workspace of neither glow_affine nor glow_affine_wide at "
                             f"{layers} layers x {features} features")
@@ -1748,8 +1643,7 @@ def sum_row_blocks(rows, groups, N, out=None, out_stride=0, accumulate=False):
     _chk(rows, torch.float32, "sum_row_blocks.rows", (groups * N, Cc))
     if out is None:
         out = torch.empty(groups, Cc, device=rows.device, dtype=torch.float32)
-    check(_lib.lib().mhe_sum_row_blocks_f32(_ptr(rows), C.c_void_p(out.data_ptr()), groups, N, Cc, int(out_stride or Cc), int(accumulate), _stream()),
-          "mhe_sum_row_blocks_f32")
+    launch("mhe_sum_row_blocks_f32", rows, out, groups, N, Cc, int(out_stride or Cc), int(accumulate))
     return out
 
 
@@ -1757,8 +1651,7 @@ def glow_finish(z_padded, v_padded, logdet, R, dim, inverse, const_parts, want_o
     """(out [R,dim] | None, log_prob [R]) with the log-determinant constant summed from the device-resident per-layer parts"""
     out = torch.empty(R, dim, device=z_padded.device) if want_out else None
     logp = torch.empty(R, device=z_padded.device)
-    check(_lib.lib().mhe_glow_finish_dev_f32(_ptr(z_padded), _ptr(v_padded), _ptr(logdet), _ptr(out), _ptr(logp), R, dim, -1.0 if inverse else 1.0,
-                                             _ptr(const_parts), const_parts.numel(), _stream()), "mhe_glow_finish_dev_f32")
+    launch("mhe_glow_finish_dev_f32", z_padded, v_padded, logdet, out, logp, R, dim, -1.0 if inverse else 1.0, const_parts, const_parts.numel())
     return out, logp
 
 
@@ -1767,7 +1660,7 @@ def dropout_bits(n, p, device, state=None):
     """keep bits of n elements (uint8 [n / 8], the format dropout_ writes / applies), drawn on the device: mhe_dropout_bits"""
     bits = torch.empty(n // 8, device=device, dtype=torch.uint8)
     st = state if state is not None else rng_state(device)
-    check(_lib.lib().mhe_dropout_bits(_ptr(bits), n, float(p), _ptr(st), _stream()), "mhe_dropout_bits")
+    launch("mhe_dropout_bits", bits, n, float(p), st)
     return bits
 
 
@@ -1826,12 +1719,9 @@ def glow_layers(noise, ctab, fp, aff, drop_bits, p_drop, N, B, dim, row_n, row_b
                            ("tb", torch.bfloat16, (L, 2, R, 512)), ("t2", torch.bfloat16, (L, 2, R, 512)), ("t3", torch.bfloat16, (L, 2, R, 512)),
                            ("hf", torch.bfloat16, (L, R, 512))):
             _chk(tape[k], dt, "glow_layers.tape." + k, shp)
-    check(_lib.lib().mhe_glow_layers_bf16(_ptr(noise), _ptr(ctab), ctab.shape[1], _ptr(fp["wxF"]), _ptr(fp["w0F"]), _ptr(fp["w1F"]), _ptr(fp["wsF"]),
-                                          _ptr(fp["wuF"]), _ptr(fp["b0"]), _ptr(fp["b1"]), _ptr(fp["bs"]), _ptr(fp["bu"]), _ptr(aff["AinvT"]),
-                                          _ptr(aff["cinv"]), _ptr(aff["const_parts"]), _ptr(drop_bits), float(p_drop), _ptr(out), _ptr(logq),
-                                          _ptr(t.get("v")), _ptr(t.get("y")), _ptr(t.get("prm")), _ptr(t.get("tb")), _ptr(t.get("t2")), _ptr(t.get("t3")),
-                                          _ptr(t.get("hf")), _ptr(t.get("prmc")), _ptr(t.get("vb")), _ptr(t.get("bits")), N, B, dim, 512, L, 2, row_n, row_b,
-                                          _stream()), "mhe_glow_layers_bf16")
+    launch("mhe_glow_layers_bf16", noise, ctab, ctab.shape[1], fp["wxF"], fp["w0F"], fp["w1F"], fp["wsF"], fp["wuF"], fp["b0"], fp["b1"], fp["bs"], fp["bu"],
+           aff["AinvT"], aff["cinv"], aff["const_parts"], drop_bits, float(p_drop), out, logq, t.get("v"), t.get("y"), t.get("prm"), t.get("tb"), t.get("t2"),
+           t.get("t3"), t.get("hf"), t.get("prmc"), t.get("vb"), t.get("bits"), N, B, dim, 512, L, 2, row_n, row_b)
     return out, logq
 
 
@@ -1855,9 +1745,7 @@ def glow_reverse_chain(g_x, g_logp, q_weight, tape, ctab, fp, aff, p_drop, out, 
         _chk(out[k], dt, "glow_reverse_chain.out." + k, shp)
     for k in ("wsT", "wuT", "w1T", "w0T", "wxT"):
         _chk(fp[k], torch.bfloat16, "glow_reverse_chain." + k)
-    check(_lib.lib().mhe_glow_reverse_chain_bf16(_ptr(g_x), _ptr(g_logp), float(q_weight), _ptr(tape["v"]), _ptr(tape["prmc"]), _ptr(tape["t3"]),
-                                                 _ptr(tape["bits"]), _ptr(ctab), ctab.shape[1], _ptr(fp["wsT"]), _ptr(fp["wuT"]), _ptr(fp["w1T"]),
-                                                 _ptr(fp["w0T"]), _ptr(fp["wxT"]), _ptr(aff["Ainv"]), float(p_drop), _ptr(out["gv"]), _ptr(out["gpc"]),
-                                                 _ptr(out["gt3"]), _ptr(out["gt2"]), _ptr(out["gh0"]), _ptr(out["gct"]), _ptr(out["bsum"]),
-                                                 _ptr(out["bfsum"]), R, B, dim, 512, L, 2, _stream()), "mhe_glow_reverse_chain_bf16")
+    launch("mhe_glow_reverse_chain_bf16", g_x, g_logp, float(q_weight), tape["v"], tape["prmc"], tape["t3"], tape["bits"], ctab, ctab.shape[1], fp["wsT"], fp["wuT"],
+           fp["w1T"], fp["w0T"], fp["wxT"], aff["Ainv"], float(p_drop), out["gv"], out["gpc"], out["gt3"], out["gt2"], out["gh0"], out["gct"], out["bsum"],
+           out["bfsum"], R, B, dim, 512, L, 2)
     return out

@@ -1348,16 +1348,12 @@ class TrainStep:
     def _mano_bwd(self, th45, det, blob, cu, vis, g_logp, N, p3=None, mods=ops.MODS_UV):
         R, B = th45.shape[0], det.shape[0]
         g45 = self._buf("g45", (R, 45)); rows = self._buf("gdet_rows", (R, 16))
-        from . import _lib
         if mods == ops.MODS_UV:
-            ops.check(_lib.lib().mhe_mano_joints_bwd_f32(ops._ptr(th45), ops._ptr(det), ops._ptr(cu), ops._ptr(vis), ops._ptr(blob), ops._ptr(g_logp),
-                                                         ops._ptr(g45), ops._ptr(rows), R, B, float(self.model.b_2d), float(self.model.th45_ref_alpha),
-                                                         1.0 / N, ops._stream()), "mhe_mano_joints_bwd_f32")
+            ops.launch("mhe_mano_joints_bwd_f32", th45, det, cu, vis, blob, g_logp, g45, rows, R, B, float(self.model.b_2d), float(self.model.th45_ref_alpha),
+                       1.0 / N)
         else:
-            ops.check(_lib.lib().mhe_mano_joints_mods_bwd_f32(ops._ptr(th45), ops._ptr(det), ops._ptr(cu), ops._ptr(vis), ops._ptr(p3), ops._ptr(blob),
-                                                              ops._ptr(g_logp), ops._ptr(g45), ops._ptr(rows), R, B, int(mods), float(self.model.b_2d),
-                                                              float(self.model.b_3d), float(self.model.th45_ref_alpha), 1.0 / N, ops._stream()),
-                      "mhe_mano_joints_mods_bwd_f32")
+            ops.launch("mhe_mano_joints_mods_bwd_f32", th45, det, cu, vis, p3, blob, g_logp, g45, rows, R, B, int(mods), float(self.model.b_2d),
+                       float(self.model.b_3d), float(self.model.th45_ref_alpha), 1.0 / N)
         return g45, rows
 
     def optimizer_step(self):

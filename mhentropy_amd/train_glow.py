@@ -13,12 +13,11 @@ gradients from dAinv, dcinv and the constant - runs in float64 ON THE DEVICE sin
 rounds 2-4 did it in numpy on the host, a queue drain per step that kept this branch out of HIP graphs).  Dropout (train mode, p = 0.2: hand/network.py:343-344,781) is applied to the second activation
 of every residual block in the sampling pass (mask bits kept on the tape) and to its gradient in the reverse pass (glow.py, mhe_dropout).
 """
-import ctypes as C
 import os
 
 import torch
 
-from . import ops, _lib
+from . import ops
 
 
 class GlowPart:
@@ -227,12 +226,12 @@ class GlowPart:
         weight gradients as TWO grouped launches after the chain (x = the tape's [L, 2, R, 512] tensors as they lie), all 16 bias gradients
         as ONE column sum of the per-image rows"""
         ts, g = self.ts, self.g
-        L_, D, H, R, L, NB = _lib.lib(), g.features, g.hidden, g_x.shape[0], g.num_layers, g.num_blocks
+        D, H, R, L, NB = g.features, g.hidden, g_x.shape[0], g.num_layers, g.num_blocks
         tp = self._tp
         ft, bits, ctab = tp["fused"], tp["bits"], tp["ctab"]
-        s, dev, raw, cs, bf = ops._stream, g_x.device, ts._raw, ctab.shape[1], torch.bfloat16
+        dev, raw, cs, bf = g_x.device, ts._raw, ctab.shape[1], torch.bfloat16
         gv = torch.empty(R, 64, device=dev)
-        ops.check(L_.mhe_pad64_f32(ops._ptr(g_x), ops._ptr(gv), R, D, s()), "mhe_pad64_f32")
+        ops.launch("mhe_pad64_f32", g_x, gv, R, D)
         Gct = ts._buf("glow_Gct", (B, cs)); Gct.zero_()
         gt3_all, gt2_all = ts._buf("glow_gt3", (L, NB, R, H), bf), ts._buf("glow_gt2", (L, NB, R, H), bf)
         bs_w = L * NB * 2 * H
@@ -245,8 +244,7 @@ class GlowPart:
             ops.linear_wgrad(y, gv, raw(rs["r_ainv"], (64, 64))); ops.colsum(gv, raw(rs["r_cinv"], (64,)))
             gy = ops.linear(gv, self.aff["AinvT"][l])
             gvc, gprm = torch.empty(R, 64, device=dev), torch.empty(R, 64, device=dev)
-            ops.check(L_.mhe_glow_coupling_inv_bwd_f32(ops._ptr(v), ops._ptr(prm), ops._ptr(gy), ops._ptr(g_logp), -1.0 / N,
-                                                       ops._ptr(gvc), ops._ptr(gprm), R, B, D, d["first"], d["T"], s()), "mhe_glow_coupling_inv_bwd_f32")
+            ops.launch("mhe_glow_coupling_inv_bwd_f32", v, prm, gy, g_logp, -1.0 / N, gvc, gprm, R, B, D, d["first"], d["T"])
             # the final layer's operand was kept as bf16: its weight gradient on bf16 operands, f32 accumulation
             ops.conv_wgrad(hf.view(R, 1, 1, H), gprm.to(bf).view(R, 1, 1, 64), 1, 1, 1, 0, raw(rs["r_wf"], (64, H)))
             ops.colsum(gprm, raw(rs["r_bf"], (64,)))
@@ -255,17 +253,13 @@ class GlowPart:
                 kb = l * NB + b
                 _, _, w0Tb, w1Tb = d["blocks_b"][b]
                 gt3, gt2 = gt3_all[l, b].view(R, 1, 1, H), gt2_all[l, b].view(R, 1, 1, H)
-                gate = C.c_void_p(ctab[:, (slot + 1 + b) * H:].data_ptr())
-                ops.check(L_.mhe_glow_glu_bwd_sum(ops._ptr(gh), ops._ptr(ft["t3"][l, b]), gate, cs, ops._ptr(gt3),
-                                                  C.c_void_p(Gct[:, (slot + 1 + b) * H:].data_ptr()), cs,
-                                                  C.c_void_p(bsum[:, (2 * kb + 1) * H:].data_ptr()), bs_w, N, B, H, s()), "mhe_glow_glu_bwd_sum")
+                ops.launch("mhe_glow_glu_bwd_sum", gh, ft["t3"][l, b], ctab[:, (slot + 1 + b) * H:], cs, gt3, Gct[:, (slot + 1 + b) * H:], cs,
+                           bsum[:, (2 * kb + 1) * H:], bs_w, N, B, H)
                 ops.conv2d_nhwc(gt3, w1Tb, 1, 1, 1, 0, out=gt2)
                 # dropout's and the ReLU's reverse in one pass: t2 = dropout(relu(.)) is zero exactly where either gate is closed
-                ops.check(L_.mhe_glow_mask_scale_sum(ops._ptr(gt2), ops._ptr(ft["t2"][l, b]), dscale, C.c_void_p(bsum[:, (2 * kb) * H:].data_ptr()),
-                                                     bs_w, N, B, H, s()), "mhe_glow_mask_scale_sum")
+                ops.launch("mhe_glow_mask_scale_sum", gt2, ft["t2"][l, b], dscale, bsum[:, (2 * kb) * H:], bs_w, N, B, H)
                 gt = ops.conv2d_nhwc(gt2, w0Tb, 1, 1, 1, 0)
-                ops.check(L_.mhe_relu_bwd_add_mixed(ops._ptr(gh), ops._ptr(gt), ops._ptr(ft["tb"][l, b]), gh.numel(), ops.BF16, ops.BF16, s()),
-                          "mhe_relu_bwd_add_mixed")
+                ops.launch("mhe_relu_bwd_add_mixed", gh, gt, ft["tb"][l, b], gh.numel(), ops.BF16, ops.BF16)
             ops.linear_wgrad(v, gh, raw(rs["r_wx"], (H, 64)))
             ops.sum_over_hypotheses(gh, N, B, out=Gct[:, slot * H:], out_stride=cs)
             gv = ops.add(gvc, ops.linear(gh, d["wxT"]))
@@ -285,10 +279,10 @@ class GlowPart:
         if "fused" in tp:           # the one-launch kernel's tape (mixed mode)
             return (self._backward_chain if tp["chain"] else self._backward_fused)(g_x, g_logp, N, B)
         ts, g = self.ts, self.g
-        L_, D, H, R = _lib.lib(), g.features, g.hidden, g_x.shape[0]
+        D, H, R = g.features, g.hidden, g_x.shape[0]
         raw, cs = ts._raw, tp["glow"]["ctab"].shape[1]
         gv = torch.empty(R, 64, device=g_x.device)
-        ops.check(L_.mhe_pad64_f32(ops._ptr(g_x), ops._ptr(gv), R, D, ops._stream()), "mhe_pad64_f32")
+        ops.launch("mhe_pad64_f32", g_x, gv, R, D)
         Gct = torch.zeros(B, cs, device=g_x.device)
         # the staged reverse (glow.py: ConditionalGlow._reverse) with the gradients landing in the raw arena
         layers = [{"AinvT": self.aff["AinvT"][l], "wfT": d["wfT"], "wxT": d["wxT"], "blocksT": [bb[2:] for bb in d["blocks_b"]] if self.mixed else d["blocksT"],
