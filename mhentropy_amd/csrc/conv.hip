@@ -655,26 +655,87 @@ static int launch_conv(const Params &p, hipStream_t s) {
 
 using namespace mhe;
 
-static inline int elem_chunk(int dtype) { return dtype == MHE_F32 ? 4 : 8; }
-
-static int conv_entry(const mhe_conv_desc *d, const void *x, const void *w, void *y, const float *in_scale,
-                      const float *in_shift, const float *out_scale, const float *out_shift, const void *residual,
-                      mhe_stat_t *stats, const void *x2, const float *x2_scale, const float *x2_shift, void *a_out, void *stream,
-                      const void *mask = nullptr, const struct BnRev *bn = nullptr, float *y32 = nullptr, const int *scatter = nullptr,
-                      const void *xcat = nullptr, int cin2 = 0, const void *mask_bits = nullptr, int a_quarter = 0);
+// the BatchNorm units whose reverse sums a data-gradient launch accumulates (Params::bn_y / bn_mi / bn_stats)
 struct BnRev { const void *y[2]; const float *mi[2]; mhe_stat_t *stats[2]; };
+
+// a data-gradient entry's bn_y0 / bn_y1 arguments as a BnRev: each bn_y needs its mean_invstd and stats, and unit 1 needs unit 0.  `units`
+// is how many the entry takes - its message says so
+static int bn_rev(BnRev &out, const char *entry, int units, const BnRev &bn) {
+    const bool ok = (!bn.y[0] || (bn.mi[0] && bn.stats[0])) && (!bn.y[1] || (bn.y[0] && bn.mi[1] && bn.stats[1]));
+    MHE_REQUIRE(ok, units == 1 ? "%s: bn_y needs its mean_invstd and stats" : "%s: each bn_y needs its mean_invstd and stats (and bn_y1 needs bn_y0)", entry);
+    out = bn;
+    return MHE_OK;
+}
+
+// every operand of a launch through conv_entry, by name: an entry sets what it takes, the rest is absent
+struct ConvRequest {
+    const void *x = nullptr, *w = nullptr, *residual = nullptr, *mask = nullptr, *mask_bits = nullptr;
+    void *y = nullptr;
+    float *y32 = nullptr;                     // f32 result of a bf16 product, instead of y
+    const float *in_scale = nullptr, *in_shift = nullptr, *out_scale = nullptr, *out_shift = nullptr;
+    mhe_stat_t *stats = nullptr;
+    const void *x2 = nullptr;                 // residual-tail operand load and its optional affine; a_out receives the operand,
+    const float *x2_scale = nullptr, *x2_shift = nullptr;
+    void *a_out = nullptr; int a_quarter = 0; // ... as the compact stride-2 quarter where a_quarter is set (Params::a_quarter)
+    BnRev bn = {};
+    const int *scatter = nullptr;             // {py, px}: parity class of a stride-2 data gradient
+    const void *xcat = nullptr; int cin2 = 0; // K-concatenated second operand tensor of cin2 channels
+};
+
+static int conv_entry(const mhe_conv_desc *d, const ConvRequest &r, void *stream) {
+    MHE_REQUIRE(d && r.x && r.w && (r.y || r.y32), "mhe_conv2d_nhwc: null pointer");
+    MHE_REQUIRE(d->dtype == MHE_F32 || d->dtype == MHE_BF16, "mhe_conv2d_nhwc: dtype=%d", d->dtype);
+    const int ce = conv::elem_chunk(d->dtype), bke = 8 * ce;
+    MHE_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0,
+                "mhe_conv2d_nhwc: bad geometry");
+    MHE_REQUIRE(d->Cin % ce == 0, "mhe_conv2d_nhwc: Cin=%d must be a multiple of %d (pad channels)", d->Cin, ce);
+    MHE_REQUIRE(d->Cout % ce == 0, "mhe_conv2d_nhwc: Cout=%d must be a multiple of %d", d->Cout, ce);
+    MHE_REQUIRE((r.in_scale == nullptr) == (r.in_shift == nullptr), "mhe_conv2d_nhwc: in_scale/in_shift must come together");
+    MHE_REQUIRE(!r.in_scale || d->Cin <= conv::MAXC, "mhe_conv2d_nhwc: fused input affine supports Cin <= %d", conv::MAXC);
+    conv::Params p{};
+    p.x = r.x; p.w = r.w; p.y = r.y; p.in_scale = r.in_scale; p.in_shift = r.in_shift; p.out_scale = r.out_scale;
+    p.out_shift = r.out_shift; p.residual = r.residual; p.stats = r.stats; p.mask = r.mask;
+    for (int u = 0; u < 2; ++u) { p.bn_y[u] = r.bn.y[u]; p.bn_mi[u] = r.bn.mi[u]; p.bn_stats[u] = r.bn.stats[u]; }
+    p.x2 = r.x2; p.x2_scale = r.x2_scale; p.x2_shift = r.x2_shift; p.a_out = r.a_out;
+    p.xcat = r.xcat; p.Cin2 = r.cin2; p.mask_bits = (const unsigned char *)r.mask_bits;
+    p.res_s2 = d->res_half ? 1 : 0;
+    MHE_REQUIRE(!p.res_s2 || (r.residual && !r.scatter && !r.y32), "mhe_conv2d_nhwc: res_half needs a residual (and no output scatter)");
+    const long long M = conv::fill_geometry(p, *d, r.scatter != nullptr);
+    if (r.scatter) { p.os2 = 1; p.os_py = r.scatter[0]; p.os_px = r.scatter[1]; }      // (one output per input position: reads past the edge give zeros)
+    MHE_REQUIRE(p.Ho > 0 && p.Wo > 0, "mhe_conv2d_nhwc: empty output");
+    MHE_REQUIRE(M < (1ll << 31), "mhe_conv2d_nhwc: too many output pixels");
+    p.relu_in = d->relu_in; p.relu_out = d->relu_out;
+    p.force = d->tile - 1;
+    if (r.y32) {      // f32 result of a bf16 product: register-staged kernels only (their epilogue stores straight from the accumulators)
+        MHE_REQUIRE(d->dtype == MHE_BF16 && !r.in_scale && !r.out_scale && !r.residual && !r.stats && !r.x2 && !r.mask && !d->relu_out && d->Cout % 4 == 0,
+                    "mhe_conv2d_f32out_nhwc: bf16 operands, optional out_shift only");
+        p.y32 = r.y32;
+        if (p.force < 0 || p.force > 4) p.force = p.Cout <= 64 ? 0 : 1;
+    }
+    if (r.a_quarter) {    // the compact operand output exists in the transfer-wave tail kernel only: no other variant may see the smaller tensor
+        p.a_quarter = 1;
+        MHE_REQUIRE(d->dtype == MHE_BF16 && conv::choose_tile(p, d->Cin % bke == 0, true) == 10,
+                    "mhe_conv1x1_residual_in_quarter_nhwc: geometry not taken by the residual-tail kernel (variant 10; Cin=%d Cout=%d M=%lld)", d->Cin, d->Cout, M);
+        return conv::launch_tail(p, (hipStream_t)stream);
+    }
+    if (d->dtype == MHE_F32) return conv::launch_conv<float>(p, (hipStream_t)stream);
+    return conv::launch_conv<u16>(p, (hipStream_t)stream);
+}
 
 extern "C" int mhe_conv2d_nhwc(const mhe_conv_desc *d, const void *x, const void *w, void *y, const float *in_scale,
                                const float *in_shift, const float *out_scale, const float *out_shift,
                                const void *residual, mhe_stat_t *stats, void *stream) {
-    return conv_entry(d, x, w, y, in_scale, in_shift, out_scale, out_shift, residual, stats, nullptr, nullptr, nullptr,
-                      nullptr, stream);
+    ConvRequest r;
+    r.x = x; r.w = w; r.y = y; r.in_scale = in_scale; r.in_shift = in_shift; r.out_scale = out_scale; r.out_shift = out_shift;
+    r.residual = residual; r.stats = stats;
+    return conv_entry(d, r, stream);
 }
 
 extern "C" int mhe_conv2d_f32out_nhwc(const mhe_conv_desc *d, const void *x, const void *w, float *y_f32, const float *out_shift, void *stream) {
     MHE_REQUIRE(y_f32, "mhe_conv2d_f32out_nhwc: null output");
-    return conv_entry(d, x, w, nullptr, nullptr, nullptr, nullptr, out_shift, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream, nullptr,
-                      nullptr, y_f32);
+    ConvRequest r;
+    r.x = x; r.w = w; r.y32 = y_f32; r.out_shift = out_shift;
+    return conv_entry(d, r, stream);
 }
 
 extern "C" int mhe_conv1x1_residual_in_nhwc(const mhe_conv_desc *d, const void *x, const void *x2, const void *w, void *y,
@@ -683,7 +744,10 @@ extern "C" int mhe_conv1x1_residual_in_nhwc(const mhe_conv_desc *d, const void *
     MHE_REQUIRE(d && x2 && in_scale && in_shift, "mhe_conv1x1_residual_in_nhwc: x2, in_scale and in_shift are required");
     MHE_REQUIRE(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0, "mhe_conv1x1_residual_in_nhwc: 1x1 stride-1 only");
     MHE_REQUIRE((x2_scale == nullptr) == (x2_shift == nullptr), "mhe_conv1x1_residual_in_nhwc: x2_scale/x2_shift must come together");
-    return conv_entry(d, x, w, y, in_scale, in_shift, nullptr, nullptr, nullptr, stats, x2, x2_scale, x2_shift, a_out, stream);
+    ConvRequest r;
+    r.x = x; r.w = w; r.y = y; r.in_scale = in_scale; r.in_shift = in_shift; r.x2 = x2; r.x2_scale = x2_scale; r.x2_shift = x2_shift; r.a_out = a_out;
+    r.stats = stats;
+    return conv_entry(d, r, stream);
 }
 
 extern "C" int mhe_conv1x1_residual_in_quarter_nhwc(const mhe_conv_desc *d, const void *x, const void *x2, const void *w, void *y,
@@ -692,8 +756,10 @@ extern "C" int mhe_conv1x1_residual_in_quarter_nhwc(const mhe_conv_desc *d, cons
     MHE_REQUIRE(d && x2 && in_scale && in_shift && a_quarter, "mhe_conv1x1_residual_in_quarter_nhwc: x2, in_scale, in_shift and a_quarter are required");
     MHE_REQUIRE(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0, "mhe_conv1x1_residual_in_quarter_nhwc: 1x1 stride-1 only");
     MHE_REQUIRE((x2_scale == nullptr) == (x2_shift == nullptr), "mhe_conv1x1_residual_in_quarter_nhwc: x2_scale/x2_shift must come together");
-    return conv_entry(d, x, w, y, in_scale, in_shift, nullptr, nullptr, nullptr, stats, x2, x2_scale, x2_shift, a_quarter, stream, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, 0, nullptr, 1);
+    ConvRequest r;
+    r.x = x; r.w = w; r.y = y; r.in_scale = in_scale; r.in_shift = in_shift; r.x2 = x2; r.x2_scale = x2_scale; r.x2_shift = x2_shift; r.a_out = a_quarter;
+    r.stats = stats; r.a_quarter = 1;
+    return conv_entry(d, r, stream);
 }
 
 extern "C" int mhe_conv1x1_cat_bias_nhwc(const mhe_conv_desc *d, const void *x, const void *xcat, int cin2, const void *w, void *y, const void *residual,
@@ -701,8 +767,9 @@ extern "C" int mhe_conv1x1_cat_bias_nhwc(const mhe_conv_desc *d, const void *x, 
     MHE_REQUIRE(d && xcat && d->dtype == MHE_BF16 && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && cin2 > 0 && cin2 % 64 == 0 && d->Cin % 64 == 0,
                 "mhe_conv1x1_cat_bias_nhwc: a bf16 1x1 stride-1 launch on two operand tensors with Cin and cin2 multiples of 64");
     MHE_REQUIRE(d->tile == 0 || d->tile == 1 || d->tile == 2, "mhe_conv1x1_cat_bias_nhwc: 128-row register-staged tiles only (tile 0, 1 or 2)");
-    return conv_entry(d, x, w, y, nullptr, nullptr, nullptr, bias, residual, nullptr, nullptr, nullptr, nullptr, nullptr, stream, nullptr, nullptr, nullptr,
-                      nullptr, xcat, cin2);
+    ConvRequest r;
+    r.x = x; r.w = w; r.y = y; r.out_shift = bias; r.residual = residual; r.xcat = xcat; r.cin2 = cin2;
+    return conv_entry(d, r, stream);
 }
 
 extern "C" int mhe_conv1x1_residual_in_masked_nhwc(const mhe_conv_desc *d, const void *x, const void *x2, const void *w, void *y,
@@ -712,33 +779,34 @@ extern "C" int mhe_conv1x1_residual_in_masked_nhwc(const mhe_conv_desc *d, const
     MHE_REQUIRE(d && x2 && in_scale && in_shift && mask, "mhe_conv1x1_residual_in_masked_nhwc: x2, in_scale, in_shift and mask are required");
     MHE_REQUIRE(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0, "mhe_conv1x1_residual_in_masked_nhwc: 1x1 stride-1 only");
     MHE_REQUIRE((x2_scale == nullptr) == (x2_shift == nullptr), "mhe_conv1x1_residual_in_masked_nhwc: x2_scale/x2_shift must come together");
-    MHE_REQUIRE(!bn_y0 || (bn_mean_invstd0 && bn_stats0), "mhe_conv1x1_residual_in_masked_nhwc: bn_y needs its mean_invstd and stats");
+    ConvRequest r;
+    r.x = x; r.w = w; r.y = y; r.in_scale = in_scale; r.in_shift = in_shift; r.x2 = x2; r.x2_scale = x2_scale; r.x2_shift = x2_shift; r.a_out = a_out;
+    if (int rc = bn_rev(r.bn, "mhe_conv1x1_residual_in_masked_nhwc", 1, {{bn_y0}, {bn_mean_invstd0}, {bn_stats0}})) return rc;
     MHE_REQUIRE(d->tile == 0 || d->tile == 1 || d->tile == 2 || d->tile == 11,
                 "mhe_conv1x1_residual_in_masked_nhwc: 128-row tiles only (tile 0, 1, 2, or 11 = the transfer-wave kernel)");
-    const BnRev bn = {{bn_y0, nullptr}, {bn_mean_invstd0, nullptr}, {bn_stats0, nullptr}};
-    return conv_entry(d, x, w, y, in_scale, in_shift, nullptr, nullptr, residual, nullptr, x2, x2_scale, x2_shift, a_out, stream, mask, &bn);
+    r.residual = residual; r.mask = mask;
+    return conv_entry(d, r, stream);
 }
 
 extern "C" int mhe_conv2d_masked_nhwc(const mhe_conv_desc *d, const void *x, const void *w, void *y, const void *residual,
                                       const void *mask, const void *bn_y0, const float *bn_mean_invstd0, mhe_stat_t *bn_stats0,
                                       const void *bn_y1, const float *bn_mean_invstd1, mhe_stat_t *bn_stats1, void *stream) {
     MHE_REQUIRE(mask, "mhe_conv2d_masked_nhwc: mask is required");
-    MHE_REQUIRE((!bn_y0 || (bn_mean_invstd0 && bn_stats0)) && (!bn_y1 || (bn_y0 && bn_mean_invstd1 && bn_stats1)),
-                "mhe_conv2d_masked_nhwc: each bn_y needs its mean_invstd and stats (and bn_y1 needs bn_y0)");
-    const BnRev bn = {{bn_y0, bn_y1}, {bn_mean_invstd0, bn_mean_invstd1}, {bn_stats0, bn_stats1}};
-    return conv_entry(d, x, w, y, nullptr, nullptr, nullptr, nullptr, residual, nullptr, nullptr, nullptr, nullptr, nullptr, stream, mask, &bn);
+    ConvRequest r;
+    if (int rc = bn_rev(r.bn, "mhe_conv2d_masked_nhwc", 2, {{bn_y0, bn_y1}, {bn_mean_invstd0, bn_mean_invstd1}, {bn_stats0, bn_stats1}})) return rc;
+    r.x = x; r.w = w; r.y = y; r.residual = residual; r.mask = mask;
+    return conv_entry(d, r, stream);
 }
 
 extern "C" int mhe_conv2d_masked_bits_nhwc(const mhe_conv_desc *d, const void *x, const void *w, void *y, const void *residual,
                                            const void *mask, const void *mask_bits, const void *bn_y0, const float *bn_mean_invstd0, mhe_stat_t *bn_stats0,
                                            const void *bn_y1, const float *bn_mean_invstd1, mhe_stat_t *bn_stats1, void *stream) {
     MHE_REQUIRE(mask, "mhe_conv2d_masked_bits_nhwc: mask is required (kernels without the bit path read it)");
-    MHE_REQUIRE((!bn_y0 || (bn_mean_invstd0 && bn_stats0)) && (!bn_y1 || (bn_y0 && bn_mean_invstd1 && bn_stats1)),
-                "mhe_conv2d_masked_bits_nhwc: each bn_y needs its mean_invstd and stats (and bn_y1 needs bn_y0)");
+    ConvRequest r;
+    if (int rc = bn_rev(r.bn, "mhe_conv2d_masked_bits_nhwc", 2, {{bn_y0, bn_y1}, {bn_mean_invstd0, bn_mean_invstd1}, {bn_stats0, bn_stats1}})) return rc;
     MHE_REQUIRE(!mask_bits || (d && d->Cout % 8 == 0), "mhe_conv2d_masked_bits_nhwc: Cout must be a multiple of 8");
-    const BnRev bn = {{bn_y0, bn_y1}, {bn_mean_invstd0, bn_mean_invstd1}, {bn_stats0, bn_stats1}};
-    return conv_entry(d, x, w, y, nullptr, nullptr, nullptr, nullptr, residual, nullptr, nullptr, nullptr, nullptr, nullptr, stream, mask, &bn, nullptr,
-                      nullptr, nullptr, 0, mask_bits);
+    r.x = x; r.w = w; r.y = y; r.residual = residual; r.mask = mask; r.mask_bits = mask_bits;
+    return conv_entry(d, r, stream);
 }
 
 extern "C" int mhe_conv2d_masked_bias_nhwc(const mhe_conv_desc *d, const void *x, const void *xcat, int cin2, const void *w, void *y,
@@ -747,11 +815,11 @@ extern "C" int mhe_conv2d_masked_bias_nhwc(const mhe_conv_desc *d, const void *x
     MHE_REQUIRE(mask && bias, "mhe_conv2d_masked_bias_nhwc: mask and bias are required");
     MHE_REQUIRE(!xcat || (d && d->dtype == MHE_BF16 && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && cin2 > 0 && cin2 % 64 == 0 && d->Cin % 64 == 0),
                 "mhe_conv2d_masked_bias_nhwc: a concatenated operand needs a bf16 1x1 stride-1 launch with Cin and cin2 multiples of 64");
-    MHE_REQUIRE(!bn_y0 || (bn_mean_invstd0 && bn_stats0), "mhe_conv2d_masked_bias_nhwc: bn_y needs its mean_invstd and stats");
+    ConvRequest r;
+    if (int rc = bn_rev(r.bn, "mhe_conv2d_masked_bias_nhwc", 1, {{bn_y0}, {bn_mean_invstd0}, {bn_stats0}})) return rc;
     MHE_REQUIRE(d && (d->tile == 0 || d->tile == 1 || d->tile == 2), "mhe_conv2d_masked_bias_nhwc: 128-row register-staged tiles only (tile 0, 1 or 2)");
-    const BnRev bn = {{bn_y0, nullptr}, {bn_mean_invstd0, nullptr}, {bn_stats0, nullptr}};
-    return conv_entry(d, x, w, y, nullptr, nullptr, nullptr, bias, residual, nullptr, nullptr, nullptr, nullptr, nullptr, stream, mask, &bn, nullptr,
-                      nullptr, xcat, xcat ? cin2 : 0);
+    r.x = x; r.w = w; r.y = y; r.out_shift = bias; r.residual = residual; r.mask = mask; r.xcat = xcat; r.cin2 = xcat ? cin2 : 0;
+    return conv_entry(d, r, stream);
 }
 
 extern "C" int mhe_conv3x3s2_dgrad_nhwc(int B, int Ho, int Wo, int Cout, int Cin, int dtype, const void *gy, const void *const *w4,
@@ -761,72 +829,18 @@ extern "C" int mhe_conv3x3s2_dgrad_nhwc(int B, int Ho, int Wo, int Cout, int Cin
     MHE_REQUIRE(gy && w4 && dx && w4[0] && w4[1] && w4[2] && w4[3], "mhe_conv3x3s2_dgrad_nhwc: null pointer");
     MHE_REQUIRE((!bn_y0 || (bn_mean_invstd0 && bn_stats0 && mask)) && (!bn_y1 || (bn_y0 && bn_mean_invstd1 && bn_stats1)),
                 "mhe_conv3x3s2_dgrad_nhwc: each bn_y needs its mean_invstd and stats (and the gate)");
-    const BnRev bn = {{bn_y0, bn_y1}, {bn_mean_invstd0, bn_mean_invstd1}, {bn_stats0, bn_stats1}};
+    ConvRequest r;
+    r.x = gy; r.y = dx; r.residual = residual; r.mask = mask;
+    if (mask) r.bn = {{bn_y0, bn_y1}, {bn_mean_invstd0, bn_mean_invstd1}, {bn_stats0, bn_stats1}};
     for (int py = 0; py < 2; ++py)
         for (int px = 0; px < 2; ++px) {
             // output rows 2i + py: py = 0 sees forward tap kh = 1 at gy row i; py = 1 sees kh = 2 at row i and kh = 0 at row i + 1
             mhe_conv_desc d = {B, Ho, Wo, Cout, Cin, 1 + py, 1 + px, 1, 0, dtype, 0, 0, tile};
             const int sc[2] = {py, px};
-            const int rc = conv_entry(&d, gy, w4[2 * py + px], dx, nullptr, nullptr, nullptr, nullptr, residual, nullptr, nullptr, nullptr,
-                                      nullptr, nullptr, stream, mask, mask ? &bn : nullptr, nullptr, sc);
-            if (rc) return rc;
+            r.w = w4[2 * py + px]; r.scatter = sc;
+            if (int rc = conv_entry(&d, r, stream)) return rc;
         }
     return MHE_OK;
-}
-
-static int conv_entry(const mhe_conv_desc *d, const void *x, const void *w, void *y, const float *in_scale,
-                      const float *in_shift, const float *out_scale, const float *out_shift, const void *residual,
-                      mhe_stat_t *stats, const void *x2, const float *x2_scale, const float *x2_shift, void *a_out, void *stream,
-                      const void *mask, const BnRev *bn, float *y32, const int *scatter, const void *xcat, int cin2, const void *mask_bits,
-                      int a_quarter) {
-    MHE_REQUIRE(d && x && w && (y || y32), "mhe_conv2d_nhwc: null pointer");
-    MHE_REQUIRE(d->dtype == MHE_F32 || d->dtype == MHE_BF16, "mhe_conv2d_nhwc: dtype=%d", d->dtype);
-    const int ce = elem_chunk(d->dtype), bke = 8 * ce;
-    MHE_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0,
-                "mhe_conv2d_nhwc: bad geometry");
-    MHE_REQUIRE(d->Cin % ce == 0, "mhe_conv2d_nhwc: Cin=%d must be a multiple of %d (pad channels)", d->Cin, ce);
-    MHE_REQUIRE(d->Cout % ce == 0, "mhe_conv2d_nhwc: Cout=%d must be a multiple of %d", d->Cout, ce);
-    MHE_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "mhe_conv2d_nhwc: in_scale/in_shift must come together");
-    MHE_REQUIRE(!in_scale || d->Cin <= conv::MAXC, "mhe_conv2d_nhwc: fused input affine supports Cin <= %d", conv::MAXC);
-    conv::Params p{};
-    p.x = x; p.w = w; p.y = y; p.in_scale = in_scale; p.in_shift = in_shift; p.out_scale = out_scale;
-    p.out_shift = out_shift; p.residual = residual; p.stats = stats; p.mask = mask;
-    for (int u = 0; u < 2; ++u) { p.bn_y[u] = bn ? bn->y[u] : nullptr; p.bn_mi[u] = bn ? bn->mi[u] : nullptr; p.bn_stats[u] = bn ? bn->stats[u] : nullptr; }
-    p.x2 = x2; p.x2_scale = x2_scale; p.x2_shift = x2_shift; p.a_out = a_out;
-    p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW;
-    p.stride = d->stride; p.pad = d->pad;
-    p.Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1;
-    p.Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-    p.os2 = 0; p.os_py = p.os_px = 0;
-    p.res_s2 = d->res_half ? 1 : 0;
-    MHE_REQUIRE(!p.res_s2 || (residual && !scatter && !y32), "mhe_conv2d_nhwc: res_half needs a residual (and no output scatter)");
-    if (scatter) {     // parity class of a stride-2 data gradient: one output per input position (reads past the edge give zeros)
-        p.Ho = d->H; p.Wo = d->W; p.os2 = 1; p.os_py = scatter[0]; p.os_px = scatter[1];
-    }
-    MHE_REQUIRE(p.Ho > 0 && p.Wo > 0, "mhe_conv2d_nhwc: empty output");
-    const long long M = (long long)p.B * p.Ho * p.Wo;
-    MHE_REQUIRE(M < (1ll << 31), "mhe_conv2d_nhwc: too many output pixels");
-    p.M = (int)M;
-    p.xcat = xcat; p.Cin2 = cin2; p.mask_bits = (const unsigned char *)mask_bits;
-    const int ktot = d->KH * d->KW * d->Cin + cin2;
-    p.Kpad = (ktot + bke - 1) / bke * bke;       // weight rows are zero-padded to this length by the packer
-    p.relu_in = d->relu_in; p.relu_out = d->relu_out;
-    p.force = d->tile - 1;
-    p.y32 = nullptr;
-    if (y32) {        // f32 result of a bf16 product: register-staged kernels only (their epilogue stores straight from the accumulators)
-        MHE_REQUIRE(d->dtype == MHE_BF16 && !in_scale && !out_scale && !residual && !stats && !x2 && !mask && !d->relu_out && d->Cout % 4 == 0,
-                    "mhe_conv2d_f32out_nhwc: bf16 operands, optional out_shift only");
-        p.y32 = y32;
-        if (p.force < 0 || p.force > 4) p.force = p.Cout <= 64 ? 0 : 1;
-    }
-    if (a_quarter) {      // the compact operand output exists in the transfer-wave tail kernel only: no other variant may see the smaller tensor
-        p.a_quarter = 1;
-        MHE_REQUIRE(d->dtype == MHE_BF16 && conv::choose_tile(p, d->Cin % bke == 0, true) == 10,
-                    "mhe_conv1x1_residual_in_quarter_nhwc: geometry not taken by the residual-tail kernel (variant 10; Cin=%d Cout=%d M=%lld)", d->Cin, d->Cout, M);
-        return conv::launch_tail(p, (hipStream_t)stream);
-    }
-    if (d->dtype == MHE_F32) return conv::launch_conv<float>(p, (hipStream_t)stream);
-    return conv::launch_conv<u16>(p, (hipStream_t)stream);
 }
 
 // ---- the statistics-only pass and the fused bottleneck tail that re-evaluates conv3 (conv_fuse.hip)
@@ -838,10 +852,9 @@ extern "C" int mhe_conv1x1_stats_nhwc(const mhe_conv_desc *d, const void *x, con
     MHE_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "mhe_conv1x1_stats_nhwc: in_scale/in_shift must come together");
     conv::Params p{};
     p.x = x; p.w = w; p.y = nullptr; p.in_scale = in_scale; p.in_shift = in_shift; p.stats = stats;
-    p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.Ho = d->H; p.Wo = d->W;
-    const long long M = (long long)d->B * d->H * d->W;
+    const long long M = conv::fill_geometry(p, *d);
     MHE_REQUIRE(M > 0 && M < (1ll << 31), "mhe_conv1x1_stats_nhwc: bad pixel count");
-    p.M = (int)M; p.Kpad = d->Cin; p.relu_in = d->relu_in; p.force = 8; p.stats_only = 1;
+    p.relu_in = d->relu_in; p.force = 8; p.stats_only = 1;
     if (d->Cin == 256) {       // the resident-slab kernel with its stores dropped (conv_wide.hip): the sums of the products as they would be stored
         p.force = 11;
         MHE_REQUIRE(conv::wide_supports(p), "mhe_conv1x1_stats_nhwc: geometry not taken by the resident-slab kernel (M=%lld Cout=%d)", M, d->Cout);
@@ -856,11 +869,24 @@ extern "C" int mhe_bottleneck_tail_supported(const mhe_conv_desc *d, int Cb) {
     static const float dummy = 0.f;
     conv::Params p{};
     p.x = p.x2 = p.w = p.w3 = p.y = p.a_out = (void *)&dummy; p.in_scale = p.in_shift = p.mid_scale = p.mid_shift = &dummy;
-    p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.Kpad = d->Cin;
-    const long long M = (long long)d->B * d->H * d->W;
+    const long long M = conv::fill_geometry(p, *d, true);
     if (M <= 0 || M >= (1ll << 31)) return 0;
-    p.M = (int)M;
     return conv::fuse_supports(p, Cb) ? 1 : 0;
+}
+
+// the bottleneck-tail entries' common body: p holds the operands (and a_bits / a_quarter, the two forms' own fields) as the entry named
+// them; `entry` names the caller in the messages
+static int bottleneck_tail(const char *entry, const mhe_conv_desc *d, int Cb, conv::Params &p, void *stream) {
+    MHE_REQUIRE(d && p.x && p.in_scale && p.in_shift && p.w3 && p.mid_scale && p.mid_shift && p.x2 && p.w && p.a_out && p.y, "%s: null pointer", entry);
+    MHE_REQUIRE(d->dtype == MHE_BF16, "%s: bf16 storage only", entry);
+    MHE_REQUIRE((p.x2_scale == nullptr) == (p.x2_shift == nullptr), "%s: id_scale/id_shift must come together", entry);
+    MHE_REQUIRE(!p.a_quarter || (d->B > 0 && d->H > 0 && d->W > 0), "%s: bad geometry", entry);
+    p.relu_in = 1; p.force = -1;
+    const long long M = conv::fill_geometry(p, *d, true);
+    MHE_REQUIRE(M > 0 && (p.a_quarter ? M * d->Cin : M) < (1ll << 31), "%s: bad pixel count", entry);     // (quarter: 32-bit byte offsets into the compact tensor)
+    MHE_REQUIRE(conv::fuse_supports(p, Cb), "%s: needs Cin = 4 Cb, Cb 64 / 128, Cout 64 / 128, pixels %% 128 == 0 (Cin=%d Cb=%d Cout=%d M=%lld)",
+                entry, d->Cin, Cb, d->Cout, M);
+    return conv::launch_fuse(p, Cb, (hipStream_t)stream);
 }
 
 extern "C" int mhe_bottleneck_tail_nhwc(const mhe_conv_desc *d, int Cb, const void *y2, const float *bn2_scale, const float *bn2_shift,
@@ -874,79 +900,43 @@ extern "C" int mhe_bottleneck_tail_bits_nhwc(const mhe_conv_desc *d, int Cb, con
                                              const void *w3, const float *bn3_scale, const float *bn3_shift, const void *identity,
                                              const float *id_scale, const float *id_shift, const void *w1, void *a_out, void *a_bits, void *y1,
                                              mhe_stat_t *stats, void *stream) {
-    MHE_REQUIRE(d && y2 && bn2_scale && bn2_shift && w3 && bn3_scale && bn3_shift && identity && w1 && a_out && y1, "mhe_bottleneck_tail_nhwc: null pointer");
-    MHE_REQUIRE(d->dtype == MHE_BF16, "mhe_bottleneck_tail_nhwc: bf16 storage only");
-    MHE_REQUIRE((id_scale == nullptr) == (id_shift == nullptr), "mhe_bottleneck_tail_nhwc: id_scale/id_shift must come together");
     conv::Params p{};
     p.x = y2; p.in_scale = bn2_scale; p.in_shift = bn2_shift; p.w3 = w3; p.mid_scale = bn3_scale; p.mid_shift = bn3_shift;
     p.x2 = identity; p.x2_scale = id_scale; p.x2_shift = id_shift; p.w = w1; p.a_out = a_out; p.y = y1; p.stats = stats;
     p.a_bits = (unsigned char *)a_bits;
-    p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-    p.Ho = d->H; p.Wo = d->W; p.Kpad = d->Cin; p.relu_in = 1; p.force = -1;
-    const long long M = (long long)d->B * d->H * d->W;
-    MHE_REQUIRE(M > 0 && M < (1ll << 31), "mhe_bottleneck_tail_nhwc: bad pixel count");
-    p.M = (int)M;
-    MHE_REQUIRE(conv::fuse_supports(p, Cb), "mhe_bottleneck_tail_nhwc: needs Cin = 4 Cb, Cb 64 / 128, Cout 64 / 128, pixels %% 128 == 0 (Cin=%d Cb=%d Cout=%d M=%lld)",
-                d->Cin, Cb, d->Cout, M);
-    return conv::launch_fuse(p, Cb, (hipStream_t)stream);
+    return bottleneck_tail("mhe_bottleneck_tail_nhwc", d, Cb, p, stream);
 }
 
 extern "C" int mhe_bottleneck_tail_quarter_nhwc(const mhe_conv_desc *d, int Cb, const void *y2, const float *bn2_scale, const float *bn2_shift,
                                                 const void *w3, const float *bn3_scale, const float *bn3_shift, const void *identity,
                                                 const float *id_scale, const float *id_shift, const void *w1, void *a_quarter, void *y1,
                                                 mhe_stat_t *stats, void *stream) {
-    MHE_REQUIRE(d && y2 && bn2_scale && bn2_shift && w3 && bn3_scale && bn3_shift && identity && w1 && a_quarter && y1, "mhe_bottleneck_tail_quarter_nhwc: null pointer");
-    MHE_REQUIRE(d->dtype == MHE_BF16, "mhe_bottleneck_tail_quarter_nhwc: bf16 storage only");
-    MHE_REQUIRE((id_scale == nullptr) == (id_shift == nullptr), "mhe_bottleneck_tail_quarter_nhwc: id_scale/id_shift must come together");
-    MHE_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0, "mhe_bottleneck_tail_quarter_nhwc: bad geometry");
     conv::Params p{};
     p.x = y2; p.in_scale = bn2_scale; p.in_shift = bn2_shift; p.w3 = w3; p.mid_scale = bn3_scale; p.mid_shift = bn3_shift;
     p.x2 = identity; p.x2_scale = id_scale; p.x2_shift = id_shift; p.w = w1; p.a_out = a_quarter; p.y = y1; p.stats = stats;
     p.a_quarter = 1;
-    p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-    p.Ho = d->H; p.Wo = d->W; p.Kpad = d->Cin; p.relu_in = 1; p.force = -1;
-    const long long M = (long long)d->B * d->H * d->W;
-    MHE_REQUIRE(M > 0 && M * d->Cin < (1ll << 31), "mhe_bottleneck_tail_quarter_nhwc: bad pixel count");
-    p.M = (int)M;
-    MHE_REQUIRE(conv::fuse_supports(p, Cb), "mhe_bottleneck_tail_quarter_nhwc: needs Cin = 4 Cb, Cb 64 / 128, Cout 64 / 128, pixels %% 128 == 0 (Cin=%d Cb=%d Cout=%d M=%lld)",
-                d->Cin, Cb, d->Cout, M);
-    return conv::launch_fuse(p, Cb, (hipStream_t)stream);
+    return bottleneck_tail("mhe_bottleneck_tail_quarter_nhwc", d, Cb, p, stream);
 }
 
 extern "C" int mhe_conv_stat_shards(void) { return conv::NSH; }
 extern "C" size_t mhe_stat_words(int C) { return C > 0 ? (size_t)2 * conv::NSH * 2 * (size_t)C : 0; }
 
-// which kernel variant the launcher picks for a geometry with plain operands (see mhe_conv_desc.tile); with a producer-BatchNorm /
-// residual-tail operand load variant 7 becomes 2
-extern "C" int mhe_conv_tile(const mhe_conv_desc *d) {
-    if (!d) return -1;
-    conv::Params p{};
-    p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-    const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-    p.M = d->B * Ho * Wo;
-    p.force = d->tile - 1;
-    const int bke = d->dtype == MHE_F32 ? 32 : 64;
-    p.Kpad = (d->KH * d->KW * d->Cin + bke - 1) / bke * bke;
-    return conv::choose_tile(p, d->Cin % bke == 0, d->dtype == MHE_BF16);
-}
-
-// the same for an operand-load form: 1 = producer BatchNorm on load (mhe_conv2d_nhwc with in_scale), 2 = residual-block tail
-// (mhe_conv1x1_residual_in_nhwc); 0 = plain (mhe_conv_tile)
+// which kernel variant the launcher picks for a geometry, by operand-load form: 0 = plain operands (mhe_conv_tile; see mhe_conv_desc.tile),
+// 1 = producer BatchNorm on load (mhe_conv2d_nhwc with in_scale), 2 = residual-block tail (mhe_conv1x1_residual_in_nhwc) - there variant 7
+// becomes 2 -, 3 = forward form with a residual operand (the streaming kernels do not take it)
 extern "C" int mhe_conv_tile_mode(const mhe_conv_desc *d, int mode) {
     if (!d || mode < 0 || mode > 3) return -1;
     static const float dummy = 0.f;
     conv::Params p{};
-    p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-    const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-    p.M = d->B * Ho * Wo;
+    conv::fill_geometry(p, *d);
     p.force = d->tile - 1;
-    const int bke = d->dtype == MHE_F32 ? 32 : 64;
-    p.Kpad = (d->KH * d->KW * d->Cin + bke - 1) / bke * bke;
     if (mode == 1 || mode == 2) p.in_scale = &dummy;
     if (mode == 2) p.x2 = &dummy;
-    if (mode == 3) p.residual = &dummy;            // forward form with a residual operand (the streaming kernels do not take it)
-    return conv::choose_tile(p, d->Cin % bke == 0, d->dtype == MHE_BF16);
+    if (mode == 3) p.residual = &dummy;
+    return conv::choose_tile(p, d->Cin % (8 * conv::elem_chunk(d->dtype)) == 0, d->dtype == MHE_BF16);
 }
+
+extern "C" int mhe_conv_tile(const mhe_conv_desc *d) { return mhe_conv_tile_mode(d, 0); }
 
 extern "C" int mhe_stem_conv7x7s2(const float *x_nchw, const void *w, void *y, mhe_stat_t *stats, int B, int H, int W, int dtype,
                                   void *stream) {
@@ -1076,7 +1066,7 @@ extern "C" int mhe_bn_act_avgpool_nhwc(const void *x, const float *scale, const 
 
 extern "C" int mhe_nchw_to_nhwc(const float *x, void *y, int B, int C, int H, int W, int dtype, void *stream) {
     MHE_REQUIRE(x && y && B > 0 && C > 0 && H > 0 && W > 0, "mhe_nchw_to_nhwc: bad arguments");
-    const int Cp = (C + elem_chunk(dtype) - 1) / elem_chunk(dtype) * elem_chunk(dtype);
+    const int Cp = (C + conv::elem_chunk(dtype) - 1) / conv::elem_chunk(dtype) * conv::elem_chunk(dtype);
     const size_t n = (size_t)B * H * W;
     if (dtype == MHE_F32)
         hipLaunchKernelGGL(conv::nchw_to_nhwc_kernel<float>, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, x,

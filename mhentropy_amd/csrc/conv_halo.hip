@@ -339,13 +339,16 @@ __global__ void halo_pack_kernel(const u16 *w, u16 *out, int Cout, int Cin, int 
 
 using namespace mhe;
 
+// the entries' fixed geometry - bf16 3x3, stride 1, pad 1 on a [B, H, W] map - into p; false: no such map of fewer than 2^31 pixels
+static bool halo_geometry(conv::Params &p, int B, int H, int W, int Cin, int Cout) {
+    const mhe_conv_desc d = {B, H, W, Cin, Cout, 3, 3, 1, 1, MHE_BF16};
+    p.force = -1;
+    return conv::fill_geometry(p, d) < (1ll << 31) && B > 0 && H > 0 && W > 0;
+}
+
 extern "C" int mhe_conv3x3_halo_supported(int B, int H, int W, int Cin, int Cout) {
     conv::Params p{};
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = p.KW = 3; p.stride = 1; p.pad = 1; p.Ho = H; p.Wo = W;
-    const long long M = (long long)B * H * W;
-    if (B <= 0 || H <= 0 || W <= 0 || M >= (1ll << 31)) return 0;
-    p.M = (int)M;
-    return conv::halo_supports(p) ? 1 : 0;
+    return halo_geometry(p, B, H, W, Cin, Cout) && conv::halo_supports(p) ? 1 : 0;
 }
 
 extern "C" int mhe_conv3x3_halo_pack_bf16(const void *w, void *w_halo, int Cout, int Cin, void *stream) {
@@ -368,11 +371,7 @@ extern "C" int mhe_conv3x3_halo_nhwc(int B, int H, int W, int Cin, int Cout, con
     conv::Params p{};
     p.x = x; p.w = w_halo; p.y = y; p.in_scale = in_scale; p.in_shift = in_shift; p.relu_in = relu_in; p.a_out = a_out; p.stats = stats;
     p.residual = residual; p.mask = mask; p.bn_y[0] = bn_y0; p.bn_mi[0] = bn_mean_invstd0; p.bn_stats[0] = bn_stats0;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = p.KW = 3; p.stride = 1; p.pad = 1; p.Ho = H; p.Wo = W;
-    const long long M = (long long)B * H * W;
-    MHE_REQUIRE(B > 0 && H > 0 && W > 0 && M < (1ll << 31), "mhe_conv3x3_halo_nhwc: bad geometry");
-    p.M = (int)M; p.Kpad = 9 * Cin;
-    p.force = -1;
+    MHE_REQUIRE(halo_geometry(p, B, H, W, Cin, Cout), "mhe_conv3x3_halo_nhwc: bad geometry");
     MHE_REQUIRE(conv::halo_supports(p), "mhe_conv3x3_halo_nhwc: geometry not taken (3x3 stride 1 pad 1, W 32 / 16, Cin %% 64, Cin <= 512, Cout %% 128)");
     return conv::launch_halo(p, (hipStream_t)stream);
 }
@@ -385,10 +384,7 @@ extern "C" int mhe_conv3x3_halo_dgrad_bn_nhwc(int B, int H, int W, int Cin, int 
     conv::Params p{};
     p.x = g; p.x2 = y_raw; p.rev_coef = coef; p.w = w_halo; p.y = gx; p.a_out = gy_out;
     p.residual = residual; p.mask = mask; p.bn_y[0] = bn_y0; p.bn_mi[0] = bn_mean_invstd0; p.bn_stats[0] = bn_stats0;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = p.KW = 3; p.stride = 1; p.pad = 1; p.Ho = H; p.Wo = W;
-    const long long M = (long long)B * H * W;
-    MHE_REQUIRE(B > 0 && H > 0 && W > 0 && M < (1ll << 31), "mhe_conv3x3_halo_dgrad_bn_nhwc: bad geometry");
-    p.M = (int)M; p.Kpad = 9 * Cin; p.force = -1;
+    MHE_REQUIRE(halo_geometry(p, B, H, W, Cin, Cout), "mhe_conv3x3_halo_dgrad_bn_nhwc: bad geometry");
     MHE_REQUIRE(conv::halo_supports(p), "mhe_conv3x3_halo_dgrad_bn_nhwc: geometry not taken (see mhe_conv3x3_halo_nhwc)");
     return conv::launch_halo(p, (hipStream_t)stream);
 }

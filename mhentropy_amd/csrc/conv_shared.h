@@ -55,6 +55,24 @@ __device__ __forceinline__ long out_pixel(const Params &p, int m) {
 constexpr int NSH = fx::NSH;     // statistic shards: block b adds into shard b % NSH
 constexpr int MAXC = 2048;       // largest Cin whose BatchNorm affine is staged in LDS
 
+inline int elem_chunk(int dtype) { return dtype == MHE_F32 ? 4 : 8; }      // elements of a 16-byte chunk
+
+// Host side, the one place a descriptor's geometry becomes Params: B ... pad, the output map, M and Kpad (the packer zero-pads the weight
+// rows to whole K tiles of 8 chunks; p.Cin2, where the caller has set it, counts).  same_map: one output per input position whatever the
+// taps say (a parity class of the stride-2 data gradient, the bottleneck tails).  Returns the output pixel count and leaves its low 32 bits
+// in p.M: each caller refuses a count outside (0, 2^31) in its own words.
+inline long long fill_geometry(Params &p, const mhe_conv_desc &d, bool same_map = false) {
+    p.B = d.B; p.H = d.H; p.W = d.W; p.Cin = d.Cin; p.Cout = d.Cout; p.KH = d.KH; p.KW = d.KW; p.stride = d.stride; p.pad = d.pad;
+    const int st = d.stride > 0 ? d.stride : 1;      // (stride <= 0 is the caller's to refuse: do not divide by it first)
+    p.Ho = same_map ? d.H : (d.H + 2 * d.pad - d.KH) / st + 1;
+    p.Wo = same_map ? d.W : (d.W + 2 * d.pad - d.KW) / st + 1;
+    const long long M = (long long)p.B * p.Ho * p.Wo;
+    p.M = (int)M;
+    const int bke = 8 * elem_chunk(d.dtype);
+    p.Kpad = (d.KH * d.KW * d.Cin + p.Cin2 + bke - 1) / bke * bke;
+    return M;
+}
+
 template <typename T> struct El;
 template <> struct El<float> { static constexpr int CE = 4; };
 template <> struct El<u16>   { static constexpr int CE = 8; };

@@ -789,40 +789,142 @@ static bool takes_slabs(const mhe_conv_desc *d, int gz) {
     return gz <= 64 && (size_t)d->Cout * d->KH * d->KW * d->Cin >= 131072;
 }
 
+static bool valid_geometry(const mhe_conv_desc *d) {
+    return d && d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0;
+}
+static size_t slab_floats(const mhe_conv_desc *d, const WgradPlan &w, int nbatch = 1) {
+    return takes_slabs(d, w.gz) ? (size_t)nbatch * w.gz * (w.gy * w.BM) * (size_t)(w.gx * w.BN) : 0;
+}
+
 // which instantiation a launch takes (bench.py names the kernel it times as rocprofv3 prints it): BM * 1000 + BN, + 1,000,000 for the
 // LDS-DMA kernel, + 2,000,000 for the register-staged bf16 kernel (0 + ... : the f32 / generic kernel)
 extern "C" int mhe_conv_wgrad_variant(const mhe_conv_desc *d, int Ho, int Wo, int nbatch) {
-    if (!d || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 || d->stride <= 0 || nbatch < 1) return -1;
+    if (!valid_geometry(d) || nbatch < 1) return -1;
     const WgradPlan w = plan_wgrad(d, Ho, Wo, nbatch);
     return w.BM * 1000 + w.BN + (w.bf16k && w.dma ? 1000000 : w.bf16k ? 2000000 : 0);
 }
 
+// measured in round 2 (tools/wgrad_bench.py, SLABS=0/1) with the serial reducer: slabs win 3-25 % from ~16 output tiles up (<= 64
+// slices each) and lost below that (many thin slices of a small dW) - the reducer now walks those 16 abreast
 extern "C" size_t mhe_conv_wgrad_workspace_floats(const mhe_conv_desc *d) {
-    if (!d || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 || d->stride <= 0) return 0;
-    const WgradPlan w = plan_wgrad(d);
-    // measured in round 2 (tools/wgrad_bench.py, SLABS=0/1) with the serial reducer: slabs win 3-25 % from ~16 output tiles up (<= 64
-    // slices each) and lost below that (many thin slices of a small dW) - the reducer now walks those 16 abreast
-    return takes_slabs(d, w.gz) ? (size_t)w.gz * (w.gy * w.BM) * (size_t)(w.gx * w.BN) : 0;
+    return valid_geometry(d) ? slab_floats(d, plan_wgrad(d)) : 0;
+}
+
+// what the rect and the grouped form add to a problem (the defaults: neither): the width direction's own stride / left padding, a given
+// output size, and nbatch problems side by side at strides in elements (x, gy) and floats (dw)
+struct WgradExtras { int stride_w = 0, pad_w = -1, Ho = 0, Wo = 0, nbatch = 1; long x_bs = 0, gy_bs = 0, dw_bs = 0; };
+
+// one problem, checked and written into Params but for what the launch plan decides (chunk, Mp, Np, ws, direct, gz); `entry` and `tag`
+// (" (problem i)" of a list, or "") frame the messages
+static int fill_problem(wgrad::Params &p, const char *entry, const char *tag, const mhe_conv_desc *d, const void *x, const void *gy, float *dw, int ldw,
+                        const WgradExtras &e) {
+    MHE_REQUIRE(d && x && gy && dw, "%s: null pointer%s", entry, tag);
+    MHE_REQUIRE(valid_geometry(d) && d->pad >= 0, "%s: bad geometry%s", entry, tag);
+    MHE_REQUIRE(d->Cin % 4 == 0 && d->Cout % 4 == 0, "%s: Cin=%d and Cout=%d must be multiples of 4%s", entry, d->Cin, d->Cout, tag);
+    MHE_REQUIRE(d->dtype == MHE_F32 || d->dtype == MHE_BF16, "%s: dtype=%d%s", entry, d->dtype, tag);
+    p.x = x; p.gy = gy; p.dw = dw;
+    p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
+    p.stride_w = e.stride_w > 0 ? e.stride_w : d->stride; p.pad_w = e.pad_w >= 0 ? e.pad_w : d->pad;
+    p.Ho = e.Ho > 0 ? e.Ho : (d->H + 2 * d->pad - d->KH) / d->stride + 1;
+    p.Wo = e.Wo > 0 ? e.Wo : (d->W + 2 * d->pad - d->KW) / d->stride + 1;
+    MHE_REQUIRE(p.Ho > 0 && p.Wo > 0, "%s: empty output%s", entry, tag);
+    p.N = d->KH * d->KW * d->Cin;
+    p.ldw = ldw > 0 ? ldw : p.N;
+    MHE_REQUIRE(p.ldw >= p.N, "%s: ldw=%d < KH*KW*Cin=%d%s", entry, ldw, p.N, tag);
+    p.P = (long)d->B * p.Ho * p.Wo;
+    if (e.nbatch > 1) { p.x_bs = e.x_bs; p.gy_bs = e.gy_bs; p.dw_bs = e.dw_bs; }
+    return MHE_OK;
+}
+
+// the LDS-DMA kernel's additions to a filled problem: reciprocals, operand sizes, the plain-rows flag
+static void fill_dma(wgrad::DmaParams &dp) {
+    const wgrad::Params &p = dp.p;
+    dp.rcp_wo = (unsigned)((0x100000000ull + p.Wo - 1) / p.Wo); dp.rcp_ho = (unsigned)((0x100000000ull + p.Ho - 1) / p.Ho);
+    dp.x_bytes = (unsigned)((size_t)p.B * p.H * p.W * p.Cin * 2); dp.gy_bytes = (unsigned)((size_t)p.P * p.Cout * 2);
+    dp.plain = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.stride_w == 1 && p.pad_w == 0;
+}
+
+// the tile classes of the MFMA kernels, one place: f(Tile<BM, BN, WM, WN>) for the plan's class.  big exists on the LDS-DMA kernels only
+// (plan_wgrad), on sixteen waves unless MHE_WGRAD_W16=0
+template <int BM_, int BN_, int WM_, int WN_> struct Tile { static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_; };
+static bool wgrad_w16() { static const int w16 = getenv("MHE_WGRAD_W16") ? atoi(getenv("MHE_WGRAD_W16")) : 1; return w16 != 0; }
+template <typename F>
+static void for_tile(const WgradPlan &w, F &&f) {
+    if (w.big && wgrad_w16()) f(Tile<256, 256, 4, 4>{});
+    else if (w.big) f(Tile<256, 256, 4, 2>{});
+    else if (w.narrow) { if (w.small) f(Tile<64, 64, 2, 2>{}); else f(Tile<128, 64, 4, 1>{}); }
+    else { if (w.small) f(Tile<64, 128, 1, 4>{}); else f(Tile<128, 128, 2, 2>{}); }
 }
 
 static int wgrad_entry(const mhe_conv_desc *d, const void *x, const void *gy, float *dw, int ldw, float *ws, size_t ws_floats, void *stream,
-                       int stride_w = 0, int pad_w = -1, int Ho_ = 0, int Wo_ = 0, int nbatch = 1, long x_bs = 0, long gy_bs = 0, long dw_bs = 0);
+                       const WgradExtras &e = {}) {
+    wgrad::Params p{};
+    if (int rc = fill_problem(p, "mhe_conv_wgrad_nhwc", "", d, x, gy, dw, ldw, e)) return rc;
+    const WgradPlan w = plan_wgrad(d, e.Ho, e.Wo, e.nbatch);
+    const int nbatch = e.nbatch, gz = w.gz;
+    p.chunk = (int)w.chunk; p.Mp = w.gy * w.BM; p.Np = w.gx * w.BN;
+    const size_t need = (size_t)nbatch * gz * p.Mp * p.Np;
+    // a workspace was passed for a launch that takes slabs, but it is too small: fail (round 4 fell back to order-dependent f32 atomics without
+    // a word - the bit-reproducibility the train step asserts would have been gone silently; ADVICE r4)
+    MHE_REQUIRE(!(ws && takes_slabs(d, gz) && need > ws_floats), "mhe_conv_wgrad_ws_nhwc: workspace of %zu floats, this launch needs %zu (mhe_conv_wgrad_workspace_floats)",
+                ws_floats, need);
+    p.ws = (ws && takes_slabs(d, gz)) ? ws : nullptr;
+    MHE_REQUIRE(nbatch == 1 || (w.dma && (long)gz * nbatch < 65536), "mhe_conv_wgrad_batched_nhwc: the grouped form runs on the LDS-DMA kernel (bf16, operands below 2 GiB)");
+    if (nbatch > 1) p.gz = gz;
+    dim3 grid(w.gx, w.gy, gz * nbatch);
+    const dim3 block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (d->dtype == MHE_F32) {
+        if (w.small) hipLaunchKernelGGL((wgrad::wgrad_kernel<float, 64, 128>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((wgrad::wgrad_kernel<float, 128, 128>), grid, block, 0, s, p);
+    } else if (w.bf16k && w.dma) {
+        wgrad::DmaParams dp;
+        dp.p = p;
+        fill_dma(dp);
+        static const int xcd_env = getenv("MHE_WGRAD_XCD") ? atoi(getenv("MHE_WGRAD_XCD")) : 1;
+        dp.nzt = gz * nbatch;
+        dp.xcd = xcd_env && w.xcd && dp.nzt >= 8;
+        if (dp.xcd) grid.z = (unsigned)((dp.nzt + 7) / 8 * 8);
+        for_tile(w, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((wgrad::wgrad_dma_kernel<T::BM, T::BN, T::WM, T::WN>), grid, dim3(64 * T::WM * T::WN), 0, s, dp);
+        });
+    } else if (w.bf16k) {
+        for_tile(w, [&](auto t) {
+            using T = decltype(t);
+            if constexpr (T::BM <= 128) hipLaunchKernelGGL((wgrad::wgrad_bf16_kernel<T::BM, T::BN, T::WM, T::WN>), grid, block, 0, s, p);
+        });
+    } else {
+        if (w.small) hipLaunchKernelGGL((wgrad::wgrad_kernel<u16, 64, 128>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((wgrad::wgrad_kernel<u16, 128, 128>), grid, block, 0, s, p);
+    }
+    if (int rc = check_launch("wgrad_kernel")) return rc;
+    if (p.ws) {
+        const long n = (long)d->Cout * (p.N / 4);
+        const dim3 rg((unsigned)((n + 63) / 64), (unsigned)nbatch);
+        if (gz > 64) hipLaunchKernelGGL(wgrad::slab_reduce_kernel<16>, rg, dim3(1024), 0, s, p.ws, dw, gz, p.Mp, p.Np, d->Cout, p.N, p.ldw, e.dw_bs);
+        else if (gz > 8 || n < 65536) hipLaunchKernelGGL(wgrad::slab_reduce_kernel<4>, rg, dim3(256), 0, s, p.ws, dw, gz, p.Mp, p.Np, d->Cout, p.N, p.ldw, e.dw_bs);
+        else hipLaunchKernelGGL(wgrad::slab_reduce_kernel<1>, rg, dim3(64), 0, s, p.ws, dw, gz, p.Mp, p.Np, d->Cout, p.N, p.ldw, e.dw_bs);
+        return check_launch("slab_reduce_kernel");
+    }
+    return MHE_OK;
+}
 
 // nbatch independent weight gradients of one geometry in ONE launch (a grouped GEMM): problem b reads x + b * x_batch_stride and
 // gy + b * gy_batch_stride (elements) and accumulates into dw + b * dw_batch_stride (floats).  The 24 coupling nets of the RealNVP reverse
 // pass (hand/flows.py:105-122; three products per net over the same 16k hypothesis rows) ran as 72 launches of 4 - 16 output tiles each,
 // 30 - 55 us apiece at 150 TF; grouped, each of the three shapes fills the chip.  bf16 operands (the LDS-DMA kernel) only.
 extern "C" size_t mhe_conv_wgrad_batched_workspace_floats(const mhe_conv_desc *d, int nbatch) {
-    if (!d || nbatch < 1 || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 || d->stride <= 0) return 0;
-    const WgradPlan w = plan_wgrad(d, 0, 0, nbatch);
-    return takes_slabs(d, w.gz) ? (size_t)nbatch * w.gz * (w.gy * w.BM) * (size_t)(w.gx * w.BN) : 0;
+    return valid_geometry(d) && nbatch >= 1 ? slab_floats(d, plan_wgrad(d, 0, 0, nbatch), nbatch) : 0;
 }
 
 extern "C" int mhe_conv_wgrad_batched_nhwc(const mhe_conv_desc *d, int nbatch, const void *x, long x_batch_stride, const void *gy, long gy_batch_stride,
                                            float *dw, long dw_batch_stride, int ldw, float *workspace, size_t workspace_floats, void *stream) {
     MHE_REQUIRE(d && nbatch >= 1 && x_batch_stride >= 0 && gy_batch_stride >= 0 && dw_batch_stride >= 0, "mhe_conv_wgrad_batched_nhwc: bad arguments");
     MHE_REQUIRE(d->dtype == MHE_BF16 && d->Cin % 8 == 0 && d->Cout % 8 == 0, "mhe_conv_wgrad_batched_nhwc: bf16 operands with channel counts in multiples of 8");
-    return wgrad_entry(d, x, gy, dw, ldw, workspace, workspace_floats, stream, 0, -1, 0, 0, nbatch, x_batch_stride, gy_batch_stride, dw_batch_stride);
+    WgradExtras e;
+    e.nbatch = nbatch; e.x_bs = x_batch_stride; e.gy_bs = gy_batch_stride; e.dw_bs = dw_batch_stride;
+    return wgrad_entry(d, x, gy, dw, ldw, workspace, workspace_floats, stream, e);
 }
 
 extern "C" int mhe_conv_wgrad_nhwc(const mhe_conv_desc *d, const void *x, const void *gy, float *dw, int ldw, void *stream) {
@@ -838,103 +940,21 @@ extern "C" int mhe_conv_wgrad_ws_nhwc(const mhe_conv_desc *d, const void *x, con
 // stride-2 weight gradient over PIXEL PAIRS - two neighbouring pixels x 4 padded channels = one 8-channel "pixel", kernel 7 x 4, stride
 // (2, 1), padding (3, 2), output width W/2 exactly - which multiplies 224 columns instead of the 392 of 3 channels padded to 8
 extern "C" size_t mhe_conv_wgrad_rect_workspace_floats(const mhe_conv_desc *d, int Ho, int Wo) {
-    if (!d || d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 || d->stride <= 0 || Ho <= 0 || Wo <= 0) return 0;
-    const WgradPlan w = plan_wgrad(d, Ho, Wo);
-    return takes_slabs(d, w.gz) ? (size_t)w.gz * (w.gy * w.BM) * (size_t)(w.gx * w.BN) : 0;
+    return valid_geometry(d) && Ho > 0 && Wo > 0 ? slab_floats(d, plan_wgrad(d, Ho, Wo)) : 0;
 }
 
 extern "C" int mhe_conv_wgrad_rect_nhwc(const mhe_conv_desc *d, int stride_w, int pad_w, int Ho, int Wo, const void *x, const void *gy, float *dw,
                                         int ldw, float *workspace, size_t workspace_floats, void *stream) {
     MHE_REQUIRE(stride_w > 0 && pad_w >= 0 && Ho > 0 && Wo > 0, "mhe_conv_wgrad_rect_nhwc: bad width geometry");
     MHE_REQUIRE(d && (Ho - 1) * d->stride - d->pad < d->H && (Wo - 1) * stride_w - pad_w < d->W, "mhe_conv_wgrad_rect_nhwc: output larger than the input allows");
-    return wgrad_entry(d, x, gy, dw, ldw, workspace, workspace_floats, stream, stride_w, pad_w, Ho, Wo);
-}
-
-static int wgrad_entry(const mhe_conv_desc *d, const void *x, const void *gy, float *dw, int ldw, float *ws, size_t ws_floats, void *stream,
-                       int stride_w, int pad_w, int Ho_, int Wo_, int nbatch, long x_bs, long gy_bs, long dw_bs) {
-    MHE_REQUIRE(d && x && gy && dw, "mhe_conv_wgrad_nhwc: null pointer");
-    MHE_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0,
-                "mhe_conv_wgrad_nhwc: bad geometry");
-    MHE_REQUIRE(d->Cin % 4 == 0 && d->Cout % 4 == 0, "mhe_conv_wgrad_nhwc: Cin=%d and Cout=%d must be multiples of 4", d->Cin, d->Cout);
-    MHE_REQUIRE(d->dtype == MHE_F32 || d->dtype == MHE_BF16, "mhe_conv_wgrad_nhwc: dtype=%d", d->dtype);
-    wgrad::Params p{};
-    p.x = x; p.gy = gy; p.dw = dw;
-    p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW;
-    p.stride = d->stride; p.pad = d->pad;
-    p.stride_w = stride_w > 0 ? stride_w : d->stride; p.pad_w = pad_w >= 0 ? pad_w : d->pad;
-    p.Ho = Ho_ > 0 ? Ho_ : (d->H + 2 * d->pad - d->KH) / d->stride + 1;
-    p.Wo = Wo_ > 0 ? Wo_ : (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-    MHE_REQUIRE(p.Ho > 0 && p.Wo > 0, "mhe_conv_wgrad_nhwc: empty output");
-    p.N = d->KH * d->KW * d->Cin;
-    p.ldw = ldw > 0 ? ldw : p.N;
-    MHE_REQUIRE(p.ldw >= p.N, "mhe_conv_wgrad_nhwc: ldw=%d < KH*KW*Cin=%d", ldw, p.N);
-    p.P = (long)d->B * p.Ho * p.Wo;
-    const WgradPlan w = plan_wgrad(d, Ho_, Wo_, nbatch);
-    const bool small = w.small, bf16k = w.bf16k, narrow = w.narrow;
-    const int gx = w.gx, gyy = w.gy, gz = w.gz;
-    p.chunk = (int)w.chunk;
-    p.Mp = gyy * w.BM; p.Np = gx * w.BN;
-    const size_t need = (size_t)nbatch * gz * p.Mp * p.Np;
-    // a workspace was passed for a launch that takes slabs, but it is too small: fail (round 4 fell back to order-dependent f32 atomics without
-    // a word - the bit-reproducibility the train step asserts would have been gone silently; ADVICE r4)
-    MHE_REQUIRE(!(ws && takes_slabs(d, gz) && need > ws_floats), "mhe_conv_wgrad_ws_nhwc: workspace of %zu floats, this launch needs %zu (mhe_conv_wgrad_workspace_floats)",
-                ws_floats, need);
-    p.ws = (ws && takes_slabs(d, gz)) ? ws : nullptr;
-    MHE_REQUIRE(nbatch == 1 || (w.dma && (long)gz * nbatch < 65536), "mhe_conv_wgrad_batched_nhwc: the grouped form runs on the LDS-DMA kernel (bf16, operands below 2 GiB)");
-    if (nbatch > 1) { p.gz = gz; p.x_bs = x_bs; p.gy_bs = gy_bs; p.dw_bs = dw_bs; }
-    dim3 grid(gx, gyy, gz * nbatch);
-    const dim3 block(256);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t xb = (size_t)d->B * d->H * d->W * d->Cin * 2, gb = (size_t)p.P * d->Cout * 2;
-    const bool use_dma = w.dma;
-    if (d->dtype == MHE_F32) {
-        if (small) hipLaunchKernelGGL((wgrad::wgrad_kernel<float, 64, 128>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((wgrad::wgrad_kernel<float, 128, 128>), grid, block, 0, s, p);
-    } else if (bf16k && use_dma) {
-        wgrad::DmaParams dp;
-        dp.p = p;
-        dp.rcp_wo = (unsigned)((0x100000000ull + p.Wo - 1) / p.Wo); dp.rcp_ho = (unsigned)((0x100000000ull + p.Ho - 1) / p.Ho);
-        dp.x_bytes = (unsigned)xb; dp.gy_bytes = (unsigned)gb;
-        dp.plain = d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && p.stride_w == 1 && p.pad_w == 0;
-        static const int xcd_env = getenv("MHE_WGRAD_XCD") ? atoi(getenv("MHE_WGRAD_XCD")) : 1;
-        dp.nzt = gz * nbatch;
-        dp.xcd = xcd_env && w.xcd && dp.nzt >= 8;
-        if (dp.xcd) grid.z = (unsigned)((dp.nzt + 7) / 8 * 8);
-        static const int w16 = getenv("MHE_WGRAD_W16") ? atoi(getenv("MHE_WGRAD_W16")) : 1;
-        if (w.big && w16) hipLaunchKernelGGL((wgrad::wgrad_dma_kernel<256, 256, 4, 4>), grid, dim3(1024), 0, s, dp);
-        else if (w.big) hipLaunchKernelGGL((wgrad::wgrad_dma_kernel<256, 256, 4, 2>), grid, dim3(512), 0, s, dp);
-        else if (narrow) {
-            if (small) hipLaunchKernelGGL((wgrad::wgrad_dma_kernel<64, 64, 2, 2>), grid, block, 0, s, dp);
-            else hipLaunchKernelGGL((wgrad::wgrad_dma_kernel<128, 64, 4, 1>), grid, block, 0, s, dp);
-        } else {
-            if (small) hipLaunchKernelGGL((wgrad::wgrad_dma_kernel<64, 128, 1, 4>), grid, block, 0, s, dp);
-            else hipLaunchKernelGGL((wgrad::wgrad_dma_kernel<128, 128, 2, 2>), grid, block, 0, s, dp);
-        }
-    } else if (narrow) {
-        if (small) hipLaunchKernelGGL((wgrad::wgrad_bf16_kernel<64, 64, 2, 2>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((wgrad::wgrad_bf16_kernel<128, 64, 4, 1>), grid, block, 0, s, p);
-    } else if (bf16k) {
-        if (small) hipLaunchKernelGGL((wgrad::wgrad_bf16_kernel<64, 128, 1, 4>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((wgrad::wgrad_bf16_kernel<128, 128, 2, 2>), grid, block, 0, s, p);
-    } else {
-        if (small) hipLaunchKernelGGL((wgrad::wgrad_kernel<u16, 64, 128>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((wgrad::wgrad_kernel<u16, 128, 128>), grid, block, 0, s, p);
-    }
-    if (int rc = check_launch("wgrad_kernel")) return rc;
-    if (p.ws) {
-        const long n = (long)d->Cout * (p.N / 4);
-        const dim3 rg((unsigned)((n + 63) / 64), (unsigned)nbatch);
-        if (gz > 64) hipLaunchKernelGGL(wgrad::slab_reduce_kernel<16>, rg, dim3(1024), 0, s, p.ws, dw, gz, p.Mp, p.Np, d->Cout, p.N, p.ldw, dw_bs);
-        else if (gz > 8 || n < 65536) hipLaunchKernelGGL(wgrad::slab_reduce_kernel<4>, rg, dim3(256), 0, s, p.ws, dw, gz, p.Mp, p.Np, d->Cout, p.N, p.ldw, dw_bs);
-        else hipLaunchKernelGGL(wgrad::slab_reduce_kernel<1>, rg, dim3(64), 0, s, p.ws, dw, gz, p.Mp, p.Np, d->Cout, p.N, p.ldw, dw_bs);
-        return check_launch("slab_reduce_kernel");
-    }
-    return MHE_OK;
+    WgradExtras e;
+    e.stride_w = stride_w; e.pad_w = pad_w; e.Ho = Ho; e.Wo = Wo;
+    return wgrad_entry(d, x, gy, dw, ldw, workspace, workspace_floats, stream, e);
 }
 
 // ---- several weight gradients in one launch (see wgrad_dma_multi_kernel) ---------------------------------------------------------------
 namespace {
-struct MultiItemPlan { WgradPlan w; long P; int Ho, Wo, tiles; };
+struct MultiItemPlan { WgradPlan w; long P; int tiles; };
 static long multi_target(bool big) {
     // measured at config C2 on one box (gpurun_out/r5, profiles/EXPERIMENTS.md "Round 5"): 512 / 1024 -> 25.85 ms per train step, 768 / 1024 -> 25.60,
     // 512 / 2048 -> 25.62, 768 / 2048 -> 25.30 (896 / 2048 -> 26.0: a fourth partial round of the one-workgroup-per-CU tile); one launch per layer: 26.0
@@ -968,16 +988,28 @@ static void layout_batch(const mhe_wgrad_item *items, const MultiItemPlan *it, c
         if (gz > 1) lo.ws_total += (size_t)gz * (q.w.gy * q.w.BM) * (size_t)(q.w.gx * q.w.BN);
     }
 }
+// a list's problems planned; false where one is no problem wgrad_entry would take (fill_problem's requirements, without the pointers)
 static bool multi_plan(const mhe_wgrad_item *items, int n, MultiItemPlan *it) {
     for (int i = 0; i < n; ++i) {
         const mhe_conv_desc *d = &items[i].d;
-        if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 || d->stride <= 0 || d->pad < 0) return false;
+        if (!valid_geometry(d) || d->pad < 0 || d->Cin % 4 || d->Cout % 4 || (d->dtype != MHE_F32 && d->dtype != MHE_BF16)) return false;
+        const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1, Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
+        if (Ho <= 0 || Wo <= 0) return false;          // (plan_wgrad divides by them)
         it[i].w = plan_wgrad(d);
-        it[i].Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1; it[i].Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-        it[i].P = (long)d->B * it[i].Ho * it[i].Wo;
+        it[i].P = (long)d->B * Ho * Wo;
         it[i].tiles = it[i].w.gx * it[i].w.gy;
     }
     return true;
+}
+// the next batch of a list: problem i and, where it is a shape of the LDS-DMA kernel, the later unused ones of its tile class.  Returns the batch size;
+// 0: it launches on its own (f32 operands, odd channel counts, or alone in its class - the single launch's plan and reducer are the better ones)
+static int next_batch(const MultiItemPlan *it, int n, int i, bool *used, int *idx) {
+    const WgradPlan &w = it[i].w;
+    if (!(w.bf16k && w.dma)) { used[i] = true; return 0; }
+    int m = 0;
+    for (int j = i; j < n && m < wgrad::MAXMULTI; ++j)
+        if (!used[j] && it[j].w.bf16k && it[j].w.dma && it[j].w.BM == w.BM && it[j].w.BN == w.BN) { idx[m++] = j; used[j] = true; }
+    return m == 1 ? 0 : m;
 }
 }  // namespace
 
@@ -989,41 +1021,34 @@ extern "C" size_t mhe_conv_wgrad_multi_workspace_floats(const mhe_wgrad_item *it
     bool used[256] = {false};
     for (int i = 0; i < n; ++i) {
         if (used[i]) continue;
-        if (!(it[i].w.bf16k && it[i].w.dma)) { used[i] = true; const size_t w = mhe_conv_wgrad_workspace_floats(&items[i].d); if (w > need) need = w; continue; }
-        int idx[wgrad::MAXMULTI], m = 0;
-        for (int j = i; j < n && m < wgrad::MAXMULTI; ++j)
-            if (!used[j] && it[j].w.bf16k && it[j].w.dma && it[j].w.BM == it[i].w.BM && it[j].w.BN == it[i].w.BN) { idx[m++] = j; used[j] = true; }
-        if (m == 1) { const size_t w = mhe_conv_wgrad_workspace_floats(&items[i].d); if (w > need) need = w; continue; }
+        int idx[wgrad::MAXMULTI];
+        const int m = next_batch(it, n, i, used, idx);
         MultiLayout lo;
-        layout_batch(items, it, idx, m, it[i].w.big, lo);
-        if (lo.ws_total > need) need = lo.ws_total;
+        if (m) layout_batch(items, it, idx, m, it[i].w.big, lo);
+        const size_t w = m ? lo.ws_total : mhe_conv_wgrad_workspace_floats(&items[i].d);
+        if (w > need) need = w;
     }
     return need;
 }
 
-template <int BM, int BN, int WM, int WN>
-static void launch_multi(const wgrad::MultiParams &mp, hipStream_t s) {
-    hipLaunchKernelGGL((wgrad::wgrad_dma_multi_kernel<BM, BN, WM, WN>), dim3((unsigned)mp.first[mp.n]), dim3(64 * WM * WN), 0, s, mp);
-}
-
 extern "C" int mhe_conv_wgrad_multi_nhwc(const mhe_wgrad_item *items, int n, float *workspace, size_t workspace_floats, void *stream) {
     MHE_REQUIRE(items && n > 0 && n <= 256, "mhe_conv_wgrad_multi_nhwc: 1 .. 256 problems");
+    for (int i = 0; i < n; ++i) MHE_REQUIRE(valid_geometry(&items[i].d) && items[i].d.pad >= 0, "mhe_conv_wgrad_multi_nhwc: bad geometry");
+    wgrad::Params pr[256];
+    for (int i = 0; i < n; ++i) {
+        char tag[32];
+        snprintf(tag, sizeof(tag), " (problem %d)", i); pr[i] = wgrad::Params{};
+        if (int rc = fill_problem(pr[i], "mhe_conv_wgrad_multi_nhwc", tag, &items[i].d, items[i].x, items[i].gy, items[i].dw, items[i].ldw, {})) return rc;
+    }
     MultiItemPlan it[256];
     MHE_REQUIRE(multi_plan(items, n, it), "mhe_conv_wgrad_multi_nhwc: bad geometry");
-    for (int i = 0; i < n; ++i) MHE_REQUIRE(items[i].x && items[i].gy && items[i].dw, "mhe_conv_wgrad_multi_nhwc: null pointer (problem %d)", i);
     hipStream_t s = (hipStream_t)stream;
     bool used[256] = {false};
     for (int i = 0; i < n; ++i) {
         if (used[i]) continue;
-        if (!(it[i].w.bf16k && it[i].w.dma)) {          // not a shape of the LDS-DMA kernel (f32 operands, odd channel counts): its own launch
-            used[i] = true;
-            if (int rc = wgrad_entry(&items[i].d, items[i].x, items[i].gy, items[i].dw, items[i].ldw, workspace, workspace_floats, stream)) return rc;
-            continue;
-        }
-        int idx[wgrad::MAXMULTI], m = 0;
-        for (int j = i; j < n && m < wgrad::MAXMULTI; ++j)
-            if (!used[j] && it[j].w.bf16k && it[j].w.dma && it[j].w.BM == it[i].w.BM && it[j].w.BN == it[i].w.BN) { idx[m++] = j; used[j] = true; }
-        if (m == 1) {            // alone in its tile class: the single launch's own plan (one resident round of workgroups, its reducer) is the better one
+        int idx[wgrad::MAXMULTI];
+        const int m = next_batch(it, n, i, used, idx);
+        if (!m) {
             if (int rc = wgrad_entry(&items[i].d, items[i].x, items[i].gy, items[i].dw, items[i].ldw, workspace, workspace_floats, stream)) return rc;
             continue;
         }
@@ -1037,24 +1062,14 @@ extern "C" int mhe_conv_wgrad_multi_nhwc(const mhe_wgrad_item *items, int n, flo
         mp.n = m; mr.n = 0;
         int first = 0, rfirst = 0;
         for (int k = 0; k < m; ++k) {
-            const mhe_wgrad_item &q = items[idx[k]];
             const MultiItemPlan &pl = it[idx[k]];
-            const mhe_conv_desc *d = &q.d;
             wgrad::DmaParams &dp = mp.p[k];
             wgrad::Params &p = dp.p;
-            p.x = q.x; p.gy = q.gy; p.dw = q.dw;
-            p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout; p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-            p.stride_w = d->stride; p.pad_w = d->pad; p.Ho = pl.Ho; p.Wo = pl.Wo;
-            p.N = d->KH * d->KW * d->Cin; p.ldw = q.ldw > 0 ? q.ldw : p.N;
-            MHE_REQUIRE(p.ldw >= p.N, "mhe_conv_wgrad_multi_nhwc: ldw=%d < KH*KW*Cin=%d (problem %d)", q.ldw, p.N, idx[k]);
-            p.P = pl.P; p.chunk = (int)lo.chunk[k];
-            p.Mp = pl.w.gy * pl.w.BM; p.Np = pl.w.gx * pl.w.BN;
             const int gz = lo.gz[k];
-            p.ws = gz > 1 ? workspace + lo.ws_off[k] : nullptr;
-            p.direct = gz == 1;
-            dp.rcp_wo = (unsigned)((0x100000000ull + p.Wo - 1) / p.Wo); dp.rcp_ho = (unsigned)((0x100000000ull + p.Ho - 1) / p.Ho);
-            dp.x_bytes = (unsigned)((size_t)d->B * d->H * d->W * d->Cin * 2); dp.gy_bytes = (unsigned)((size_t)p.P * d->Cout * 2);
-            dp.plain = d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0;
+            p = pr[idx[k]];
+            p.chunk = (int)lo.chunk[k]; p.Mp = pl.w.gy * pl.w.BM; p.Np = pl.w.gx * pl.w.BN;
+            p.ws = gz > 1 ? workspace + lo.ws_off[k] : nullptr; p.direct = gz == 1;
+            fill_dma(dp);
             dp.nzt = gz;
             // a problem cut at least 8 ways takes the single launch's XCD-aware order (8 slices side by side, one per XCD, their tiles next to each
             // other in time: slot = 8 * (tile + tiles * (slice / 8)) + slice % 8); fewer slices: tile-major within the slice
@@ -1065,18 +1080,16 @@ extern "C" int mhe_conv_wgrad_multi_nhwc(const mhe_wgrad_item *items, int n, flo
             first += wgs;
             if (gz > 1) {
                 const int r = mr.n++;
-                mr.ws[r] = p.ws; mr.dw[r] = q.dw; mr.gz[r] = gz; mr.Mp[r] = p.Mp; mr.Np[r] = p.Np; mr.M[r] = d->Cout; mr.N[r] = p.N; mr.ldw[r] = p.ldw;
+                mr.ws[r] = p.ws; mr.dw[r] = p.dw; mr.gz[r] = gz; mr.Mp[r] = p.Mp; mr.Np[r] = p.Np; mr.M[r] = p.Cout; mr.N[r] = p.N; mr.ldw[r] = p.ldw;
                 mr.first[r] = rfirst;
-                rfirst += (int)(((long)d->Cout * (p.N / 4) + 63) / 64);
+                rfirst += (int)(((long)p.Cout * (p.N / 4) + 63) / 64);
             }
         }
         mp.first[m] = first; mr.first[mr.n] = rfirst;
-        const WgradPlan &w = it[i].w;
-        static const int w16 = getenv("MHE_WGRAD_W16") ? atoi(getenv("MHE_WGRAD_W16")) : 1;
-        if (w.big && w16) launch_multi<256, 256, 4, 4>(mp, s);
-        else if (w.big) launch_multi<256, 256, 4, 2>(mp, s);
-        else if (w.narrow) { if (w.small) launch_multi<64, 64, 2, 2>(mp, s); else launch_multi<128, 64, 4, 1>(mp, s); }
-        else { if (w.small) launch_multi<64, 128, 1, 4>(mp, s); else launch_multi<128, 128, 2, 2>(mp, s); }
+        for_tile(it[i].w, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((wgrad::wgrad_dma_multi_kernel<T::BM, T::BN, T::WM, T::WN>), dim3((unsigned)first), dim3(64 * T::WM * T::WN), 0, s, mp);
+        });
         if (int rc = check_launch("wgrad_dma_multi_kernel")) return rc;
         if (mr.n) {
             hipLaunchKernelGGL(wgrad::slab_reduce_multi_kernel, dim3((unsigned)rfirst), dim3(256), 0, s, mr);
