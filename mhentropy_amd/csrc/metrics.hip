@@ -230,6 +230,10 @@ extern "C" int mhe_metrics_split_f32(const float *xyz_err, const float *xyz_spre
 // Top-Q hypothesis selection of MHEnt.sample (hand/network.py:866-871): per image keep the Q hypotheses
 // of highest log q, in descending order (torch.topk semantics), and gather their flow samples.
 // One wavefront per image; rank by counting (N is a few hundred at most).
+// The rank is a strict total order over ALL scores, torch.topk's: NaN ranks above every number (+inf included), NaNs among themselves and
+// equal numbers (-0.0 == +0.0) go by index, lower first.  So the ranks of an image are a permutation of 0 .. N-1 whatever the scores are and
+// every one of the Q slots of idx_out is written before the gather reads it (with `u > v || (u == v && m < n)` alone every NaN row had rank 0
+// and counted in nobody's rank: a diverged flow left Q - K slots of idx_out unwritten and the gather took them as row indices).
 namespace mhe { namespace metrics {
 __global__ __launch_bounds__(256) void topk_gather_kernel(const float *__restrict__ score, const float *__restrict__ rows,
                                                           int *__restrict__ idx_out, float *__restrict__ rows_out,
@@ -238,10 +242,13 @@ __global__ __launch_bounds__(256) void topk_gather_kernel(const float *__restric
     if (b >= B) return;
     for (int n = lane; n < N; n += 64) {
         const float v = score[(size_t)n * B + b];
+        const bool vnan = v != v;
         int rank = 0;
         for (int m = 0; m < N; ++m) {
             const float u = score[(size_t)m * B + b];
-            rank += (u > v || (u == v && m < n)) ? 1 : 0;
+            const bool unan = u != u;
+            const bool above = unan ? !vnan : u > v, level = unan ? vnan : u == v;      // (u > v and u == v are false for a NaN v)
+            rank += (above || (level && m < n)) ? 1 : 0;
         }
         if (rank < Q) idx_out[(size_t)rank * B + b] = n;
     }
