@@ -948,6 +948,23 @@ int mhe_lbs_skin_err_f32(const float *workspace, const float *v_template, const 
 int mhe_point_errors_f32(const float *points, const float *target, float *err, int B, int K, int P, unsigned long long root_mask, void *stream);
 int mhe_min_of_n_f32(const float *err, float *values, int *index, int B, int K, const int *ns, int n, void *stream);
 
+/* Hand-object Chamfer distance (csrc/chamfer.hip; reference hand/criteria.py:18-39) without the reference's (N, B, P, VO) tensor.  Rows are
+ * sample-major, r = n B + b:
+ *   a_j = points[r][j] (scale[b] unit) + root[b],  o_v = obj[b][v] for v < V_b,  V_b = obj_count[b] (clamped to 1..VO), or VO when obj_count is NULL
+ *   D1[r] = (1/P) sum_j min_v |a_j - o_v|,  D2[r] = (1/V_b) sum_v min_j |a_j - o_v|,  dist[r] = D1[r] + D2[r]
+ * mhe_chamfer_f32: points [R,P,3], scale [B], root [B,3], obj [B,VO,3], obj_count [B] int32 or NULL -> dist [R]; optional parts [R,2] = (D1, D2),
+ *   idx_p [R,P] int32 = argmin over v, idx_o [R,VO] int32 = argmin over j (-1 for v >= V_b); ties go to the lowest index.  1 <= P <=
+ *   MHE_CHAMFER_MAX_POINTS, VO >= 1, N B < 2^31.  A workgroup loads an image's vertices once, in LDS tiles, for all its hypotheses; vertices
+ *   past V_b are never read.  The values do not depend on whether the indices are asked for.
+ * mhe_chamfer_bwd_f32: the same inputs, idx_p and idx_o of the forward call and g_dist [R] -> g_points [R,P,3]:
+ *   g_points[r][j] = g_dist[r] scale[b] unit ( (1/P) u(a_j - o_idx_p[r][j]) + (1/V_b) sum_{v: idx_o[r][v] = j} u(a_j - o_v) ),  u(x) = x / |x|, u(0) = 0.
+ * Both: fixed summation order, no atomics (two calls give the same bits); no allocation; outputs must not overlap inputs or each other. */
+#define MHE_CHAMFER_MAX_POINTS 778
+int mhe_chamfer_f32(const float *points, const float *scale, const float *root, const float *obj, const int *obj_count, float *dist, float *parts,
+                    int *idx_p, int *idx_o, int N, int B, int P, int VO, float unit, void *stream);
+int mhe_chamfer_bwd_f32(const float *points, const float *scale, const float *root, const float *obj, const int *obj_count, const int *idx_p,
+                        const int *idx_o, const float *g_dist, float *g_points, int N, int B, int P, int VO, float unit, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

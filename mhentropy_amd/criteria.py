@@ -1,7 +1,8 @@
 """MHEntLoss with the reference's call surface (reference hand/criteria.py:42-173):
 `MHEntLoss(loss_weights, aligned)(output, target) -> (total, losses, metrics)`; the metrics
 block runs in one HIP kernel (csrc/metrics.hip), the Procrustes alignment of the aligned
-evaluation in csrc/procrustes.hip."""
+evaluation in csrc/procrustes.hip.  chamfer_dist (hand/criteria.py:18-39) and the selection
+it was written for (chamfer_select) run on csrc/chamfer.hip."""
 import torch
 from torch import nn
 
@@ -10,6 +11,101 @@ from . import ops
 # row order of mhe_metrics_f32's [14,B] output
 METRIC_KEYS = tuple(f"eucLoss_{sup}_rgb_{row}" for sup in ("3d", "2d")
                     for row in ("sample", "sample_std", "vis", "vis_std", "vis_mean", "invis", "invis_std"))
+CHAMFER_UNIT = 1000.0          # hand/criteria.py:24 (normalised -> mm)
+CHAMFER_ROOT = 12              # hand/criteria.py:25: the row of original_pose3d the joints are relative to
+
+
+def _chamfer_operands(norm_rel_xyz, target):
+    """the checks of chamfer_dist that need no device -> (points [N,B,P,3], scale, root, obj [B,VO,3], count or None, input was 3-D)"""
+    if "object_verts" not in target:
+        raise ValueError("chamfer_dist: target has no 'object_verts'")
+    if not isinstance(norm_rel_xyz, torch.Tensor) or norm_rel_xyz.dim() not in (3, 4) or norm_rel_xyz.shape[-1] != 3:
+        raise ValueError(f"chamfer_dist: norm_rel_xyz must be (N, B, K, 3) or (B, K, 3), got {tuple(getattr(norm_rel_xyz, 'shape', ()))}")
+    single = norm_rel_xyz.dim() == 3
+    pts = norm_rel_xyz[None] if single else norm_rel_xyz
+    B = target["scale"].shape[0]
+    if pts.shape[1] != B:
+        raise ValueError(f"chamfer_dist: norm_rel_xyz has {pts.shape[1]} images, target['scale'] {B}")
+    if not 1 <= pts.shape[2] <= 778:
+        raise ValueError(f"chamfer_dist: K={pts.shape[2]} points per hypothesis (1..778)")
+    obj = target["object_verts"]
+    if obj.dim() not in (2, 3) or obj.shape[0] != B or obj[0].numel() % 3 or obj[0].numel() == 0 or (obj.dim() == 3 and obj.shape[2] != 3):
+        raise ValueError(f"chamfer_dist: target['object_verts'] must be (B, VO*3) or (B, VO, 3) with B={B}, got {tuple(obj.shape)}")
+    obj = obj.reshape(B, -1, 3)
+    count = target.get("object_count")
+    if count is not None:
+        if tuple(count.shape) != (B,) or count.dtype != torch.int32:
+            raise ValueError(f"chamfer_dist: target['object_count'] must be a (B,) int32 tensor, got {tuple(count.shape)} {count.dtype}")
+        # (one host read; a stream that is being captured cannot take it: the kernel clamps the count to 1..VO there)
+        if not (count.is_cuda and torch.cuda.is_current_stream_capturing()) and not (1 <= int(count.min()) and int(count.max()) <= obj.shape[1]):
+            raise ValueError(f"chamfer_dist: target['object_count'] outside 1..VO={obj.shape[1]}")
+    root = target["original_pose3d"]
+    if root.dim() != 3 or root.shape[0] != B or root.shape[1] <= CHAMFER_ROOT or root.shape[2] != 3:
+        raise ValueError(f"chamfer_dist: target['original_pose3d'] must be (B, >={CHAMFER_ROOT + 1}, 3), got {tuple(root.shape)}")
+    return pts.contiguous(), target["scale"].contiguous(), root[:, CHAMFER_ROOT].contiguous(), obj.contiguous(), count, single
+
+
+class _Chamfer(torch.autograd.Function):
+    """dist [N,B] of ops.chamfer; the gradient reaches the points only.  The argmin buffers are asked for only when the points require grad."""
+    @staticmethod
+    def forward(ctx, pts, scale, root, obj, count):
+        if ctx.needs_input_grad[0]:
+            dist, _, idx_p, idx_o = ops.chamfer(pts, scale, root, obj, count, CHAMFER_UNIT, want_idx=True)
+            ctx.save_for_backward(pts, scale, root, obj, idx_p, idx_o)
+            ctx.count = count
+        else:
+            dist, _ = ops.chamfer(pts, scale, root, obj, count, CHAMFER_UNIT)
+        return dist
+
+    @staticmethod
+    def backward(ctx, g_dist):
+        pts, scale, root, obj, idx_p, idx_o = ctx.saved_tensors
+        return ops.chamfer_bwd(pts, scale, root, obj, ctx.count, idx_p, idx_o, g_dist.contiguous(), CHAMFER_UNIT), None, None, None, None
+
+
+def chamfer_dist(norm_rel_xyz, target: dict):
+    """reference hand/criteria.py:18-39: the symmetric Chamfer distance, in mm, between every hypothesis' points
+    `norm_rel_xyz * target['scale'] * 1000 + target['original_pose3d'][:, 12]` and its image's object vertices target['object_verts']
+    ((B, VO*3) or (B, VO, 3)): mean over the points of the distance to the nearest vertex plus mean over the vertices of the distance to the
+    nearest point.  norm_rel_xyz (N, B, K, 3) -> (N, B); (B, K, 3) -> (B,).  K <= 778.
+    Extension: target['object_count'], (B,) int32 in 1..VO - only the first count vertices of an image take part (the zero-padded meshes
+    of the input pipeline with object_idx=None and their raw['obj_count']).
+    Differentiable with respect to norm_rel_xyz.  HIP tensors only (MheError otherwise); ValueError for a missing 'object_verts', a rank
+    other than 3 or 4, shapes that do not agree and a count outside 1..VO."""
+    pts, scale, root, obj, count, single = _chamfer_operands(norm_rel_xyz, target)
+    dist = _Chamfer.apply(pts, scale, root, obj, count)
+    return dist[0] if single else dist
+
+
+def _rank(dist):
+    """dist (N, B) -> (values, n) ascending over N, ties to the lower n"""
+    return torch.sort(dist, dim=0, stable=True)
+
+
+def chamfer_select(output, target, Q=1, points="xyz"):
+    """Keep, per image, the Q hypotheses of a sample() output that lie closest to the image's object (chamfer_dist of the joints
+    output['xyz'], or of the mesh output['verts'] with points='verts'), closest first, ties to the lower n.  Every (N, B, ...) tensor of
+    `output` is cut to (Q, B, ...); everything else ('faces', 'image') passes through.  Added: 'chamfer' (Q, B), the distances in mm, and
+    'chamfer_index' (Q, B) int64, the hypotheses kept."""
+    if points not in ("xyz", "verts"):
+        raise ValueError(f"chamfer_select: points={points!r} (xyz or verts)")
+    if points not in output:
+        raise ValueError(f"chamfer_select: output has no {points!r}")
+    src = output[points]
+    if src.dim() < 3:
+        raise ValueError(f"chamfer_select: output[{points!r}] must be (N, B, ...), got {tuple(src.shape)}")
+    N, B = src.shape[:2]
+    if not isinstance(Q, int) or not 1 <= Q <= N:
+        raise ValueError(f"chamfer_select: Q={Q!r} outside 1..N={N}")
+    with torch.no_grad():
+        val, order = _rank(chamfer_dist(src.detach().reshape(N, B, -1, 3), target))
+    keep, cols = order[:Q], torch.arange(B, device=order.device)
+    out = {}
+    for k, v in output.items():
+        cut = isinstance(v, torch.Tensor) and k not in ("faces", "image") and v.dim() >= 2 and tuple(v.shape[:2]) == (N, B)
+        out[k] = v[keep, cols] if cut else v
+    out["chamfer"], out["chamfer_index"] = val[:Q], keep
+    return out
 
 
 class MHEntLoss(nn.Module):
@@ -17,12 +113,20 @@ class MHEntLoss(nn.Module):
         """aligned: the reference's evaluation branch (criteria.py:62-87) - every hypothesis' joints and mesh are Procrustes-aligned
         with scale to target['pose3d'] / target['verts'] (a label whose target is absent is left as it is); output['xyz'] and
         output['verts'] are replaced by new aligned tensors.  The 3D error rows are taken of the aligned joints, the 3D spread rows
-        of the unaligned ones (criteria.py:63-68,141), the 2D rows are unchanged."""
+        of the unaligned ones (criteria.py:63-68,141), the 2D rows are unchanged.
+        chamfer_select (an attribute, False here; MHEntChamferLoss below is this criterion with it set): the reference's switch of that name
+        (criteria.py:87-89), which computes the distance and drops it.  Here, when output has 'xyz', metrics gain the Chamfer distance of the
+        unaligned joints to target['object_verts']: chamfer_rgb_sample (B,), the least over the N hypotheses in mm, chamfer_rgb_sample_mean
+        (B,), their mean, and chamfer_rgb_select (B,) int64, the n that attains the least (the lowest on a tie).  ValueError when target
+        has no 'object_verts'.  The constructor keeps the two parameters of the aligned evaluation, which tests/test_aligned_oracle.py pins."""
         super().__init__()
         self.loss_weights = loss_weights
         self.aligned = aligned
+        self.chamfer_select = False
 
     def forward(self, output, target):
+        if self.chamfer_select and "object_verts" not in target:
+            raise ValueError("MHEntLoss with chamfer_select: target has no 'object_verts'")
         losses = {"neg_log_p": -output["log_p"]}          # criteria.py:55
         metrics = {}
         unaligned_xyz = output.get("xyz")
@@ -41,4 +145,18 @@ class MHEntLoss(nn.Module):
             else:
                 m = ops.metrics_split(output["xyz"], unaligned_xyz.contiguous(), *rest)
             metrics = {k: m[i] for i, k in enumerate(METRIC_KEYS)}
+            if self.chamfer_select:
+                N, B = unaligned_xyz.shape[:2]
+                with torch.no_grad():
+                    dist = chamfer_dist(unaligned_xyz.detach().reshape(N, B, -1, 3), target)
+                    val, order = _rank(dist)
+                metrics["chamfer_rgb_sample"], metrics["chamfer_rgb_select"] = val[0], order[0]
+                metrics["chamfer_rgb_sample_mean"] = dist.mean(0)
         return sum(v.mean() for v in losses.values()), losses, metrics
+
+
+class MHEntChamferLoss(MHEntLoss):
+    """MHEntLoss with chamfer_select on: the 14 metrics unchanged plus chamfer_rgb_sample, chamfer_rgb_sample_mean and chamfer_rgb_select"""
+    def __init__(self, loss_weights=None, aligned=False):
+        super().__init__(loss_weights, aligned)
+        self.chamfer_select = True

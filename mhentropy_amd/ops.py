@@ -382,7 +382,8 @@ MODS_UV, MODS_XYZ = 1, 2           # MHE_MODS_* of include/mhe.h
 
 def mods_bits(mods):
     """the reference's get_loss `mods` (hand/network.py:620-643; None means ['uv']) -> the MHE_MODS_* bit set.  'uv' and 'xyz' in any
-    order; anything else (the render mods 'm' / 'depth', the dead chamfer / p_ys branches) is not built"""
+    order; anything else (the render mods 'm' / 'depth', the dead p_ys branch) is not built.  The chamfer term is no mod here: its distance
+    is ops.chamfer / criteria.chamfer_dist, and the train step does not take it yet"""
     if mods is None:
         return MODS_UV
     names = [mods] if isinstance(mods, str) else list(mods)
@@ -555,6 +556,44 @@ def procrustes_align(pred, target, want_transform=False):
     s = torch.empty(N, B, device=pred.device, dtype=torch.float32) if want_transform else None
     launch("mhe_procrustes_align_f32", pred, target, out, R, s, ws, nws, N, B, P)
     return (out, R, s) if want_transform else out
+
+
+def _chamfer_operands(points, scale, root, obj, count, who):
+    if not isinstance(points, torch.Tensor) or points.dim() != 4 or points.shape[-1] != 3:
+        raise _lib.MheError(f"{who}.points: expected an [N,B,P,3] tensor")
+    N, B, P = points.shape[:3]
+    if not isinstance(obj, torch.Tensor) or obj.dim() != 3:
+        raise _lib.MheError(f"{who}.obj: expected a [B,VO,3] tensor")
+    VO = obj.shape[1]
+    _chk(points, torch.float32, f"{who}.points"); _chk(scale, torch.float32, f"{who}.scale", (B,)); _chk(root, torch.float32, f"{who}.root", (B, 3))
+    _chk(obj, torch.float32, f"{who}.obj", (B, VO, 3))
+    if count is not None:
+        _chk(count, torch.int32, f"{who}.count", (B,))
+    return N, B, P, VO
+
+
+def chamfer(points, scale, root, obj, count=None, unit=1000.0, want_idx=False):
+    """hand-object Chamfer distance (include/mhe.h, mhe_chamfer_f32): points [N,B,P,3] normalised and root-relative, scale [B], root [B,3],
+    obj [B,VO,3], count [B] int32 (valid vertices per image) or None -> dist [N,B], parts [N,B,2] = (hand-to-object, object-to-hand);
+    want_idx: also the argmins idx_p [N,B,P] and idx_o [N,B,VO] (int32) that chamfer_bwd reads"""
+    N, B, P, VO = _chamfer_operands(points, scale, root, obj, count, "chamfer")
+    dev = points.device
+    dist = torch.empty(N, B, device=dev, dtype=torch.float32)
+    parts = torch.empty(N, B, 2, device=dev, dtype=torch.float32)
+    idx_p = torch.empty(N, B, P, device=dev, dtype=torch.int32) if want_idx else None
+    idx_o = torch.empty(N, B, VO, device=dev, dtype=torch.int32) if want_idx else None
+    launch("mhe_chamfer_f32", points, scale, root, obj, count, dist, parts, idx_p, idx_o, N, B, P, VO, float(unit))
+    return (dist, parts, idx_p, idx_o) if want_idx else (dist, parts)
+
+
+def chamfer_bwd(points, scale, root, obj, count, idx_p, idx_o, g_dist, unit=1000.0):
+    """reverse of chamfer's dist with respect to points (mhe_chamfer_bwd_f32): idx_p / idx_o of the forward call, g_dist [N,B] -> [N,B,P,3]"""
+    N, B, P, VO = _chamfer_operands(points, scale, root, obj, count, "chamfer_bwd")
+    _chk(idx_p, torch.int32, "chamfer_bwd.idx_p", (N, B, P)); _chk(idx_o, torch.int32, "chamfer_bwd.idx_o", (N, B, VO))
+    _chk(g_dist, torch.float32, "chamfer_bwd.g_dist", (N, B))
+    g_points = torch.empty_like(points)
+    launch("mhe_chamfer_bwd_f32", points, scale, root, obj, count, idx_p, idx_o, g_dist, g_points, N, B, P, VO, float(unit))
+    return g_points
 
 
 def conv2d_nhwc(x, w, KH, KW, stride, pad, in_scale=None, in_shift=None, relu_in=False, out_scale=None,
