@@ -32,14 +32,14 @@ SWITCHES = {
     "MHE_GRAM_WGS_64": ("512", "csrc/conv_gram.hip", "workgroups of the 64-channel Gram launch"),
     "MHE_GRAM_WGS_128": ("256", "csrc/conv_gram.hip", "workgroups of the 128-channel Gram launch"),
     # ---- flow / MANO
-    "MHE_FLOW_FRAG": ("1", "flows.py, train.py", "0: second-generation coupling-stack kernel (flow_ns.hip) instead of the fragment-streaming one"),
+    "MHE_FLOW_FRAG": ("1", "flows.py, train_flow.py", "0: second-generation coupling-stack kernel (flow_ns.hip) instead of the fragment-streaming one"),
     "MHE_FLOW_W1_SETS": ("2", "csrc/flow_fwd.hip", "3: a third register set of layer-1 weight fragments (measured equal)"),
     "MHE_GLOW_FUSED": ("1", "glow.py, train_glow.py", "0: the Glow branch's sampling pass layer by layer (~60 launches) instead of the one-launch kernel"),
     "MHE_GLOW_REV_FUSED": ("1", "train_glow.py", "0: the Glow branch's reverse pass over the tape stage by stage instead of the one-launch chain (csrc/glow_rev.hip)"),
     "MHE_MANO_FOUR": ("1", "csrc/mano.hip", "0: one hypothesis per wavefront"),
     "MHE_LBS_MFMA": ("1", "body.py", "0: the body model's skinning with one thread per vertex (csrc/body.hip) instead of the matrix-core kernel (csrc/lbs_skin.hip)"),
     "MHE_MANO_SKIN_MFMA": ("1", "csrc/mano.hip", "0: full-mesh skinning with one thread per vertex (round 1) instead of the matrix-core kernel on bf16 pieces (csrc/mano_skin.hip)"),
-    # ---- train step (train.py / csrc/wgrad.hip, trunk_bwd.hip)
+    # ---- train step (train.py, arena.py, train_flow.py / csrc/wgrad.hip, trunk_bwd.hip)
     "MHE_TRAIN_RECOMPUTE": ("1", "train.py", "0: conv3 of layer1 / layer2 written by the train step's forward pass"),
     "MHE_CONV3_FOLD": ("1", "train.py", "0: conv3 + bn3 reversed by reading y3 (no Gram fold)"),
     "MHE_CONV3_FOLD_CAT": ("1", "train.py", "0: the fold's second product as a launch of its own"),
@@ -57,12 +57,12 @@ SWITCHES = {
     "MHE_BN_BWD_ON_LOAD_WIDE": ("1", "train.py", "0: layer3 / layer4's conv3 reverse without the apply on its load"),
     "MHE_BN_BWD_APPLY_WIDE": ("1", "csrc/trunk_bwd.hip", "0: 8-byte lanes in the apply pass"),
     "MHE_COND_BWD_BF16": ("1", "train.py", "0: the conditioning projections' reverse products on f32 operands"),
-    "MHE_FLOW_WGRAD_GROUPED": ("1", "train.py", "0: one weight-gradient launch per coupling net"),
-    "MHE_FLOW_REV_FUSED": ("1", "train.py", "0: the flow's reverse chain coupling by coupling"),
-    "MHE_FLOW_RECOMPUTE": ("0", "train.py", "1: the reverse pass re-evaluates the flow nets instead of reading emitted activations"),
-    "MHE_LAZY_FALLBACK_TABLES": ("1", "train.py", "0: the fallback operand layouts refreshed every step"),
-    "MHE_POISON_STALE_TABLES": ("0", "train.py", "1 (debug): fallback operand layouts a repack leaves behind are filled with NaN"),
-    "MHE_GATHER_AFFINE": ("1", "train.py", "0: the bf16 operand re-pack from one index per element instead of (base, stride, validity) per eight"),
+    "MHE_FLOW_WGRAD_GROUPED": ("1", "train_flow.py", "0: one weight-gradient launch per coupling net"),
+    "MHE_FLOW_REV_FUSED": ("1", "train_flow.py", "0: the flow's reverse chain coupling by coupling"),
+    "MHE_FLOW_RECOMPUTE": ("0", "train_flow.py", "1: the reverse pass re-evaluates the flow nets instead of reading emitted activations"),
+    "MHE_LAZY_FALLBACK_TABLES": ("1", "arena.py", "0: the fallback operand layouts refreshed every step"),
+    "MHE_POISON_STALE_TABLES": ("0", "arena.py", "1 (debug): fallback operand layouts a repack leaves behind are filled with NaN"),
+    "MHE_GATHER_AFFINE": ("1", "arena.py", "0: the bf16 operand re-pack from one index per element instead of (base, stride, validity) per eight"),
     "MHE_WGRAD_MULTI": ("1", "train.py", "0: one weight-gradient launch per trunk layer instead of one multi-problem launch per gradient bucket and tile shape"),
     "MHE_WGRAD_MULTI_WGS": ("2048", "csrc/wgrad.hip", "workgroups a multi-problem launch of the 4-wave tiles aims at"),
     "MHE_WGRAD_MULTI_WGS_BIG": ("768", "csrc/wgrad.hip", "workgroups a multi-problem launch of the 256 x 256 tile aims at"),

@@ -883,7 +883,7 @@ def test_shortcut_reverse_on_gram_statistics_equals_the_pass_over_its_output(gpu
     ts = TrainStep(model)
     assert ts.shortcut_fold
     ts.forward(x, y, noise=z0, N=N)
-    ud = ts.blocks[0]["ud"]
+    ud = ts.blocks[0].ud
     assert ud.fold_rev and ud.y is not None
     res = {}
     for mode, fold in (("pass", False), ("fold", True), ("fold again", True)):
@@ -1005,29 +1005,29 @@ def test_fallback_operand_layouts_are_refreshed_when_a_fallback_path_runs(gpu_li
 
     model, _ = _model_and_state("resnet18", 512, 2, dtype=torch.bfloat16)
     ts = TrainStep(model, lr=1e-3)                          # steps large enough that stale layouts would be visible (1e-2 diverges in two steps)
-    ts._poison_stale = True                                 # ... and a reader that skipped _need_fallback() would meet NaN (MHE_POISON_STALE_TABLES)
-    assert ts.flow_fused_tables and not ts._fb_keep
+    ts.arena.poison_stale = True                                 # ... and a reader that skipped need_fallback() would meet NaN (MHE_POISON_STALE_TABLES)
+    assert ts.flow_fused_tables and not ts.arena.fb_keep
     for _ in range(2):
         ts.step(x, y, noise=z64, N=64)                      # the one-launch kernels only: the fallback layouts are left behind
-    assert ts._fb_stale and not ts._fb_keep
+    assert ts.arena.fb_stale and not ts.arena.fb_keep
     assert_close(sample_of(model), sample_of(fresh_like(model)), 1e-5, what="sample after eager steps on the one-launch kernels")
-    assert ts._fb_keep and not ts._fb_stale                 # ... refreshed on demand, and kept fresh from now on
+    assert ts.arena.fb_keep and not ts.arena.fb_stale                 # ... refreshed on demand, and kept fresh from now on
     ts.step(x, y, noise=z64, N=64)
-    assert not ts._fb_stale
+    assert not ts.arena.fb_stale
     assert_close(sample_of(model), sample_of(fresh_like(model)), 1e-5, what="sample after a further step")
     # graph replays: the captured repack of a trainer that never needed the layouts does not refresh them
     model2, _ = _model_and_state("resnet18", 512, 2, dtype=torch.bfloat16)
     ts2 = TrainStep(model2, lr=1e-3)
-    ts2._poison_stale = True
+    ts2.arena.poison_stale = True
     gs = GraphedStep(ts2, x, y, noise=z64, N=64)
     assert not gs._fb_in_graph
     gs.replay(); gs.replay()
     torch.cuda.synchronize()
-    assert ts2._fb_stale
+    assert ts2.arena.fb_stale
     assert_close(sample_of(model2), sample_of(fresh_like(model2)), 1e-5, what="sample after graph replays")
     gs.replay()
     torch.cuda.synchronize()
-    assert ts2._fb_stale                                    # (the replay cannot refresh them: stale again, refreshed again on demand)
+    assert ts2.arena.fb_stale                                    # (the replay cannot refresh them: stale again, refreshed again on demand)
     assert_close(sample_of(model2), sample_of(fresh_like(model2)), 1e-5, what="sample after a further replay")
     # a train step that takes the coupling-by-coupling passes itself (16 hypotheses per image) equals the same step of a fresh trainer
     out = ts2.forward_backward(x, y, noise=z16, N=16)
@@ -1086,23 +1086,23 @@ def test_operand_repack_from_affine_groups_equals_the_indexed_repack(gpu_lib):
     torch.manual_seed(2)
     model = harness.build_mhent(backbone="resnet50", tables=synth.mano_tables(0), compute_dtype=torch.bfloat16).cuda().train()
     ts = TrainStep(model)
-    a = ts._arena[torch.bfloat16]
-    assert a["aff"] is not None and a["idx"].numel() > 5e7, "the bf16 arena is expected to be affine in groups of eight"
-    segs = a["aff"][2]
-    assert sum(hi - lo for kind, lo, hi in segs if kind == "idx") < 1e-3 * a["idx"].numel() / 8, segs      # (the stem's taps stay on indices)
+    a = ts.arena.main[torch.bfloat16]
+    assert a.aff is not None and a.idx.numel() > 5e7, "the bf16 arena is expected to be affine in groups of eight"
+    segs = a.aff[2]
+    assert sum(hi - lo for kind, lo, hi in segs if kind == "idx") < 1e-3 * a.idx.numel() / 8, segs      # (the stem's taps stay on indices)
     with torch.no_grad():
         ts.P.add_(torch.randn_like(ts.P) * 1e-3)          # operands of other parameters than the ones packed at construction
     ts.repack()
-    got = a["view"].clone()
-    ops.gather(ts.P, a["idx"], a["view"], a["idx2"])
-    assert torch.equal(got, a["view"])
+    got = a.view.clone()
+    ops.gather(ts.P, a.idx, a.view, a.idx2)
+    assert torch.equal(got, a.view)
     # (the fallback layouts - gathered only when a fallback path runs - go through the same choice: affine where every range qualifies)
-    ts._repack_fallback()
-    fb = ts._arena_fb[torch.bfloat16]
-    if fb["idx"].numel():
-        got = fb["view"].clone()
-        ops.gather(ts.P, fb["idx"], fb["view"], fb["idx2"])
-        assert torch.equal(got, fb["view"])
+    ts.arena.repack_fallback()
+    fb = ts.arena.fallback[torch.bfloat16]
+    if fb.idx.numel():
+        got = fb.view.clone()
+        ops.gather(ts.P, fb.idx, fb.view, fb.idx2)
+        assert torch.equal(got, fb.view)
 
 
 def test_queued_multi_problem_weight_gradients_equal_one_launch_per_layer(gpu_lib):
