@@ -965,6 +965,30 @@ int mhe_chamfer_f32(const float *points, const float *scale, const float *root, 
 int mhe_chamfer_bwd_f32(const float *points, const float *scale, const float *root, const float *obj, const int *obj_count, const int *idx_p,
                         const int *idx_o, const float *g_dist, float *g_points, int N, int B, int P, int VO, float unit, void *stream);
 
+/* Silhouette and depth of a triangle mesh under the 2D head's orthographic camera (csrc/render.hip; the call chain of the reference's
+ * ManoLayer.render, hand/ManoLayer.py:62-105, whose third-party rasteriser `neural_renderer` is commented out there and absent here: parity
+ * with it is UNPINNED, the contract below is this project's own and is what the tests pin).  R rows (hypotheses), forward only.
+ *   verts [R,V,3], faces [F,3] int32, scale [R], trans [R,2], zscale [R] or NULL, target [B,S,S] in [0,1] or NULL: row r is scored against
+ *   image r % B (sample-major rows) -> mask [R,S,S] or NULL, depth [R,S,S] or NULL, iou_sums [R,2] = (sum min(mask, target), sum max(mask,
+ *   target)) or NULL (needs target).  At least one output.
+ * Sample grid: G = S A, A = 2 with anti_aliasing (render at 2S, average-pool), else 1; sample (row i, col j) sits at x = (2j+1)/G - 1,
+ *   y = (2i+1)/G - 1 (the `uv` convention (uv+1)/2 size: the mask lines up with the crop and with hand_mask).
+ * Projection: p = (|scale| vx + tx, |scale| vy + ty); d = vz zscale / 1000, or vz when zscale is NULL.
+ * Coverage: a sample is covered by a face when it lies inside the projected triangle, either winding (no culling); a sample exactly on an
+ *   edge may go either way; a face of zero projected area (a repeated index included) covers nothing; a face with an index outside [0,V) is
+ *   skipped, never read.
+ * mask = mean coverage of a pixel's A^2 samples (multiples of 1/A^2).  Per sample the smallest d over the covering faces, d interpolated over
+ *   the triangle (affine in the image); depth = the minimum over a pixel's covered samples, `far` when none is covered.
+ * Coverage and depth do not depend on the order of the faces (integer minimum in LDS); iou_sums are summed in a fixed order: two calls give
+ *   the same bits, and the values do not depend on which other outputs are asked for.  With iou_sums alone no image is written.
+ * R >= 1, V >= 1, F >= 1, MHE_RENDER_MIN_SIZE <= S <= MHE_RENDER_MAX_SIZE; target needs B >= 1 and R % B == 0; outputs must not overlap inputs
+ *   or each other (MHE_ERR_ARG otherwise, before any launch).  No allocation, no workspace: an image larger than the 16,384 depth words of a
+ *   workgroup is rendered in row bands, one workgroup per (row, band) - a row's bands by one workgroup when a score is asked for. */
+#define MHE_RENDER_MIN_SIZE 8
+#define MHE_RENDER_MAX_SIZE 256
+int mhe_render_mesh_f32(const float *verts, const int *faces, const float *scale, const float *trans, const float *zscale, const float *target,
+                        float *mask, float *depth, float *iou_sums, int R, int B, int V, int F, int S, int anti_aliasing, float far, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

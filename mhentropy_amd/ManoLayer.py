@@ -41,6 +41,8 @@ class _ManoBuffers(nn.Module):
         self.register_buffer("th_J_regressor", f(t["J_regressor"]))
         self.register_buffer("th_weights", f(t["weights"]))
         self.register_buffer("th_faces", torch.as_tensor(np.asarray(t["faces"]).astype(np.int32)).long())
+        # the renderer's operand (ops.render_mesh reads int32): not persistent, the state_dict keeps the reference's keys
+        self.register_buffer("faces_i32", torch.as_tensor(np.asarray(t["faces"]).astype(np.int32)).contiguous(), persistent=False)
         mean = np.zeros(45, np.float32) if flat_hand_mean else np.asarray(t["hands_mean"], np.float32)
         self.register_buffer("th_hands_mean", f(mean).unsqueeze(0))
         self.register_buffer("th_comps", f(t["hands_components"]))
@@ -107,5 +109,20 @@ class ManoLayer(nn.Module):
             out = (out + 1.0) / 2.0 * image_size
         return out
 
-    def render(self, *a, **k):
-        raise NotImplementedError("the reference's renderer is commented out (hand/ManoLayer.py:40); never on the hot path")
+    def render(self, scale_camera, trans_camera, vertex=None, norm=None, render=("mask",)):
+        """reference hand/ManoLayer.py:62-105 -> {'mask': (R, mask_sz, mask_sz), 'depth': ...} for the names in `render`; {} without a
+        vertex.  scale_camera (R, 1) (its absolute value is used), trans_camera (R, 2), vertex (R, 778, 3) normalised, norm (R,): depth is
+        vertex_z * norm / 1000 (mm to m).  The reference's rasteriser (neural_renderer, anti_aliasing=True) is commented out there and absent
+        here: the images are ops.render_mesh's, whose contract is written in include/mhe.h - parity with neural_renderer is unpinned.
+        Uncovered depth pixels hold ops.render_mesh's `far` (100)."""
+        if vertex is None:
+            return {}
+        names = {"mask", "depth"} & set([render] if isinstance(render, str) else render)
+        if not names:
+            return {}
+        R = vertex.shape[0]
+        if norm is None:
+            raise ValueError("ManoLayer.render: vertex= needs norm= (R,), the depth scale of each row")
+        return ops.render_mesh(vertex.reshape(R, -1, 3).contiguous(), self.mano_layer.faces_i32, scale_camera.reshape(R).contiguous(),
+                               trans_camera.reshape(R, 2).contiguous(), norm.reshape(R).contiguous(), size=self.mask_sz, anti_aliasing=True,
+                               want=tuple(k for k in ("mask", "depth") if k in names))

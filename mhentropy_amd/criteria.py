@@ -2,7 +2,8 @@
 `MHEntLoss(loss_weights, aligned)(output, target) -> (total, losses, metrics)`; the metrics
 block runs in one HIP kernel (csrc/metrics.hip), the Procrustes alignment of the aligned
 evaluation in csrc/procrustes.hip.  chamfer_dist (hand/criteria.py:18-39) and the selection
-it was written for (chamfer_select) run on csrc/chamfer.hip."""
+it was written for (chamfer_select) run on csrc/chamfer.hip; silhouette_iou scores the hypotheses' meshes against the image's hand mask
+on csrc/render.hip."""
 import torch
 from torch import nn
 
@@ -106,6 +107,40 @@ def chamfer_select(output, target, Q=1, points="xyz"):
         out[k] = v[keep, cols] if cut else v
     out["chamfer"], out["chamfer_index"] = val[:Q], keep
     return out
+
+
+def silhouette_iou(verts, logs_t, faces, hand_mask, size=64):
+    """Intersection over union of every hypothesis' silhouette with its image's hand mask: verts (N, B, V*3) or (N, B, V, 3) and logs_t
+    (N, B, 3) = (log s, tx, ty) of a sample() output, faces (F, 3) int32 (ManoLayer's `mano_layer.faces_i32`; an int64 tensor is converted on
+    every call), hand_mask (B, H, H) bool or float in [0, 1] (the input pipeline's target['hand_mask']) -> (N, B) f32.  H must be a
+    multiple of `size`; the mask is box-averaged down to (size, size) when it is larger.  The silhouette is ops.render_mesh's anti-aliased mask
+    under the camera p = exp(log s) v_xy + t; IoU = sum min(mask, target) / sum max(mask, target), 0 where the union is empty.  The fused
+    path: only the two sums per hypothesis leave the kernel, no mask tensor exists.  Forward only (no gradient).
+        iou = silhouette_iou(out['verts'], out['logs_t'], faces, target['hand_mask'])
+        best = iou.max(0).values          # (B,) best of N
+        keep = iou.argmax(0)              # (B,) a selection index, used like chamfer_select's: out['xyz'][keep, torch.arange(B)]"""
+    if not isinstance(verts, torch.Tensor) or verts.dim() not in (3, 4) or (verts.dim() == 4 and verts.shape[-1] != 3) or verts[0, 0].numel() % 3:
+        raise ValueError(f"silhouette_iou: verts must be (N, B, V*3) or (N, B, V, 3), got {tuple(getattr(verts, 'shape', ()))}")
+    N, B = verts.shape[:2]
+    if tuple(logs_t.shape) != (N, B, 3):
+        raise ValueError(f"silhouette_iou: logs_t must be (N, B, 3) = ({N}, {B}, 3), got {tuple(logs_t.shape)}")
+    if hand_mask.dim() != 3 or hand_mask.shape[0] != B or hand_mask.shape[1] != hand_mask.shape[2]:
+        raise ValueError(f"silhouette_iou: hand_mask must be (B, H, H) with B={B}, got {tuple(hand_mask.shape)}")
+    H = hand_mask.shape[1]
+    if H < size or H % size:
+        raise ValueError(f"silhouette_iou: hand_mask is {H} x {H}, not a multiple of size={size}")
+    with torch.no_grad():
+        tgt = hand_mask.float()
+        if H != size:
+            k = H // size
+            tgt = tgt.view(B, size, k, size, k).mean((2, 4))
+        lt = logs_t.detach().reshape(N * B, 3).float()
+        if faces.dtype != torch.int32:
+            faces = faces.to(torch.int32)
+        sums = ops.render_mesh(verts.detach().reshape(N * B, -1, 3).float().contiguous(), faces.contiguous(), lt[:, 0].exp().contiguous(),
+                               lt[:, 1:].contiguous(), size=size, anti_aliasing=True, want=("iou_sums",), target=tgt.contiguous())["iou_sums"]
+        inter, union = sums[:, 0], sums[:, 1]
+        return torch.where(union > 0, inter / union.clamp_min(1e-30), torch.zeros_like(inter)).view(N, B)
 
 
 class MHEntLoss(nn.Module):

@@ -14,7 +14,8 @@ Extensions (all optional, defaults reproduce the reference):
     set False to run the reference's two-pass form.
 The `q_z_giv_i_model='glow'` branch (hand/network.py:342-344,736-742) runs on mhentropy_amd/glow.py's ConditionalGlow - a
 restatement of the published nflows algorithm, parity UNPINNED (the third-party class is absent from the reference tree).
-Dead reference branches (VAE prior, renderer, GT evidences) raise NotImplementedError.
+Dead reference branches (VAE prior, GT evidences) raise NotImplementedError.  The renderer (hand/network.py:528-558, whose third-party
+rasteriser the reference has commented out) is ops.render_mesh: `sample(mods=[..., 'm', 'depth'])` adds mask / depth, forward only.
 """
 from typing import Union
 
@@ -198,7 +199,9 @@ class MHEnt(nn.Module):
 
     def sample(self, x, N: Union[int, list] = 5, temp=0.5, mods=None, y=None, noise=None, feat=None):
         """reference hand/network.py:846-883 -> th_bt (N,B,58), logs_t (N,B,3), verts (N,B,2334),
-        xyz (N,B,63), uv (N,B,42) in pixels, faces."""
+        xyz (N,B,63), uv (N,B,42) in pixels, faces.  mods may also hold 'm' and / or 'depth' (hand/network.py:541-558): mask / depth
+        (N,B,64,64) of every hypothesis' mesh through ManoLayer.render - camera exp(logs_t[0]), logs_t[1:], depth scaled by the normaliser
+        |J11 - J12| of the un-normalised joints.  The default mods (None) returns what it always did."""
         N_quant = N
         if isinstance(N, (list, tuple)):
             N, N_quant = N
@@ -220,9 +223,11 @@ class MHEnt(nn.Module):
             _, th45 = ops.topk_gather(log_q, th45, N, B, N_quant)
             N = N_quant
         mods = {"xyz", "uv", "verts"} if mods is None else set(mods)
+        render = [k for m, k in (("m", "mask"), ("depth", "depth")) if m in mods]
         blob = self.mano_dec.table_blob()
         o = ops.mano_joints(th45, self._det(feat), blob, inv_norm=True, image_size=float(self.image_size),
-                            want=("z", "xyz", "uv") + (("verts",) if "verts" in mods else ()))      # the mesh from the joint pass' operands
+                            want=("z", "xyz", "uv") + (("verts",) if "verts" in mods or render else ()) +      # the mesh from the joint pass' operands
+                            (("joints_mm",) if render else ()))
         z = o["z"].view(N, B, 61)
         out["th_bt"], out["logs_t"] = z[..., :58], z[..., -3:]
         if "verts" in mods:
@@ -232,6 +237,13 @@ class MHEnt(nn.Module):
             out["xyz"] = o["xyz"].view(N, B, -1)
         if "uv" in mods:
             out["uv"] = o["uv"].view(N, B, -1)
+        if render:
+            J = o["joints_mm"].view(N * B, 21, 3)
+            logs_t = o["z"][:, -3:]
+            img = self.mano_dec.render(logs_t[:, :1].exp(), logs_t[:, 1:].contiguous(), vertex=o["verts"], norm=(J[:, 11] - J[:, 12]).norm(dim=-1),
+                                       render=render)
+            for k, v in img.items():
+                out[k] = v.view(N, B, *v.shape[1:])
         return out
 
     def training_step_start(self, step):

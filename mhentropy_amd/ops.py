@@ -382,8 +382,9 @@ MODS_UV, MODS_XYZ = 1, 2           # MHE_MODS_* of include/mhe.h
 
 def mods_bits(mods):
     """the reference's get_loss `mods` (hand/network.py:620-643; None means ['uv']) -> the MHE_MODS_* bit set.  'uv' and 'xyz' in any
-    order; anything else (the render mods 'm' / 'depth', the dead p_ys branch) is not built.  The chamfer term is no mod here: its distance
-    is ops.chamfer / criteria.chamfer_dist, and the train step does not take it yet"""
+    order; anything else (the dead p_ys branch) is not built.  The render mods 'm' / 'depth' are no likelihood here: MHEnt.sample(mods=)
+    takes them (ops.render_mesh, forward only) and the train step has no mask term.  Nor is the chamfer term a mod: its distance is ops.chamfer
+    / criteria.chamfer_dist, and the train step does not take it yet"""
     if mods is None:
         return MODS_UV
     names = [mods] if isinstance(mods, str) else list(mods)
@@ -594,6 +595,63 @@ def chamfer_bwd(points, scale, root, obj, count, idx_p, idx_o, g_dist, unit=1000
     g_points = torch.empty_like(points)
     launch("mhe_chamfer_bwd_f32", points, scale, root, obj, count, idx_p, idx_o, g_dist, g_points, N, B, P, VO, float(unit))
     return g_points
+
+
+RENDER_OUTPUTS = ("mask", "depth", "iou_sums")
+
+
+def _faces_index_range(faces):
+    """(lowest, highest) index of a faces tensor: one host read per tensor (and per in-place change of it), kept on the tensor"""
+    cached = getattr(faces, "_mhe_index_range", None)
+    if cached is None or cached[0] != faces._version:
+        cached = (faces._version, int(faces.min()), int(faces.max()))
+        faces._mhe_index_range = cached
+    return cached[1:]
+
+
+def render_mesh(verts, faces, scale, trans, zscale=None, size=64, anti_aliasing=True, far=100.0, want=("mask",), target=None):
+    """silhouette and depth of R meshes under the orthographic camera p = |scale| v_xy + trans (include/mhe.h, mhe_render_mesh_f32, whose
+    comment is the contract): verts [R,V,3], faces [F,3] int32 (one set for all rows), scale [R] or [R,1], trans [R,2], zscale [R] or None
+    (depth = v_z zscale / 1000, v_z without it) -> dict of the outputs named in `want`: 'mask' [R,size,size] in [0,1] (multiples of 1/4 with
+    anti_aliasing, which renders at 2 size and averages), 'depth' [R,size,size] (`far` where nothing covers) and 'iou_sums' [R,2] =
+    (sum min(mask, target), sum max(mask, target)) against target [B,size,size] in [0,1], row r against image r % B.  With
+    want=('iou_sums',) no image is allocated or written.  ValueError for a face index outside [0,V) (checked once per faces tensor)."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[-1] != 3:
+        raise _lib.MheError("render_mesh.verts: expected an [R,V,3] tensor")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[-1] != 3:
+        raise _lib.MheError("render_mesh.faces: expected an [F,3] tensor")
+    R, V, F, S = verts.shape[0], verts.shape[1], faces.shape[0], int(size)
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in RENDER_OUTPUTS for k in want):
+        raise ValueError(f"render_mesh: want={want!r} (any of {RENDER_OUTPUTS})")
+    if "iou_sums" in want and target is None:
+        raise ValueError("render_mesh: 'iou_sums' needs target=")
+    if not 8 <= S <= 256:
+        raise ValueError(f"render_mesh: size={S} (8..256)")
+    _chk(verts, torch.float32, "render_mesh.verts"); _chk(faces, torch.int32, "render_mesh.faces")
+    if isinstance(scale, torch.Tensor) and tuple(scale.shape) == (R, 1):
+        scale = scale.view(R)
+    _chk(scale, torch.float32, "render_mesh.scale", (R,)); _chk(trans, torch.float32, "render_mesh.trans", (R, 2))
+    if zscale is not None:
+        _chk(zscale, torch.float32, "render_mesh.zscale", (R,))
+    B = 1
+    if target is not None:
+        if not isinstance(target, torch.Tensor) or target.dim() != 3:
+            raise _lib.MheError("render_mesh.target: expected a [B,size,size] tensor")
+        B = target.shape[0]
+        _chk(target, torch.float32, "render_mesh.target", (B, S, S))
+        if B < 1 or R % B:
+            raise ValueError(f"render_mesh: R={R} rows are not a multiple of the B={B} target images")
+    if R < 1 or V < 1 or F < 1:
+        raise ValueError(f"render_mesh: R={R} V={V} F={F} (each >= 1)")
+    lo, hi = _faces_index_range(faces)
+    if lo < 0 or hi >= V:
+        raise ValueError(f"render_mesh: faces index {lo}..{hi} outside the V={V} vertices")
+    shapes = {"mask": (R, S, S), "depth": (R, S, S), "iou_sums": (R, 2)}
+    o = {k: (torch.empty(shapes[k], device=verts.device, dtype=torch.float32) if k in want else None) for k in RENDER_OUTPUTS}
+    launch("mhe_render_mesh_f32", verts, faces, scale, trans, zscale, target, o["mask"], o["depth"], o["iou_sums"], R, B, V, F, S, int(bool(anti_aliasing)),
+           float(far))
+    return {k: v for k, v in o.items() if v is not None}
 
 
 def conv2d_nhwc(x, w, KH, KW, stride, pad, in_scale=None, in_shift=None, relu_in=False, out_scale=None,
