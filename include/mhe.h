@@ -215,6 +215,23 @@ int mhe_mano_joints_mods_f32(const float *th45, const float *det, const float *c
                              float *joints_mm, int R, int B, int mods, float laplace_b, float laplace_b_3d, float th45_alpha,
                              int inv_norm, float image_size, void *stream);
 
+/* mhe_mano_joints_mods_f32 with the hand-object Chamfer term evaluated inside the same pass: the training half of the reference's
+ * `log_p - w_chamfer * chamfer_dist(xyz, y)` (hand/network.py:821-826, hand/criteria.py:18-39).  For row r = n*B + b
+ *   a_j = xyz_r[j] * (scale[b] * 1000) + root[b]                       (mm; root = original_pose3d[b, 12])
+ *   dist[r] = mean_j min_{v < V_b} |a_j - o_v| + mean_{v < V_b} min_j |a_j - o_v|,   o_v = obj[b][v]
+ * over the 21 joints, exactly mhe_chamfer_f32's distance (P = 21, unit = 1000): squared distances compared, one square root per minimum.
+ *   scale [B], root [B,3], obj [B,VO,3] (read straight from global memory, lanes striding over the vertices; never written)
+ *   obj_count [B] int32 or NULL: V_b, clamped to 1..VO in the kernel (NULL: V_b = VO; vertices at or past V_b are never read)
+ *   dist [R] (required; must not overlap the four inputs above).  log_p / terms [R,5] and every other output are those of
+ *   mhe_mano_joints_mods_f32 bit for bit: the term is NOT added to log_p here (the caller averages dist over n and weights it).
+ * Fixed summation order, no atomics: two launches give the same bits.  Runs on the four-hypotheses-per-wave kernel only.
+ * MHE_ERR_ARG as mhe_mano_joints_mods_f32, and for a null scale / root / obj / dist, VO < 1 or an overlapping dist. */
+int mhe_mano_joints_chamfer_f32(const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
+                                const float *tables, const float *scale, const float *root, const float *obj, const int *obj_count,
+                                float *z, float *xyz, float *uv, float *terms, float *log_p, float *norms,
+                                float *joints_mm, float *dist, int R, int B, int VO, int mods, float laplace_b, float laplace_b_3d,
+                                float th45_alpha, int inv_norm, float image_size, void *stream);
+
 /* Full 778-vertex linear-blend skinning for MHEnt.sample
  * (hand/manopth/manolayer.py:181-246, hand/network.py:480): verts [R,778,3]
  * normalised like xyz ((mesh - root)/bone), or with mm_mode != 0 the `mesh`
@@ -491,6 +508,19 @@ int mhe_mano_joints_mods_bwd_f32(const float *th45, const float *det, const floa
                                  const float *tables, const float *g_log_p, float *g_th45, float *g_det_rows,
                                  int R, int B, int mods, float laplace_b, float laplace_b_3d, float th45_alpha, float row_weight,
                                  void *stream);
+/* Reverse of  log_p[r] - chamfer_w * dist[r]  of mhe_mano_joints_chamfer_f32 (arguments as there and in mhe_mano_joints_mods_bwd_f32):
+ * row r receives d loss / d log_p[r] = g_log_p[b] * row_weight, hence d loss / d dist[r] = -chamfer_w * g_log_p[b] * row_weight.  The
+ * kernel is mhe_mano_joints_mods_bwd_f32's with the Chamfer adjoint of the joints added, for all three `mods` values: after re-running the
+ * joint pass the wave finds the argmins again by the forward's scan (nothing but the forward's inputs is read - no xyz and no index
+ * tensor), holds them fixed (ties to the lowest index) and uses d|a - o| / da = (a - o) / |a - o|, 0 at a zero distance as
+ * mhe_chamfer_bwd_f32 does.  Joint 12 is the normalisation root (xyz = 0): it takes part in both minima and takes no gradient.
+ * The object -> hand scatter onto the 21 joints is one masked wave reduction per joint and 64-vertex round: fixed order, no atomics, no
+ * LDS of its own.  Outputs g_th45 [R,45], g_det_rows [R,16] as in mhe_mano_joints_bwd_f32. */
+int mhe_mano_joints_chamfer_bwd_f32(const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
+                                    const float *tables, const float *scale, const float *root, const float *obj, const int *obj_count,
+                                    const float *g_log_p, float *g_th45, float *g_det_rows, int R, int B, int VO, int mods,
+                                    float laplace_b, float laplace_b_3d, float th45_alpha, float row_weight, float chamfer_w,
+                                    void *stream);
 /* out[b*out_stride + c] (+)= sum_n rows[(n*B + b)][c] : the adjoint of `.repeat(N,1)` (hand/network.py:734,747);
  * out_stride <= 0 means C (dense). */
 int mhe_sum_over_hypotheses_f32(const float *rows, float *out, int N, int B, int C, int accumulate, long out_stride,

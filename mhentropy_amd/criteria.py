@@ -16,6 +16,32 @@ CHAMFER_UNIT = 1000.0          # hand/criteria.py:24 (normalised -> mm)
 CHAMFER_ROOT = 12              # hand/criteria.py:25: the row of original_pose3d the joints are relative to
 
 
+def chamfer_target_operands(target, B=None, who="chamfer_dist"):
+    """the target's half of chamfer_dist's checks, shared with the training term (MHEnt.get_loss(chamfer_w=...)): -> (scale [B],
+    root [B,3] = original_pose3d[:, 12], obj [B,VO,3], count [B] int32 | None).  B: the images the caller's other operand has."""
+    if "object_verts" not in target:
+        raise ValueError(f"{who}: target has no 'object_verts'")
+    nb = target["scale"].shape[0]
+    if B is not None and B != nb:
+        raise ValueError(f"{who}: norm_rel_xyz has {B} images, target['scale'] {nb}")
+    B = nb
+    obj = target["object_verts"]
+    if obj.dim() not in (2, 3) or obj.shape[0] != B or obj[0].numel() % 3 or obj[0].numel() == 0 or (obj.dim() == 3 and obj.shape[2] != 3):
+        raise ValueError(f"{who}: target['object_verts'] must be (B, VO*3) or (B, VO, 3) with B={B}, got {tuple(obj.shape)}")
+    obj = obj.reshape(B, -1, 3)
+    count = target.get("object_count")
+    if count is not None:
+        if tuple(count.shape) != (B,) or count.dtype != torch.int32:
+            raise ValueError(f"{who}: target['object_count'] must be a (B,) int32 tensor, got {tuple(count.shape)} {count.dtype}")
+        # (one host read; a stream that is being captured cannot take it: the kernel clamps the count to 1..VO there)
+        if not (count.is_cuda and torch.cuda.is_current_stream_capturing()) and not (1 <= int(count.min()) and int(count.max()) <= obj.shape[1]):
+            raise ValueError(f"{who}: target['object_count'] outside 1..VO={obj.shape[1]}")
+    root = target["original_pose3d"]
+    if root.dim() != 3 or root.shape[0] != B or root.shape[1] <= CHAMFER_ROOT or root.shape[2] != 3:
+        raise ValueError(f"{who}: target['original_pose3d'] must be (B, >={CHAMFER_ROOT + 1}, 3), got {tuple(root.shape)}")
+    return target["scale"].contiguous(), root[:, CHAMFER_ROOT].contiguous(), obj.contiguous(), count
+
+
 def _chamfer_operands(norm_rel_xyz, target):
     """the checks of chamfer_dist that need no device -> (points [N,B,P,3], scale, root, obj [B,VO,3], count or None, input was 3-D)"""
     if "object_verts" not in target:
@@ -24,26 +50,12 @@ def _chamfer_operands(norm_rel_xyz, target):
         raise ValueError(f"chamfer_dist: norm_rel_xyz must be (N, B, K, 3) or (B, K, 3), got {tuple(getattr(norm_rel_xyz, 'shape', ()))}")
     single = norm_rel_xyz.dim() == 3
     pts = norm_rel_xyz[None] if single else norm_rel_xyz
-    B = target["scale"].shape[0]
-    if pts.shape[1] != B:
-        raise ValueError(f"chamfer_dist: norm_rel_xyz has {pts.shape[1]} images, target['scale'] {B}")
+    if pts.shape[1] != target["scale"].shape[0]:
+        raise ValueError(f"chamfer_dist: norm_rel_xyz has {pts.shape[1]} images, target['scale'] {target['scale'].shape[0]}")
     if not 1 <= pts.shape[2] <= 778:
         raise ValueError(f"chamfer_dist: K={pts.shape[2]} points per hypothesis (1..778)")
-    obj = target["object_verts"]
-    if obj.dim() not in (2, 3) or obj.shape[0] != B or obj[0].numel() % 3 or obj[0].numel() == 0 or (obj.dim() == 3 and obj.shape[2] != 3):
-        raise ValueError(f"chamfer_dist: target['object_verts'] must be (B, VO*3) or (B, VO, 3) with B={B}, got {tuple(obj.shape)}")
-    obj = obj.reshape(B, -1, 3)
-    count = target.get("object_count")
-    if count is not None:
-        if tuple(count.shape) != (B,) or count.dtype != torch.int32:
-            raise ValueError(f"chamfer_dist: target['object_count'] must be a (B,) int32 tensor, got {tuple(count.shape)} {count.dtype}")
-        # (one host read; a stream that is being captured cannot take it: the kernel clamps the count to 1..VO there)
-        if not (count.is_cuda and torch.cuda.is_current_stream_capturing()) and not (1 <= int(count.min()) and int(count.max()) <= obj.shape[1]):
-            raise ValueError(f"chamfer_dist: target['object_count'] outside 1..VO={obj.shape[1]}")
-    root = target["original_pose3d"]
-    if root.dim() != 3 or root.shape[0] != B or root.shape[1] <= CHAMFER_ROOT or root.shape[2] != 3:
-        raise ValueError(f"chamfer_dist: target['original_pose3d'] must be (B, >={CHAMFER_ROOT + 1}, 3), got {tuple(root.shape)}")
-    return pts.contiguous(), target["scale"].contiguous(), root[:, CHAMFER_ROOT].contiguous(), obj.contiguous(), count, single
+    scale, root, obj, count = chamfer_target_operands(target, pts.shape[1])
+    return pts.contiguous(), scale, root, obj, count, single
 
 
 class _Chamfer(torch.autograd.Function):

@@ -111,14 +111,17 @@ __device__ __forceinline__ float group_sum16(float v) {
 // MODS: the likelihoods evaluated (MODS_UV: 2D joints against crop_uv, MODS_XYZ: normalised 3D joints against pose3d,
 // hand/network.py:620-643).  NTERMS = 4: terms [R,4] = (uv, th3, th45, bt) of mhe_mano_joints_f32 (MODS_UV only);
 // 5: [R,5] = (uv, xyz, th3, th45, bt) of mhe_mano_joints_mods_f32, 0 for a modality that is off.
-template <int MODS, int NTERMS>
+// CHAM: also the hand-object Chamfer distance of the row's 21 joints to its image's object vertices (mhe_mano_joints_chamfer_f32):
+// ch.dist[r]; no other output depends on it.
+template <int MODS, int NTERMS, bool CHAM = false>
 __global__ __launch_bounds__(256) void mano_joints16_kernel(
     const float *__restrict__ th45_g, const float *__restrict__ det_g, const float *__restrict__ crop_uv,
     const float *__restrict__ vis, const float *__restrict__ pose3d, const float *__restrict__ tables,
     float *__restrict__ z_o, float *__restrict__ xyz_o, float *__restrict__ uv_o, float *__restrict__ terms_o,
     float *__restrict__ logp_o, float *__restrict__ norms_o, float *__restrict__ jmm_o, float *__restrict__ ws_o,
-    int R, int B, float lap_b, float lap_b3, float th45_alpha, int inv_norm, float image_size) {
-    static_assert(MODS >= 1 && MODS <= 3 && (NTERMS == 5 || (NTERMS == 4 && MODS == MODS_UV)), "mano_joints16_kernel instantiation");
+    int R, int B, float lap_b, float lap_b3, float th45_alpha, int inv_norm, float image_size, ChamferArgs ch) {
+    static_assert(MODS >= 1 && MODS <= 3 && (NTERMS == 5 || (NTERMS == 4 && MODS == MODS_UV)) && (!CHAM || NTERMS == 5),
+                  "mano_joints16_kernel instantiation");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *tb = smem;
     for (int i = threadIdx.x; i < JOINT_FLOATS / 4; i += 256)
@@ -303,6 +306,46 @@ __global__ __launch_bounds__(256) void mano_joints16_kernel(
             if (sub == 0) w[WS_NRM + 6] = bone;
         }
         wave_sync();
+        if constexpr (CHAM) {
+            // -- hand-object Chamfer distance (hand/criteria.py:18-39): a_j = xyz_j (scale[b] 1000) + root[b] into the dead S_ROT scratch,
+            //    then the group's 16 lanes stride over the image's V_b vertices, read straight from global memory (the rows of one image
+            //    share them through L2).  A lane keeps the 21 running minima over its vertices (hand -> object) and adds the square root
+            //    of the minimum over the joints of each of its vertices (object -> hand); fixed order, no atomics
+            const float su = ch.scale[b] * kChamferUnit;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = sub + 16 * i;
+                if (e < 63) sc[S_ROT + e] = fmaf(sc[S16_XYZ + e], su, ch.root[(size_t)b * 3 + e % 3]);
+            }
+            wave_sync();
+            const int Vb = ch.obj_count ? min(max(ch.obj_count[b], 1), ch.VO) : ch.VO;
+            const float *ob = ch.obj + (size_t)b * ch.VO * 3;
+            float m1[21];
+#pragma unroll
+            for (int j = 0; j < 21; ++j) m1[j] = __builtin_inff();
+            float s2 = 0.f;
+            for (int v = sub; v < Vb; v += 16) {
+                const float ox = ob[(size_t)v * 3], oy = ob[(size_t)v * 3 + 1], oz = ob[(size_t)v * 3 + 2];
+                float m2 = __builtin_inff();
+#pragma unroll
+                for (int j = 0; j < 21; ++j) {
+                    const float d = chamfer_sqdist(sc[S_ROT + 3 * j], sc[S_ROT + 3 * j + 1], sc[S_ROT + 3 * j + 2], ox, oy, oz);
+                    m1[j] = fminf(m1[j], d);
+                    m2 = fminf(m2, d);
+                }
+                s2 += sqrtf(m2);
+            }
+            float d1 = 0.f;
+#pragma unroll
+            for (int j = 0; j < 21; ++j) {
+                float m = m1[j];
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));
+                d1 += sqrtf(m);
+            }
+            s2 = group_sum16(s2);
+            if (live && sub == 0) ch.dist[r] = d1 / 21.f + s2 / (float)Vb;
+        }
         // -- orthographic projection (hand/network.py:497-514, ManoLayer.py:150-165) + visibility-masked Laplace (hand/network.py:255-257)
         const float s_cam = expf(sc[S16_DET + 13]);
         float lt = 0.f;
@@ -545,16 +588,17 @@ using namespace mhe;
 
 extern "C" size_t mhe_mano_table_floats(void) { return mano::TOTAL_FLOATS; }
 
-template <int MODS, int NTERMS>
+template <int MODS, int NTERMS, bool CHAM = false>
 static int launch16(const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d, const float *tables,
                     float *z, float *xyz, float *uv, float *terms, float *log_p, float *norms, float *joints_mm, float *ws_rows, int R, int B,
-                    float laplace_b, float laplace_b_3d, float th45_alpha, int inv_norm, float image_size, void *stream) {
+                    float laplace_b, float laplace_b_3d, float th45_alpha, int inv_norm, float image_size, void *stream,
+                    mano::ChamferArgs ch = mano::ChamferArgs{}) {
     const int quads = (R + 3) / 4, wgs = (quads + 3) / 4;
     const int blocks = wgs < 512 ? wgs : 512;            // two workgroups per CU (67 KiB of LDS each), every wave walks its share of the row quads
     const size_t lds = (mano::JOINT_FLOATS + 16 * mano::SCRATCH16) * sizeof(float);
-    hipLaunchKernelGGL((mano::mano_joints16_kernel<MODS, NTERMS>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, th45, det, crop_uv,
+    hipLaunchKernelGGL((mano::mano_joints16_kernel<MODS, NTERMS, CHAM>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, th45, det, crop_uv,
                        vis, pose3d, tables, z, xyz, uv, terms, log_p, norms, joints_mm, ws_rows, R, B, laplace_b, laplace_b_3d, th45_alpha,
-                       inv_norm, image_size);
+                       inv_norm, image_size, ch);
     return check_launch("mano_joints16_kernel");
 }
 
@@ -577,7 +621,7 @@ static int joints_launch(const char *who, const float *th45, const float *det, c
         auto fn = mods == MHE_MODS_UV ? launch16<mano::MODS_UV, 5> : (mods == MHE_MODS_XYZ ? launch16<mano::MODS_XYZ, 5>
                                                                                             : launch16<mano::MODS_UV | mano::MODS_XYZ, 5>);
         return fn(th45, det, crop_uv, vis, pose3d, tables, z, xyz, uv, terms, log_p, norms, joints_mm, ws_rows, R, B, laplace_b, laplace_b_3d,
-                  th45_alpha, inv_norm, image_size, stream);
+                  th45_alpha, inv_norm, image_size, stream, mano::ChamferArgs{});
     }
     MHE_REQUIRE(!ws_rows, "mhe_mano_decode_f32 runs on the four-hypotheses-per-wave kernel (MHE_MANO_FOUR=1)");
     MHE_REQUIRE(!m_xyz, "%s: the one-hypothesis-per-wave kernel (MHE_MANO_FOUR=0) evaluates the uv likelihood only", who);
@@ -612,6 +656,33 @@ extern "C" int mhe_mano_joints_mods_f32(const float *th45, const float *det, con
     MHE_REQUIRE(vis, "mhe_mano_joints_mods_f32: null vis");
     return joints_launch("mhe_mano_joints_mods_f32", th45, det, crop_uv, vis, pose3d, tables, z, xyz, uv, terms, log_p, norms, joints_mm,
                          nullptr, R, B, mods, 5, laplace_b, laplace_b_3d, th45_alpha, inv_norm, image_size, stream);
+}
+
+// mhe_mano_joints_mods_f32 + the hand-object Chamfer distance of every row's joints, evaluated inside the same pass (the training half of
+// hand/network.py:821-826); log_p and every other output are those of mhe_mano_joints_mods_f32, bit for bit
+extern "C" int mhe_mano_joints_chamfer_f32(const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
+                                           const float *tables, const float *scale, const float *root, const float *obj, const int *obj_count,
+                                           float *z, float *xyz, float *uv, float *terms, float *log_p, float *norms, float *joints_mm,
+                                           float *dist, int R, int B, int VO, int mods, float laplace_b, float laplace_b_3d, float th45_alpha,
+                                           int inv_norm, float image_size, void *stream) {
+    const char *who = "mhe_mano_joints_chamfer_f32";
+    const bool m_uv = mods & MHE_MODS_UV, m_xyz = mods & MHE_MODS_XYZ;
+    MHE_REQUIRE(mods >= 1 && mods <= (MHE_MODS_UV | MHE_MODS_XYZ), "%s: mods=%d must be a non-empty set of MHE_MODS_UV | MHE_MODS_XYZ", who, mods);
+    MHE_REQUIRE(th45 && det && tables && vis, "%s: null input", who);
+    MHE_REQUIRE(scale && root && obj && dist, "%s: null pointer (scale, root, obj, dist)", who);
+    MHE_REQUIRE(R > 0 && B > 0 && R % B == 0, "%s: R=%d must be a positive multiple of B=%d", who, R, B);
+    MHE_REQUIRE(VO >= 1, "%s: VO=%d (VO >= 1)", who, VO);
+    MHE_REQUIRE(!m_uv || crop_uv, "%s: mods has MHE_MODS_UV but crop_uv is null", who);
+    MHE_REQUIRE(!m_xyz || pose3d, "%s: mods has MHE_MODS_XYZ but pose3d is null", who);
+    MHE_REQUIRE(!m_uv || laplace_b > 0.f, "%s: laplace_b must be > 0", who);
+    MHE_REQUIRE(!m_xyz || laplace_b_3d > 0.f, "%s: laplace_b_3d must be > 0", who);
+    const struct { const void *p; size_t n; } in[4] = {{scale, (size_t)B * 4}, {root, (size_t)B * 12}, {obj, (size_t)B * VO * 12}, {obj_count, (size_t)B * 4}};
+    for (int i = 0; i < 4; ++i) MHE_REQUIRE(disjoint(dist, (size_t)R * 4, in[i].p, in[i].n), "%s: dist overlaps input %d", who, i);
+    const mano::ChamferArgs ch{scale, root, obj, obj_count, dist, VO};
+    auto fn = mods == MHE_MODS_UV ? launch16<mano::MODS_UV, 5, true> : (mods == MHE_MODS_XYZ ? launch16<mano::MODS_XYZ, 5, true>
+                                                                                             : launch16<mano::MODS_UV | mano::MODS_XYZ, 5, true>);
+    return fn(th45, det, crop_uv, vis, pose3d, tables, z, xyz, uv, terms, log_p, norms, joints_mm, nullptr, R, B, laplace_b, laplace_b_3d,
+              th45_alpha, inv_norm, image_size, stream, ch);
 }
 
 extern "C" size_t mhe_mano_verts_workspace_floats(int R) { return R > 0 ? mhe_mano_skin_split_floats() + (size_t)R * mano::WS_STRIDE : 0; }

@@ -26,11 +26,15 @@ constexpr int A_POSE = 656;    // [48]      axis-angles
 constexpr int A_SCRATCH = 704;
 
 // MODS: the likelihoods in log_p (MODS_UV and / or MODS_XYZ, as in mano_joints16_kernel)
-template <int MODS>
+// CHAM: log_p also carries -chamfer_w * (hand-object Chamfer distance of the row's joints, ch as in the loss pass; ch.dist is not used).  The
+// wave finds the argmins again by the scan of the loss pass - no xyz or index tensor exists between the two passes - and the adjoint
+// of the joints joins a_xyz.  LDS: none of its own (the joints a_j sit in the adjoint scratch, which is written only later).
+template <int MODS, bool CHAM = false>
 __global__ __launch_bounds__(256) void mano_joints_bwd_kernel(
     const float *__restrict__ th45_g, const float *__restrict__ det_g, const float *__restrict__ crop_uv,
     const float *__restrict__ vis, const float *__restrict__ pose3d, const float *__restrict__ tables, const float *__restrict__ g_logp,
-    float *__restrict__ g_th45_o, float *__restrict__ g_det_o, int R, int B, float lap_b, float lap_b3, float th45_alpha, float row_w) {
+    float *__restrict__ g_th45_o, float *__restrict__ g_det_o, int R, int B, float lap_b, float lap_b3, float th45_alpha, float row_w,
+    ChamferArgs ch, float chamfer_w) {
     static_assert(MODS >= 1 && MODS <= 3, "mano_joints_bwd_kernel instantiation");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *tb = smem;
@@ -71,6 +75,73 @@ __global__ __launch_bounds__(256) void mano_joints_bwd_kernel(
                 const float d = o.xyz - pose3d[b * 63 + lane];
                 if (vis[b * 21 + k21] == 1.f && fabsf(d) > 1e-4f) a_xyz += (d > 0.f ? -g : g) / lap_b3;
             }
+        }
+        if constexpr (CHAM) {
+            // ---- dist = mean_j min_v |a_j - o_v| + mean_v min_j |a_j - o_v|,  a_j = xyz_j (scale[b] 1000) + root[b]  (hand/criteria.py:18-39)
+            // d|a - o| / da = (a - o) / |a - o|, 0 at a zero distance (as chamfer_bwd_kernel); argmins fixed, ties to the lowest index
+            const float su = ch.scale[b] * kChamferUnit;
+            if (lane < 63) ad[lane] = fmaf(o.xyz, su, ch.root[(size_t)b * 3 + c3]);
+            wave_sync();
+            const int Vb = ch.obj_count ? min(max(ch.obj_count[b], 1), ch.VO) : ch.VO;
+            const float *ob = ch.obj + (size_t)b * ch.VO * 3;
+            float m1[21];
+            int i1[21];
+#pragma unroll
+            for (int j = 0; j < 21; ++j) { m1[j] = __builtin_inff(); i1[j] = 0; }
+            float acc = 0.f;        // lane 3 j + c: component c of sum over the vertices nearest to joint j of their unit vectors
+            for (int t0 = 0; t0 < Vb; t0 += 64) {
+                // lanes stride over the vertices: 64 per round, lane = vertex t0 + lane (past V_b: the last one again, taking part in nothing)
+                const int v = t0 + lane;
+                const bool ok = v < Vb;
+                const size_t vo = (size_t)(ok ? v : Vb - 1) * 3;
+                const float ox = ob[vo], oy = ob[vo + 1], oz = ob[vo + 2];
+                float m2 = __builtin_inff();
+                int j2 = 0;
+#pragma unroll
+                for (int j = 0; j < 21; ++j) {
+                    const float d = chamfer_sqdist(ad[3 * j], ad[3 * j + 1], ad[3 * j + 2], ox, oy, oz);
+                    if (ok && d < m1[j]) { m1[j] = d; i1[j] = v; }
+                    if (d < m2) { m2 = d; j2 = j; }
+                }
+                float ux = 0.f, uy = 0.f, uz = 0.f;
+                if (ok && m2 > 0.f) {
+                    const float inv = 1.f / sqrtf(m2);
+                    ux = (ad[3 * j2] - ox) * inv; uy = (ad[3 * j2 + 1] - oy) * inv; uz = (ad[3 * j2 + 2] - oz) * inv;
+                }
+                if (!ok) j2 = -1;
+                // object -> hand scatter in a fixed order, no atomics: one masked wave reduction per joint that some vertex of the round chose
+                for (int j = 0; j < 21; ++j) {
+                    const bool mine = j2 == j;
+                    if (__any(mine)) {
+                        const float sx = wave_sum(mine ? ux : 0.f), sy = wave_sum(mine ? uy : 0.f), sz = wave_sum(mine ? uz : 0.f);
+                        if (k21 == j) acc += c3 == 0 ? sx : (c3 == 1 ? sy : sz);
+                    }
+                }
+            }
+            // hand -> object: the lanes' (minimum, vertex) pairs to the wave's, the lower vertex on equal minima
+            int iv = 0;
+#pragma unroll
+            for (int j = 0; j < 21; ++j) {
+                float m = m1[j];
+                int i = i1[j];
+#pragma unroll
+                for (int of = 32; of > 0; of >>= 1) {
+                    const float om = __shfl_xor(m, of, 64);
+                    const int oi = __shfl_xor(i, of, 64);
+                    if (om < m || (om == m && oi < i)) { m = om; i = oi; }
+                }
+                if (k21 == j) iv = i;
+            }
+            float u1 = 0.f;
+            {
+                const size_t vo = (size_t)iv * 3;         // iv < V_b: an index some lane scanned (0 where a lane scanned none)
+                const float dx = ad[3 * k21] - ob[vo], dy = ad[3 * k21 + 1] - ob[vo + 1], dz = ad[3 * k21 + 2] - ob[vo + 2];
+                const float q = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+                if (q > 0.f) u1 = (c3 == 0 ? dx : (c3 == 1 ? dy : dz)) * (1.f / sqrtf(q));
+            }
+            // the root's normalised coordinates are identically 0 (a constant a_12 = root[b]): it takes part in both minima, no adjoint
+            if (lane < 63 && k21 != kRootIdx) a_xyz += (-chamfer_w * g * su) * fmaf(u1, 1.f / 21.f, acc * (1.f / (float)Vb));
+            wave_sync();            // the adjoint scratch is written from here on
         }
 
         // ---- xyz = (J - J_root) / |J_norm - J_root|
@@ -268,7 +339,8 @@ using namespace mhe;
 
 static int joints_bwd_launch(const char *who, const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
                              const float *tables, const float *g_log_p, float *g_th45, float *g_det_rows, int R, int B, int mods,
-                             float laplace_b, float laplace_b_3d, float th45_alpha, float row_weight, void *stream) {
+                             float laplace_b, float laplace_b_3d, float th45_alpha, float row_weight, void *stream,
+                             const mano::ChamferArgs *ch = nullptr, float chamfer_w = 0.f) {
     MHE_REQUIRE(th45 && det && vis && tables && g_log_p && g_th45 && g_det_rows, "%s: null pointer", who);
     MHE_REQUIRE(mods >= 1 && mods <= (MHE_MODS_UV | MHE_MODS_XYZ), "%s: mods=%d must be a non-empty set of MHE_MODS_UV | MHE_MODS_XYZ", who, mods);
     MHE_REQUIRE(!(mods & MHE_MODS_UV) || crop_uv, "%s: mods has MHE_MODS_UV but crop_uv is null", who);
@@ -278,11 +350,19 @@ static int joints_bwd_launch(const char *who, const float *th45, const float *de
     MHE_REQUIRE(!(mods & MHE_MODS_XYZ) || laplace_b_3d > 0.f, "%s: laplace_b_3d must be > 0", who);
     const int blocks = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
     const size_t lds = (mano::JOINT_FLOATS + 4 * (mano::SCRATCH + mano::A_SCRATCH)) * sizeof(float);
+    if (ch) {
+        auto kc = mods == MHE_MODS_UV ? mano::mano_joints_bwd_kernel<mano::MODS_UV, true>
+                                      : (mods == MHE_MODS_XYZ ? mano::mano_joints_bwd_kernel<mano::MODS_XYZ, true>
+                                                              : mano::mano_joints_bwd_kernel<mano::MODS_UV | mano::MODS_XYZ, true>);
+        hipLaunchKernelGGL(kc, dim3(blocks), dim3(256), lds, (hipStream_t)stream, th45, det, crop_uv, vis, pose3d, tables, g_log_p, g_th45,
+                           g_det_rows, R, B, laplace_b, laplace_b_3d, th45_alpha, row_weight, *ch, chamfer_w);
+        return check_launch("mano_joints_bwd_kernel (chamfer)");
+    }
     auto kern = mods == MHE_MODS_UV ? mano::mano_joints_bwd_kernel<mano::MODS_UV>
                                     : (mods == MHE_MODS_XYZ ? mano::mano_joints_bwd_kernel<mano::MODS_XYZ>
                                                             : mano::mano_joints_bwd_kernel<mano::MODS_UV | mano::MODS_XYZ>);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, (hipStream_t)stream, th45, det, crop_uv, vis, pose3d, tables, g_log_p, g_th45,
-                       g_det_rows, R, B, laplace_b, laplace_b_3d, th45_alpha, row_weight);
+                       g_det_rows, R, B, laplace_b, laplace_b_3d, th45_alpha, row_weight, mano::ChamferArgs{}, 0.f);
     return check_launch("mano_joints_bwd_kernel");
 }
 
@@ -298,6 +378,21 @@ extern "C" int mhe_mano_joints_mods_bwd_f32(const float *th45, const float *det,
                                             int mods, float laplace_b, float laplace_b_3d, float th45_alpha, float row_weight, void *stream) {
     return joints_bwd_launch("mhe_mano_joints_mods_bwd_f32", th45, det, crop_uv, vis, pose3d, tables, g_log_p, g_th45, g_det_rows, R, B,
                              mods, laplace_b, laplace_b_3d, th45_alpha, row_weight, stream);
+}
+
+// Reverse of mhe_mano_joints_chamfer_f32's  log_p[r] - chamfer_w dist[r]
+extern "C" int mhe_mano_joints_chamfer_bwd_f32(const float *th45, const float *det, const float *crop_uv, const float *vis, const float *pose3d,
+                                               const float *tables, const float *scale, const float *root, const float *obj, const int *obj_count,
+                                               const float *g_log_p, float *g_th45, float *g_det_rows, int R, int B, int VO, int mods,
+                                               float laplace_b, float laplace_b_3d, float th45_alpha, float row_weight, float chamfer_w,
+                                               void *stream) {
+    const char *who = "mhe_mano_joints_chamfer_bwd_f32";
+    MHE_REQUIRE(scale && root && obj, "%s: null pointer (scale, root, obj)", who);
+    MHE_REQUIRE(VO >= 1, "%s: VO=%d (VO >= 1)", who, VO);
+    MHE_REQUIRE(chamfer_w == chamfer_w, "%s: chamfer_w is NaN", who);
+    const mano::ChamferArgs ch{scale, root, obj, obj_count, nullptr, VO};
+    return joints_bwd_launch(who, th45, det, crop_uv, vis, pose3d, tables, g_log_p, g_th45, g_det_rows, R, B, mods, laplace_b, laplace_b_3d,
+                             th45_alpha, row_weight, stream, &ch, chamfer_w);
 }
 
 extern "C" int mhe_sum_over_hypotheses_f32(const float *rows, float *out, int N, int B, int C, int accumulate, long out_stride,

@@ -29,6 +29,21 @@ constexpr int S_PRE = 640;     // [21][3]  chain joints + skinned tips
 constexpr int S_J21 = 704;     // [21][3]  final joints, mm, centred
 constexpr int SCRATCH = 768;
 
+// operands of the hand-object Chamfer term of the loss pass and its reverse (mhe_mano_joints_chamfer_f32 / _bwd_f32)
+struct ChamferArgs {
+    const float *scale, *root, *obj;      // [B], [B,3], [B,VO,3]
+    const int *obj_count;                 // [B] | nullptr
+    float *dist;                          // [R]
+    int VO;
+};
+constexpr float kChamferUnit = 1000.f;    // normalised -> mm (hand/criteria.py:24)
+
+// as csrc/chamfer.hip: squared distances are compared, one square root per minimum
+__device__ __forceinline__ float chamfer_sqdist(float ax, float ay, float az, float ox, float oy, float oz) {
+    const float dx = ax - ox, dy = ay - oy, dz = az - oz;
+    return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+}
+
 __device__ __forceinline__ float bcast(float v, int srclane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), srclane));
 }

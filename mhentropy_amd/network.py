@@ -11,7 +11,9 @@ Extensions (all optional, defaults reproduce the reference):
   * `noise=` host-supplied base noise for reproducible parity,
   * `fused_entropy=True`: log q from the sampling pass instead of a second,
     inverse pass through the flow (same value to fp32 round-off, SURVEY.md A2 ii);
-    set False to run the reference's two-pass form.
+    set False to run the reference's two-pass form,
+  * `chamfer_w=` / the attribute `MHEnt.chamfer_w` (0.0): the weight of the hand-object Chamfer term the reference has behind a literal
+    `use_chamfer_loss = False` (hand/network.py:821-826, its w_chamfer = 10): log_p -= chamfer_w * chamfer, new key 'chamfer' (B,) in mm.
 The `q_z_giv_i_model='glow'` branch (hand/network.py:342-344,736-742) runs on mhentropy_amd/glow.py's ConditionalGlow - a
 restatement of the published nflows algorithm, parity UNPINNED (the third-party class is absent from the reference tree).
 Dead reference branches (VAE prior, GT evidences) raise NotImplementedError.  The renderer (hand/network.py:528-558, whose third-party
@@ -121,6 +123,7 @@ class MHEnt(nn.Module):
         self._extra_ws = {"log_p_vis_giv_z": 1.0}
         self.loss_N = 10                        # network.py:780
         self.fused_entropy = True
+        self.chamfer_w = 0.0                    # network.py:821-826: use_chamfer_loss = False as shipped; its w_chamfer is 10
 
     # ---- pieces ---------------------------------------------------------------
     def _det(self, feat):
@@ -146,20 +149,38 @@ class MHEnt(nn.Module):
         z0 = self._noise(N * B, temp, noise, feat.device)
         return self.q_z_giv_i._run(z0, feat.contiguous(), True, 1, B)
 
+    def chamfer_operands(self, y, chamfer_w=None):
+        """(weight, operands | None) of the hand-object Chamfer term for the target y: chamfer_w None falls back to self.chamfer_w; a weight
+        of 0 is the term off (None).  The checks are criteria.chamfer_dist's, on the host, before any launch."""
+        w = float(self.chamfer_w if chamfer_w is None else chamfer_w)
+        if not w >= 0.0:
+            raise ValueError(f"get_loss: chamfer_w={w} (>= 0)")
+        if w == 0.0:
+            return 0.0, None
+        if "object_verts" not in y:
+            raise ValueError("get_loss(chamfer_w > 0) needs the object target y['object_verts'] (B, VO*3) or (B, VO, 3)")
+        from .criteria import chamfer_target_operands
+        scale, root, obj, count = chamfer_target_operands(y, who="get_loss(chamfer_w)")
+        return w, (scale.float(), root.float(), obj.float(), count)
+
     # ---- reference surface ------------------------------------------------------
-    def _reverse_kld(self, y, x, mods=None, return_dict=True, N=None, noise=None):
+    def _reverse_kld(self, y, x, mods=None, return_dict=True, N=None, noise=None, chamfer_w=None):
         """reference hand/network.py:760-831.  mods: ['uv'] (None; weak supervision), ['xyz'] or ['xyz', 'uv'] (3D supervision,
-        hand/CrossModalHand.py:354: adds the Laplace likelihood of the normalised joints against y['pose3d'], network.py:620-643)."""
+        hand/CrossModalHand.py:354: adds the Laplace likelihood of the normalised joints against y['pose3d'], network.py:620-643).
+        chamfer_w (None: self.chamfer_w) > 0: the Chamfer term of network.py:821-826 for N hypotheses - out['chamfer'][b] = mean_n of
+        criteria.chamfer_dist of row n*B+b's joints against y['object_verts'] (y['object_count'], 'scale', 'original_pose3d'), and
+        log_p -= chamfer_w * chamfer; the other keys are not touched by it."""
         bits = ops.mods_bits(mods)
         if bits & ops.MODS_XYZ and "pose3d" not in y:
             raise ValueError("get_loss(mods=[..., 'xyz']) needs the 3D target y['pose3d'] (B, 63)")
+        cw, cham = self.chamfer_operands(y, chamfer_w)
         N = N or self.loss_N
         tr = getattr(self, "_trainer", None)
         if tr is not None and self.training and torch.is_grad_enabled():
             # a train.TrainStep is attached: the loss dict comes out as ONE autograd node whose backward is the
             # hand-written reverse pass, so the reference's `total_loss.backward()` works unchanged
             from .train import differentiable_get_loss
-            return differentiable_get_loss(tr, x, y, N=N, noise=noise, mods=bits)
+            return differentiable_get_loss(tr, x, y, N=N, noise=noise, mods=bits, chamfer_w=cw)
         _, feat, _ = self.feat_extractor(x)
         B = feat.shape[0]
         if isinstance(self.q_z_giv_i, ConditionalGlow):      # entropy from the sampling pass itself (network.py:781-783,798-799)
@@ -171,7 +192,12 @@ class MHEnt(nn.Module):
             z0 = self._noise(N * B, 1.0, noise, feat.device)
             th45 = self.q_z_giv_i.forward_p(z0, cond=feat)
             log_q = self.q_z_giv_i.log_prob(th45, logvar=feat) if self.entropy else None       # network.py:801
-        if bits == ops.MODS_UV:
+        if cham is not None:
+            o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(),
+                                y["crop_uv"].contiguous() if bits & ops.MODS_UV else None, y["vis"].contiguous(), self.b_2d,
+                                self.th45_ref_alpha, want=("log_p", "norms"), mods=bits, laplace_b_3d=self.b_3d, chamfer=cham,
+                                pose3d=y["pose3d"].contiguous().float() if bits & ops.MODS_XYZ else None)
+        elif bits == ops.MODS_UV:
             o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(), y["crop_uv"].contiguous(),
                                 y["vis"].contiguous(), self.b_2d, self.th45_ref_alpha, want=("log_p", "norms"))
         else:
@@ -186,6 +212,9 @@ class MHEnt(nn.Module):
             out["log_p"] = log_p
         else:
             out["log_p"] = q_log_p
+        if cham is not None:
+            out["chamfer"] = ops.elbo_reduce(o["chamfer"], None, N, B)[0]          # mean over the N hypotheses
+            out["log_p"] = out["log_p"] - cw * out["chamfer"]
         if not return_dict:
             raise NotImplementedError
         return out

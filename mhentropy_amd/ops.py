@@ -384,7 +384,7 @@ def mods_bits(mods):
     """the reference's get_loss `mods` (hand/network.py:620-643; None means ['uv']) -> the MHE_MODS_* bit set.  'uv' and 'xyz' in any
     order; anything else (the dead p_ys branch) is not built.  The render mods 'm' / 'depth' are no likelihood here: MHEnt.sample(mods=)
     takes them (ops.render_mesh, forward only) and the train step has no mask term.  Nor is the chamfer term a mod: its distance is ops.chamfer
-    / criteria.chamfer_dist, and the train step does not take it yet"""
+    / criteria.chamfer_dist, and the loss takes it through get_loss(chamfer_w=...) (mano_joints(chamfer=...))"""
     if mods is None:
         return MODS_UV
     names = [mods] if isinstance(mods, str) else list(mods)
@@ -398,12 +398,30 @@ def mods_bits(mods):
     return bits
 
 
+def _chamfer_target(chamfer, B, who):
+    """chamfer = (scale [B], root [B,3], obj [B,VO,3], count [B] int32 | None), as criteria.chamfer_target_operands returns them -> VO"""
+    if not isinstance(chamfer, (tuple, list)) or len(chamfer) != 4:
+        raise ValueError(f"{who}: chamfer must be (scale, root, obj, count)")
+    scale, root, obj, count = chamfer
+    if not isinstance(obj, torch.Tensor) or obj.dim() != 3:
+        raise _lib.MheError(f"{who}.obj: expected a [B,VO,3] tensor")
+    VO = obj.shape[1]
+    _chk(scale, torch.float32, f"{who}.scale", (B,)); _chk(root, torch.float32, f"{who}.root", (B, 3)); _chk(obj, torch.float32, f"{who}.obj", (B, VO, 3))
+    if count is not None:
+        _chk(count, torch.int32, f"{who}.count", (B,))
+    return VO
+
+
 def mano_joints(th45, det, tables, crop_uv=None, vis=None, laplace_b=0.03, th45_alpha=50.0, inv_norm=False,
-                image_size=256.0, want=("z", "xyz", "uv", "terms", "log_p", "norms"), pose3d=None, mods=None, laplace_b_3d=0.03):
+                image_size=256.0, want=("z", "xyz", "uv", "terms", "log_p", "norms"), pose3d=None, mods=None, laplace_b_3d=0.03,
+                chamfer=None):
     """want may also include "joints_mm", and "verts" (the full mesh, normalised like xyz) or "mesh_mm" (ManoLayer's mesh in mm): the mesh
     of the same hypotheses through mhe_mano_decode_f32 - the joint pass leaves the skinning operands, no second pose pass.
     mods (None, or a MHE_MODS_* bit set / the reference's list of names): the likelihoods in terms / log_p through
-    mhe_mano_joints_mods_f32 - terms is then [R,5] = (uv, xyz, th3, th45, bt); 'xyz' needs pose3d [B,63] (Laplace with b = laplace_b_3d)."""
+    mhe_mano_joints_mods_f32 - terms is then [R,5] = (uv, xyz, th3, th45, bt); 'xyz' needs pose3d [B,63] (Laplace with b = laplace_b_3d).
+    chamfer = (scale [B], root [B,3], obj [B,VO,3], count [B] int32 | None): the same pass through mhe_mano_joints_chamfer_f32 (mods None
+    means uv there, terms [R,5]) - adds "chamfer" [R], every row's hand-object Chamfer distance in mm (ops.chamfer's, of the 21 joints);
+    log_p and the other outputs do not change by a bit."""
     R, B = th45.shape[0], det.shape[0]
     dev = th45.device
     _chk(th45, torch.float32, "mano.th45", (R, 45)); _chk(det, torch.float32, "mano.det", (B, 16))
@@ -415,6 +433,20 @@ def mano_joints(th45, det, tables, crop_uv=None, vis=None, laplace_b=0.03, th45_
     if pose3d is not None:
         _chk(pose3d, torch.float32, "mano.pose3d", (B, 63))
     bits = None if mods is None else (int(mods) if isinstance(mods, int) else mods_bits(mods))
+    if chamfer is not None:
+        VO = _chamfer_target(chamfer, B, "mano.chamfer")
+        if vis is None:
+            raise ValueError("mano_joints(chamfer=...): vis is required")
+        if "verts" in want or "mesh_mm" in want:
+            raise ValueError("mano_joints: the mesh outputs come from the uv-only pass (mods=None, chamfer=None)")
+        bits = MODS_UV if bits is None else bits
+        shapes = {"z": (R, 61), "xyz": (R, 63), "uv": (R, 42), "terms": (R, 5), "log_p": (R,), "norms": (R, 2), "joints_mm": (R, 63)}
+        o = {k: (torch.empty(shapes[k], device=dev, dtype=torch.float32) if k in want else None) for k in shapes}
+        o["chamfer"] = torch.empty(R, device=dev, dtype=torch.float32)
+        launch("mhe_mano_joints_chamfer_f32", th45, det, crop_uv, vis, pose3d, tables, *chamfer, o["z"], o["xyz"], o["uv"], o["terms"], o["log_p"],
+               o["norms"], o["joints_mm"], o["chamfer"], R, B, VO, bits, float(laplace_b), float(laplace_b_3d), float(th45_alpha), int(inv_norm),
+               float(image_size))
+        return o
     shapes = {"z": (R, 61), "xyz": (R, 63), "uv": (R, 42), "terms": (R, 4 if bits is None else 5), "log_p": (R,), "norms": (R, 2),
               "joints_mm": (R, 63)}
     o = {k: (torch.empty(shapes[k], device=dev, dtype=torch.float32) if k in want else None) for k in shapes}
@@ -439,9 +471,10 @@ def mano_joints(th45, det, tables, crop_uv=None, vis=None, laplace_b=0.03, th45_
 
 
 def mano_joints_bwd(th45, det, tables, crop_uv, vis, g_log_p, N, laplace_b=0.03, th45_alpha=50.0, pose3d=None, mods=None,
-                    laplace_b_3d=0.03):
+                    laplace_b_3d=0.03, chamfer=None, chamfer_w=0.0):
     """reverse of mano_joints' log_p: (d/d th45 [R,45], d/d det [B,16]) for d loss/d log_p[n*B+b] = g_log_p[b]/N;
-    mods / pose3d / laplace_b_3d as in mano_joints (crop_uv may be None when 'uv' is off)"""
+    mods / pose3d / laplace_b_3d as in mano_joints (crop_uv may be None when 'uv' is off).
+    chamfer (as in mano_joints) with chamfer_w: the reverse of log_p[r] - chamfer_w * chamfer[r] (mhe_mano_joints_chamfer_bwd_f32)"""
     R, B = th45.shape[0], det.shape[0]
     _chk(th45, torch.float32, "mano_bwd.th45", (R, 45)); _chk(det, torch.float32, "mano_bwd.det", (B, 16))
     if crop_uv is not None or mods is None:
@@ -452,7 +485,12 @@ def mano_joints_bwd(th45, det, tables, crop_uv, vis, g_log_p, N, laplace_b=0.03,
     _chk(g_log_p, torch.float32, "mano_bwd.g_log_p", (B,))
     g_th45 = torch.empty(R, 45, device=th45.device, dtype=torch.float32)
     g_rows = torch.empty(R, 16, device=th45.device, dtype=torch.float32)
-    if mods is None:
+    if chamfer is not None:
+        VO = _chamfer_target(chamfer, B, "mano_bwd.chamfer")
+        bits = MODS_UV if mods is None else (int(mods) if isinstance(mods, int) else mods_bits(mods))
+        launch("mhe_mano_joints_chamfer_bwd_f32", th45, det, crop_uv, vis, pose3d, tables, *chamfer, g_log_p, g_th45, g_rows, R, B, VO, bits,
+               float(laplace_b), float(laplace_b_3d), float(th45_alpha), 1.0 / N, float(chamfer_w))
+    elif mods is None:
         launch("mhe_mano_joints_bwd_f32", th45, det, crop_uv, vis, tables, g_log_p, g_th45, g_rows, R, B, float(laplace_b), float(th45_alpha), 1.0 / N)
     else:
         bits = int(mods) if isinstance(mods, int) else mods_bits(mods)

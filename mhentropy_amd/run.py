@@ -6,6 +6,7 @@ on synthetic batches (no dataset ships with this repository; the HO3D pipeline i
     python -m mhentropy_amd.run --backbone resnet50 --batch 256 --hyps 64 --dtype bf16 --epochs 1 --iters 20
     python -m torch.distributed.run --nproc-per-node 8 -m mhentropy_amd.run ...      # one process per GPU, RCCL
     python -m mhentropy_amd.run --mods uv,xyz ...        # 3D-supervised training (hand/CrossModalHand.py:354, mods = ['xyz', 'uv'])
+    python -m mhentropy_amd.run --chamfer-w 10 ...       # with the hand-object Chamfer term (hand/network.py:821-826, w_chamfer = 10)
 """
 import argparse
 import json
@@ -52,7 +53,13 @@ def main(argv=None):
     ap.add_argument("--mods", default="uv",
                     help="likelihoods of the loss, comma-separated (hand/CrossModalHand.py:354): uv (weak supervision, the reference's default), "
                          "uv,xyz or xyz (3D supervision: adds the Laplace likelihood of the normalised joints against the batch's pose3d)")
+    ap.add_argument("--chamfer-w", type=float, default=0.0,
+                    help="weight of the hand-object Chamfer term in the loss (hand/network.py:821-826: the reference's w_chamfer is 10, behind a "
+                         "switch it ships off; 0 = off).  Synthetic objects (synth.object_targets) by default, the pipeline's object_verts "
+                         "with object_count = the decoded samples' obj_count under --input-pipeline")
     args = ap.parse_args(argv)
+    if args.chamfer_w < 0:
+        raise SystemExit("--chamfer-w must be >= 0")
     from . import ops
     mods = [m.strip() for m in args.mods.split(",") if m.strip()]
     ops.mods_bits(mods)                               # NotImplementedError for anything but uv / xyz, before any work
@@ -105,20 +112,26 @@ def main(argv=None):
         for it in range(args.iters):
             if args.input_pipeline:
                 order = aug_rng.randint(0, len(pool), args.batch)
-                x, y = pipe(hd.collate_decoded([pool[i] for i in order]), aug=hd.draw_aug(args.batch, aug_rng))
+                raw = hd.collate_decoded([pool[i] for i in order])
+                x, y = pipe(raw, aug=hd.draw_aug(args.batch, aug_rng))
+                if args.chamfer_w > 0:
+                    y["object_count"] = raw["obj_count"]
             else:
                 xn, yn = synth.batch(args.seed + 1000 * rank + step, args.batch, image_size=args.image_size)
                 x = torch.as_tensor(xn).cuda()
+                if args.chamfer_w > 0:
+                    yn.update(synth.object_targets(args.seed + 1000 * rank + step, args.batch, with_count=True))
                 y = {k: torch.as_tensor(v).cuda() for k, v in yn.items()}
             model.training_step_start(step)
             if args.graph and not args.test_samples:
                 from .train import GraphedStep
-                yk = {k: y[k].contiguous() for k in ("crop_uv", "vis") + (("pose3d",) if "xyz" in mods else ())}     # what the loss consumes
+                yk = {k: y[k].contiguous() for k in ("crop_uv", "vis") + (("pose3d",) if "xyz" in mods else ()) +      # what the loss consumes
+                      (("object_verts", "object_count", "scale", "original_pose3d") if args.chamfer_w > 0 else ())}
                 if graphed is None or graphed_lr != trainer.lr:
                     # (re-)capture: GraphedStep's warm-up pass is one real step on this batch - it IS this iteration (replaying the
                     # same batch as well would apply two optimizer steps to it and advance Adam's count and the BatchNorm buffers twice)
                     sx, sy = x.clone(), {k: v.clone() for k, v in yk.items()}
-                    graphed, graphed_lr = GraphedStep(trainer, sx, sy, N=args.hyps, mods=mods), trainer.lr
+                    graphed, graphed_lr = GraphedStep(trainer, sx, sy, N=args.hyps, mods=mods, chamfer_w=args.chamfer_w), trainer.lr
                     out = graphed.warm_out
                 else:
                     sx.copy_(x)
@@ -126,7 +139,7 @@ def main(argv=None):
                         sy[k].copy_(v)
                     out = graphed.replay()
             else:
-                out = trainer.step(x, y, N=args.hyps, test_samples=args.test_samples, mods=mods)
+                out = trainer.step(x, y, N=args.hyps, test_samples=args.test_samples, mods=mods, chamfer_w=args.chamfer_w)
             with torch.no_grad():
                 total, losses, metrics = criterion(dict(out), y)
             meters["loss"].update(float(total))

@@ -168,6 +168,23 @@ def batch(seed=0, B=2, image_size=256, with_image=True):
     return x, y
 
 
+def object_targets(seed=0, B=2, VO=256, with_count=False):
+    """Seeded object targets of B images for the hand-object Chamfer term (get_loss(chamfer_w=...), criteria.chamfer_dist), in the units
+    of the data: original_pose3d (B,21,3) in mm (row 12, the root, about half a metre in front of the camera), scale (B,) the bone length
+    in m (0.025..0.04), object_verts (B, VO*3) within 90 mm of the root and, with_count, object_count (B,) int32 in VO//2..VO (the
+    vertices past it are zero padding, as the input pipeline leaves them).  A dict to merge into batch()'s target: it replaces
+    batch()'s 'scale' (drawn there for the metrics, 0.5..1.5, with which normalised joints would span metres)."""
+    rng = np.random.default_rng(seed + 6000)
+    pose = (rng.normal(0, 40.0, (B, 21, 3)) + np.array([0.0, 0.0, 500.0])).astype(np.float32)
+    y = {"original_pose3d": pose, "scale": rng.uniform(0.025, 0.04, (B,)).astype(np.float32)}
+    obj = (pose[:, 12][:, None, :] + rng.uniform(-90.0, 90.0, (B, VO, 3))).astype(np.float32)
+    if with_count:
+        y["object_count"] = rng.integers(max(VO // 2, 1), VO + 1, (B,)).astype(np.int32)
+        obj[np.arange(VO)[None, :] >= y["object_count"][:, None]] = 0.0
+    y["object_verts"] = obj.reshape(B, VO * 3)
+    return y
+
+
 def structured_images(seed=0, B=2, image_size=256):
     """Images with image-to-image structure (a smooth random field per image: random 4x4 / 16x16 colour patterns bilinearly enlarged, a
     per-image gain and offset, a little pixel noise), in [-1,1].  batch()'s default images are i.i.d. white noise: after global average pooling

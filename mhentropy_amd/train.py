@@ -9,7 +9,7 @@ with total_loss = mean_b(-log_p[b]) (hand/criteria.py:55,173).
 There is no autograd graph here: `TrainStep` runs the forward of MHEnt.get_loss stage by stage keeping
 what the reverse pass needs (raw convolution outputs, post-activation tensors, BatchNorm batch
 statistics, the flow sample), then walks the stages backwards through hand-written reverse kernels:
-    loss -> MANO likelihood (mhe_mano_joints_bwd_f32) -> RealNVP couplings (re-evaluated layer by layer,
+    loss -> MANO likelihood (mhe_mano_joints_bwd_f32; with the hand-object Chamfer term mhe_mano_joints_chamfer_bwd_f32) -> RealNVP couplings (re-evaluated layer by layer,
     csrc/flow_bwd.hip + mhe_conv_wgrad_nhwc) -> conditioning / det-head / l1 dense layers -> ResNet trunk
     (data gradients through the forward implicit-GEMM kernel on transposed, tap-flipped weights; weight
     gradients through mhe_conv_wgrad_nhwc; train-mode BatchNorm reverse) -> clip + Adam (one fused pass).
@@ -726,16 +726,19 @@ class TrainStep:
         self._grad_ready(0)
 
     # ------------------------------------------------------------------ the step
-    def forward(self, x, y, noise=None, N=None, trunk_out=None, mods=None):
+    def forward(self, x, y, noise=None, N=None, trunk_out=None, mods=None, chamfer_w=None):
         """forward of MHEnt.get_loss (hand/network.py:760-831) keeping what the reverse pass needs.  Returns the get_loss dict.
         trunk_out (B, feat_dim) f32 (testing aid): stands in for the ResNet trunk's output, whose forward and reverse
         passes are then skipped - the reference's golden gradients are pinned from the trunk feature on.
-        mods: get_loss's likelihoods (None = ['uv']; ['xyz'] / ['xyz', 'uv'] read y['pose3d'], hand/CrossModalHand.py:354)."""
+        mods: get_loss's likelihoods (None = ['uv']; ['xyz'] / ['xyz', 'uv'] read y['pose3d'], hand/CrossModalHand.py:354).
+        chamfer_w: get_loss's weight of the hand-object Chamfer term (None: the model's chamfer_w; > 0 reads y['object_verts'], 'scale',
+        'original_pose3d' and, if present, 'object_count'; 0 launches what the step launched without the argument)."""
         m = self.model
         N = N or m.loss_N
         bits = ops.mods_bits(mods) if not isinstance(mods, int) else mods
         if bits & ops.MODS_XYZ and "pose3d" not in y:
             raise ValueError("TrainStep.forward(mods=[..., 'xyz']) needs the 3D target y['pose3d'] (B, 63)")
+        cw, cham = m.chamfer_operands(y, chamfer_w)
         B = x.shape[0] if trunk_out is None else trunk_out.shape[0]
         self.arena.sync()     # someone else (torch.optim, load_state_dict) may have written the parameters
         f = self._trunk_forward(x.contiguous()) if trunk_out is None else trunk_out.contiguous()
@@ -749,6 +752,8 @@ class TrainStep:
             feat_own, feat = feat, hs.gather_rows(feat)                       # (world*B, 512): every image's conditioning feature
             feat_b = None
             y = {k: hs.gather_rows(y[k]) for k in ("crop_uv", "vis") + (("pose3d",) if bits & ops.MODS_XYZ else ())}
+            if cham is not None:       # the object targets of every image: (scale, root, vertices, count) rows, rank-major like the features
+                cham = tuple(None if t is None else hs.gather_rows(t) for t in cham)
             if noise is not None:
                 noise = hs.gather_hypothesis_rows(noise.reshape(N * B, 45), B)
             lo, hi = hs.hypotheses()
@@ -759,25 +764,34 @@ class TrainStep:
         blob = m.mano_dec.table_blob()
         cu, vis = y["crop_uv"].contiguous() if bits & ops.MODS_UV else None, y["vis"].contiguous()
         p3 = y["pose3d"].contiguous().float() if bits & ops.MODS_XYZ else None
-        if bits == ops.MODS_UV:
+        if cham is not None:
+            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=("log_p", "norms"), pose3d=p3, mods=bits,
+                                laplace_b_3d=m.b_3d, chamfer=cham)
+        elif bits == ops.MODS_UV:
             o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=("log_p", "norms"))
         else:
             o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=("log_p", "norms"), pose3d=p3, mods=bits,
                                 laplace_b_3d=m.b_3d)
         q_log_p, hq, log_p = ops.elbo_reduce(o["log_p"], log_q if m.entropy else None, N, B)
+        ch = ops.elbo_reduce(o["chamfer"], None, N, B)[0] if cham is not None else None      # mean over the (local) hypotheses
         if hs is not None:
             # means over the local hypotheses -> sums -> all-reduce -> means over all K; each rank reports its own images
-            part = torch.stack([q_log_p, hq]) * (float(N) / N_all)
+            part = torch.stack([q_log_p, hq] + ([ch] if ch is not None else [])) * (float(N) / N_all)
             hs.reduce_images(part)
             own = slice(hs.rank * B_own, (hs.rank + 1) * B_own)
             q_log_p, hq = part[0, own].contiguous(), part[1, own].contiguous()
             log_p = hq + q_log_p
+            if ch is not None:
+                ch = part[2, own].contiguous()
         out = {"th_norm": o["norms"][:, 0], "bt_norm": o["norms"][:, 1], "q_log_p_z_giv_y": q_log_p,
                "log_p": log_p if m.entropy else q_log_p}
         if m.entropy:
             out["h_q_z_giv_i"] = hq
+        if ch is not None:
+            out["chamfer"] = ch
+            out["log_p"] = out["log_p"] - cw * ch
         self.tape = {"f": f, "feat": feat, "hd": hd, "det": det, "th45": th45, "blob": blob, "cu": cu, "vis": vis,
-                     "p3": p3, "mods": bits, "N": N, "B": B, "trunk": trunk_out is None, "hs": hs, "B_own": B_own, "N_all": N_all, "feat_own": feat_own}
+                     "p3": p3, "mods": bits, "cham": cham, "chamfer_w": cw, "N": N, "B": B, "trunk": trunk_out is None, "hs": hs, "B_own": B_own, "N_all": N_all, "feat_own": feat_own}
         return out
 
     def backward(self, g_log_p=None):
@@ -795,7 +809,8 @@ class TrainStep:
             g_logp.copy_(hs.gather_rows(g_log_p.reshape(B_own).contiguous()))
         else:
             g_logp.copy_(g_log_p.reshape(B))
-        g45, gdet_rows = self._mano_bwd(th45, det, t["blob"], t["cu"], t["vis"], g_logp, N_all, t["p3"], t["mods"])
+        g45, gdet_rows = self._mano_bwd(th45, det, t["blob"], t["cu"], t["vis"], g_logp, N_all, t["p3"], t["mods"], t.get("cham"),
+                                        t.get("chamfer_w", 0.0))
         self.part.reverse(th45, g45, g_logp if m.entropy else None, N, B, N_all)
         # det head: gdet [B,16] -> padded [B,32]
         gdet = self.arena.buf("gdet", (B, 32)); gdet.zero_()
@@ -822,9 +837,9 @@ class TrainStep:
             self.G.mul_(1.0 / self.world)
             self._G_averaged = True        # optimizer_step() must not divide by world a second time
 
-    def forward_backward(self, x, y, noise=None, N=None, trunk_out=None, mods=None):
+    def forward_backward(self, x, y, noise=None, N=None, trunk_out=None, mods=None, chamfer_w=None):
         """forward + reverse pass of total = mean_b(-log_p[b]); fills self.G.  Returns the get_loss dict + 'total'."""
-        out = self.forward(x, y, noise=noise, N=N, trunk_out=trunk_out, mods=mods)
+        out = self.forward(x, y, noise=noise, N=N, trunk_out=trunk_out, mods=mods, chamfer_w=chamfer_w)
         self.backward()
         out["total"] = -out["log_p"].mean()
         return out
@@ -838,10 +853,13 @@ class TrainStep:
         self.model._trainer = self
         return self
 
-    def _mano_bwd(self, th45, det, blob, cu, vis, g_logp, N, p3=None, mods=ops.MODS_UV):
+    def _mano_bwd(self, th45, det, blob, cu, vis, g_logp, N, p3=None, mods=ops.MODS_UV, cham=None, chamfer_w=0.0):
         R, B = th45.shape[0], det.shape[0]
         g45 = self.arena.buf("g45", (R, 45)); rows = self.arena.buf("gdet_rows", (R, 16))
-        if mods == ops.MODS_UV:
+        if cham is not None:
+            ops.launch("mhe_mano_joints_chamfer_bwd_f32", th45, det, cu, vis, p3, blob, *cham, g_logp, g45, rows, R, B, cham[2].shape[1], int(mods),
+                       float(self.model.b_2d), float(self.model.b_3d), float(self.model.th45_ref_alpha), 1.0 / N, float(chamfer_w))
+        elif mods == ops.MODS_UV:
             ops.launch("mhe_mano_joints_bwd_f32", th45, det, cu, vis, blob, g_logp, g45, rows, R, B, float(self.model.b_2d), float(self.model.th45_ref_alpha),
                        1.0 / N)
         else:
@@ -877,14 +895,14 @@ class TrainStep:
         torch._foreach_lerp_([u.bn.running_var for u in units], var, BN_MOMENTUM)
         torch._foreach_add_([u.bn.num_batches_tracked for u in units], 1)
 
-    def step(self, x, y, noise=None, N=None, test_samples=0, temp=0.8, double_bn_update=True, mods=None):
+    def step(self, x, y, noise=None, N=None, test_samples=0, temp=0.8, double_bn_update=True, mods=None, chamfer_w=None):
         """one iteration of the reference's training loop (hand/CrossModalHand.py:353-361,455-470).  test_samples > 0
         adds its per-iteration metrics pass `sample(N=[n,n], temp=0.8, mods={uv,xyz,verts})` to the returned dict,
         from the conditioning feature of THIS forward.  The reference runs the encoder a second time on the same
         batch in train mode for it: same feature, but the BatchNorm running statistics advance twice per iteration -
         double_bn_update=True (default) reproduces that on the buffers, so checkpoints / eval-mode results match a
-        reference-trained model.  mods: get_loss's likelihoods, as in forward()."""
-        out = self.forward_backward(x, y, noise=noise, N=N, mods=mods)
+        reference-trained model.  mods, chamfer_w: get_loss's likelihoods and Chamfer weight, as in forward()."""
+        out = self.forward_backward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w)
         if test_samples:
             if double_bn_update and self.tape["trunk"]:
                 self.second_bn_update()
@@ -901,18 +919,20 @@ class GraphedStep:
     (RCCL, async_op: it runs on the communicator's stream under the next graph's kernels), the next graph starts; the last
     graph (norm, clip, Adam, operand re-pack) is launched after the waits.  Six graphs and four collectives per step."""
 
-    def __init__(self, ts, x, y, noise=None, N=None, test_samples=0, criterion=None, mods=None):
+    def __init__(self, ts, x, y, noise=None, N=None, test_samples=0, criterion=None, mods=None, chamfer_w=None):
         """test_samples / criterion: the reference's whole iteration (hand/CrossModalHand.py:349-361,452-470) in the graph - the
         metrics pass sample(N=[n,n], temp=0.8) from this forward's feature and `criterion(out, y)` (MHEntLoss: 14 metrics);
         self.out then carries 'criterion' = (total, losses, metrics).  mods: get_loss's likelihoods (TrainStep.forward); with 'xyz'
-        the graphs read y['pose3d'] - a new target is copied into that static tensor like the rest of the batch"""
+        the graphs read y['pose3d'] - a new target is copied into that static tensor like the rest of the batch.  chamfer_w > 0 (None: the
+        model's): y['object_verts'], 'scale', 'original_pose3d' and 'object_count' are static inputs in the same way; the count's range is
+        checked on the host by the warm-up step only (a capturing stream takes no host read: the kernels clamp it to 1..VO)"""
         if ts.shard_hypotheses:
             raise NotImplementedError("GraphedStep: the hypothesis-sharded forward has collectives inside the forward pass")
         self.ts, self.graphs, self.actions = ts, [], []
         _step = ts.step
 
         def step(x, y, noise=None, N=None):
-            out = _step(x, y, noise=noise, N=N, test_samples=test_samples, mods=mods)
+            out = _step(x, y, noise=noise, N=N, test_samples=test_samples, mods=mods, chamfer_w=chamfer_w)
             if criterion is not None:
                 with torch.no_grad():
                     out["criterion"] = criterion(dict(out), y)
@@ -969,8 +989,8 @@ class GraphedStep:
 class _LossFn(torch.autograd.Function):
     """MHEnt.get_loss as one autograd node: forward = TrainStep.forward, backward = TrainStep.backward(d loss / d log_p)."""
     @staticmethod
-    def forward(ctx, trainer, x, y, N, noise, mods, *params):
-        out = trainer.forward(x, y, noise=noise, N=N, mods=mods)
+    def forward(ctx, trainer, x, y, N, noise, mods, chamfer_w, *params):
+        out = trainer.forward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w)
         ctx.trainer, ctx.keys = trainer, list(out)
         vals = tuple(out[k] for k in ctx.keys)
         ctx.mark_non_differentiable(*[v for k, v in zip(ctx.keys, vals) if k != "log_p"])
@@ -981,12 +1001,13 @@ class _LossFn(torch.autograd.Function):
         tr = ctx.trainer
         g = grads[ctx.keys.index("log_p")]
         tr.backward(None if g is None else g.contiguous().float())
-        return (None, None, None, None, None, None) + tuple(tr.grad_of(p) for p in tr.arena.params)
+        return (None, None, None, None, None, None, None) + tuple(tr.grad_of(p) for p in tr.arena.params)
 
 
-def differentiable_get_loss(trainer, x, y, N=None, noise=None, mods=None):
-    vals = _LossFn.apply(trainer, x, y, N, noise, mods, *trainer.arena.params)
-    return dict(zip(_LossFn_keys(trainer), vals))
+def differentiable_get_loss(trainer, x, y, N=None, noise=None, mods=None, chamfer_w=None):
+    w, _ = trainer.model.chamfer_operands(y, chamfer_w)
+    vals = _LossFn.apply(trainer, x, y, N, noise, mods, w, *trainer.arena.params)
+    return dict(zip(_LossFn_keys(trainer) + (["chamfer"] if w > 0 else []), vals))
 
 
 def _LossFn_keys(trainer):
