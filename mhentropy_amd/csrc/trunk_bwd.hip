@@ -144,8 +144,8 @@ __global__ __launch_bounds__(256) void bn_mean_invstd_kernel(const mhe_stat_t *_
     mean_invstd[C + c] = 1.f / sqrtf((float)dvar + eps);
 }
 
-// 3x3 stride-2 pad-1 max pool that also records which of the 9 taps won (first maximum in scan order, as
-// torch's max_pool2d does) so that the reverse pass is a gather
+// 3x3 stride-2 pad-1 max pool that also records which of the 9 taps won (first maximum in scan order over the taps inside
+// the image, as torch's max_pool2d does) so that the reverse pass is a gather
 template <typename T>
 __global__ void maxpool_idx_kernel(const T *__restrict__ x, T *__restrict__ y, unsigned char *__restrict__ idx, int B, int H,
                                    int W, int C, int Ho, int Wo) {
@@ -157,8 +157,11 @@ __global__ void maxpool_idx_kernel(const T *__restrict__ x, T *__restrict__ y, u
         const int wo = (int)(t % Wo); t /= Wo;
         const int ho = (int)(t % Ho);
         const int b = (int)(t / Ho);
-        float m[4] = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+        // the first tap inside the image starts the scan (not a finite sentinel at tap 0: a window of -inf, or of values below the sentinel,
+        // pooled to the sentinel with a winner that can lie outside the image, and the reverse pass dropped its gradient)
+        float m[4] = {0.f, 0.f, 0.f, 0.f};
         unsigned am[4] = {0, 0, 0, 0};
+        bool first = true;
 #pragma unroll
         for (int dh = 0; dh < 3; ++dh)
 #pragma unroll
@@ -169,7 +172,8 @@ __global__ void maxpool_idx_kernel(const T *__restrict__ x, T *__restrict__ y, u
                 load4<T>(x + (((size_t)b * H + hi) * W + wi) * C + c, v);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    if (v[k] > m[k]) { m[k] = v[k]; am[k] = dh * 3 + dw; }
+                    if (first || v[k] > m[k]) { m[k] = v[k]; am[k] = dh * 3 + dw; }
+                first = false;
             }
         store4<T>(y + e, m);
         *reinterpret_cast<unsigned *>(idx + e) = am[0] | (am[1] << 8) | (am[2] << 16) | (am[3] << 24);

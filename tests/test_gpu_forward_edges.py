@@ -38,6 +38,7 @@ import pytest
 import torch
 
 from conftest import assert_close
+from edge_measure import Measure as _Measure
 
 BF, F32 = torch.bfloat16, torch.float32
 U32, UB = 2.0 ** -24, 2.0 ** -8
@@ -57,29 +58,6 @@ def _np(t):
 def _bits(t):
     t = t.detach().cpu().contiguous()
     return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-class _Measure:
-    """collects |diff| / bound over the cases of one test; report() prints the largest ratio, then asserts every case (ratio <= 1)"""
-
-    def __init__(self, kernel):
-        self.kernel, self.rows = kernel, []
-
-    def add(self, case, got, ref, bound):
-        got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-        assert got.shape == ref.shape, (self.kernel, case, got.shape, ref.shape)
-        bound = np.broadcast_to(np.asarray(bound, np.float64), ref.shape)
-        diff = np.abs(got - ref)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            ratio = np.where(diff == 0.0, 0.0, diff / bound)          # a zero bound admits a zero difference only; NaN stays NaN
-        self.rows.append((case, ratio))
-
-    def report(self):
-        worst = [(float("inf") if np.isnan(r).any() else float(r.max()) if r.size else 0.0, case) for case, r in self.rows]
-        top = max(worst, key=lambda w: w[0])
-        print("forward-edges: %s: max(|diff| / bound) = %.3f over %d cases (at %s)" % (self.kernel, top[0], len(worst), top[1]))
-        for case, ratio in self.rows:
-            assert_close(ratio, np.zeros_like(ratio), 0.0, atol=1.0, what="%s %s: |diff| / bound" % (self.kernel, case))
 
 
 # ---- references (float64, CPU) -----------------------------------------------------------------------------------------------------------
