@@ -312,25 +312,40 @@ void conv1x1_stream_kernel(const Params p, int nchunks, int ntiles_n) {
 // 16.  XOR with 2 * ((row >> 1) & 3) is conflict-free for every first row (rows of one parity: the 4 + 4 rows cover all four values).
 __device__ __forceinline__ int swz3(int row, int slot) { return row * 8 + (slot ^ (((row >> 1) & 3) << 1)); }
 
-// Two roles in one 512-thread workgroup (one wave of each role per SIMD):
+// ROLES roles in one workgroup of 256 x ROLES threads, one wave of each role per SIMD.
 //   multiply waves 0-3 : per tick 144 MFMAs (two output rows x 64 pixels x 64 channels; a wave = 32 pixels of one row, all channels), then the
 //                        accumulators as bf16 into the staging buffer of this tick's parity;
-//   transfer waves 4-7 : global loads of the input rows two ticks ahead into registers, (BatchNorm + ReLU,) the row pair of the next tick into
-//                        the ring, and the epilogue of the PREVIOUS tick's output (staging -> batch statistics or the data-gradient
-//                        epilogue -> 16-byte global stores).
+//   load waves 4-7     : global loads of the input rows two ticks ahead into registers, (BatchNorm + ReLU,) the row pair of the next tick into
+//                        the ring;
+//   store waves        : the epilogue of the PREVIOUS tick's output (staging -> batch statistics or the data-gradient epilogue -> 16-byte
+//                        global stores) and, at the end, the fold of the per-thread partial sums into the workgroup's shard.
+//                        ROLES = 3 (BatchNorm on load, 768 threads): waves 8-11.  ROLES = 2 (plain and data-gradient forms, 512 threads):
+//                        the load waves do this too, after the ring write of the same tick ("transfer waves").
 // One barrier per tick.  Input rows travel in pairs (2k - 1, 2k), k = 0 .. ceil(H / 2); tick t holds pair t of the flat stream over this
 // workgroup's images and multiplies the step whose second pair it is (no step on an image's first pair: 1 tick in 33 idle at H = 64).
+// Who touches what between barrier t and barrier t + 1 (ring slot of pair k = k % 3 in the flat stream, staging by tick parity):
+//   multiply : reads ring slots (t - 1) % 3 and t % 3, writes staging t & 1;
+//   load     : writes ring slot (t + 1) % 3 - the slot of pair t - 2, last read by the multiply waves in tick t - 1, next read in tick t + 1;
+//   store    : reads staging (t - 1) & 1 - written in tick t - 1, next written in tick t + 1.
+// No role reads and no two roles write the same slot or parity inside one tick, and every write -> read and read -> write pair above lies in
+// different ticks: the barrier alone orders them, whichever waves carry the roles (pair 0, the pad columns and the weights are written
+// before barrier 0).
 // With one role doing everything in turn (the first version) the MFMA pipe idled during loads, staging and stores: 96 us; the 16-pixel
-// wave tile before that needed 320 B/clk of LDS reads per CU: 127 us.
-template <bool BNLOAD, bool DG>
-__global__ __launch_bounds__(512) void conv3x3_c64_stream_kernel(const Params p) {
+// wave tile before that needed 320 B/clk of LDS reads per CU: 127 us.  With BatchNorm + ReLU on the load AND the statistics in the transfer
+// waves that single instruction stream per SIMD was the long role of the tick (101 us alone, 126 us in the step); as two streams 83 us.
+// The plain form gains nothing from the third role (93 us either way: its transfer role is short) and the data-gradient form has no
+// registers for it (218 VGPRs against 170 at three waves per SIMD): both stay on two.
+template <bool BNLOAD, bool DG, int ROLES>
+__device__ __forceinline__ void conv3x3_c64_stream_body(const Params &p) {
+    static_assert(ROLES == 2 || (ROLES == 3 && !DG), "the data-gradient form keeps its two roles");
     using T = u16;
-    constexpr int NTH = 512, NT2 = 256, CPR = 8, WPX = 64, RROW = (WPX + 2) * 8;   // 16-byte chunks per output row; uint4 per row buffer
+    constexpr int NTH = 256 * ROLES, NT2 = 256, CPR = 8, WPX = 64, RROW = (WPX + 2) * 8;   // 16-byte chunks per output row; uint4 per row buffer
     __shared__ uint4 Wl[9 * 64 * 8];                                        // [tap][64 output channels][64 input channels]          72 KiB
     __shared__ uint4 Rl[6][RROW];                                           // three pair slots; pixel slots 0 and 65 = zero padding 49.5 KiB
     __shared__ uint4 Ol[2][1024];                                           // output staging of two rows, by tick parity            32 KiB
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, l15 = lane & 15;
     const bool mult = wave < 4;
+    const bool storer = !mult && (ROLES == 2 || wave >= 8);
     const int t2 = tid & (NT2 - 1);
     const int s = t2 & 7, pbase = t2 >> 3;
     const int wrow = (wave >> 1) & 1, wpx = (wave & 1) * 32;                // multiply wave: output row y + wrow, pixels wpx .. wpx + 31
@@ -415,8 +430,10 @@ __global__ __launch_bounds__(512) void conv3x3_c64_stream_kernel(const Params p)
     } else {
         float sc[8], sh[8];
         if constexpr (BNLOAD) {
+            if (ROLES == 2 || wave < 8) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) { sc[i] = p.in_scale[s * 8 + i]; sh[i] = p.in_shift[s * 8 + i]; }
+                for (int i = 0; i < 8; ++i) { sc[i] = p.in_scale[s * 8 + i]; sh[i] = p.in_shift[s * 8 + i]; }
+            }
         }
         const T *mk = reinterpret_cast<const T *>(p.mask), *rg = reinterpret_cast<const T *>(p.residual);
         const T *y0g = reinterpret_cast<const T *>(p.bn_y[0]), *y1g = reinterpret_cast<const T *>(p.bn_y[1]);
@@ -542,38 +559,51 @@ __global__ __launch_bounds__(512) void conv3x3_c64_stream_kernel(const Params p)
             if (li < nimg) load_pair(li, lk, SET);
             if (++lk == npair) { lk = 0; ++li; }
         };
-        next_load(S0{});
-        store_pair(0, 0, S0{});                                              // pair 0 (the only exposed load)
-        next_load(S1{});                                                     // pair 1: written in tick 0
-        next_load(S0{});                                                     // pair 2: written in tick 1
-        int wk = 1, ws = 1;                                                  // the pair written in this tick (t + 1): index in its image, slot
         int ci = 0, ck = 0, pi = 0, pk = 0;                                  // pair of this tick, of the previous tick
-        auto tick = [&](int t, auto SET) __attribute__((always_inline)) {
-            __syncthreads();
-            if (t + 1 < NT) store_pair(wk, ws, SET);
-            if (++wk == npair) wk = 0;
-            ws = ws == 2 ? 0 : ws + 1;
-            if (t >= 1 && pk >= 1) epilogue(pi, pk, (t - 1) & 1);            // first everything that consumes loaded registers ...
-            next_load(SET);                                                  // ... then this tick's loads: pair t + 3
-            if (t < NT && ck >= 1) dg_load(ci, ck);
-            pi = ci; pk = ck;
-            if (++ck == npair) { ck = 0; ++ci; }
-        };
-        for (int t = 0; t <= NT; t += 2) {
-            tick(t, S1{});
-            if (t + 1 <= NT) tick(t + 1, S0{});
+        if (ROLES == 2 || wave < 8) {
+            next_load(S0{});
+            store_pair(0, 0, S0{});                                          // pair 0 (the only exposed load)
+            next_load(S1{});                                                 // pair 1: written in tick 0
+            next_load(S0{});                                                 // pair 2: written in tick 1
+            int wk = 1, ws = 1;                                              // the pair written in this tick (t + 1): index in its image, slot
+            auto tick = [&](int t, auto SET) __attribute__((always_inline)) {
+                __syncthreads();
+                if (t + 1 < NT) store_pair(wk, ws, SET);
+                if (++wk == npair) wk = 0;
+                ws = ws == 2 ? 0 : ws + 1;
+                if constexpr (ROLES == 2) {
+                    if (t >= 1 && pk >= 1) epilogue(pi, pk, (t - 1) & 1);    // first everything that consumes loaded registers ...
+                }
+                next_load(SET);                                              // ... then this tick's loads: pair t + 3
+                if constexpr (ROLES == 2) {
+                    if (t < NT && ck >= 1) dg_load(ci, ck);
+                    pi = ci; pk = ck;
+                    if (++ck == npair) { ck = 0; ++ci; }
+                }
+            };
+            for (int t = 0; t <= NT; t += 2) {
+                tick(t, S1{});
+                if (t + 1 <= NT) tick(t + 1, S0{});
+            }
+        } else {                                                             // store waves of the three-role form
+            for (int t = 0; t <= NT; ++t) {
+                __syncthreads();
+                if (t >= 1 && pk >= 1) epilogue(pi, pk, (t - 1) & 1);
+                pi = ci; pk = ck;
+                if (++ck == npair) { ck = 0; ++ci; }
+            }
         }
     }
-    // fold the transfer threads' partial sums (threads sharing a column chunk: 32 of them) and add them to this workgroup's shard
+    // fold the store threads' partial sums (threads sharing a column chunk: 32 of them) and add them to this workgroup's shard
     float *red = reinterpret_cast<float *>(Ol[0]);
     auto fold = [&](const float *a8, const float *b8, fx::acc_t *dst) __attribute__((always_inline)) {
         __syncthreads();
-        if (!mult) {
+        if (storer) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) { red[t2 * 16 + i] = a8[i]; red[t2 * 16 + 8 + i] = b8[i]; }
         }
         __syncthreads();
-        if (!mult && t2 < 64) {
+        if (storer && t2 < 64) {
             const int cch = t2 / 8, e = t2 % 8;
             float a = 0.f, b = 0.f;
             for (int k = 0; k < NT2 / CPR; ++k) { a += red[(cch + CPR * k) * 16 + e]; b += red[(cch + CPR * k) * 16 + 8 + e]; }
@@ -588,6 +618,11 @@ __global__ __launch_bounds__(512) void conv3x3_c64_stream_kernel(const Params p)
     } else if (st_on) fold(ss1, ss2, p.stats);
 }
 
+template <bool BNLOAD, bool DG>
+__global__ __launch_bounds__(512) void conv3x3_c64_stream_kernel(const Params p) { conv3x3_c64_stream_body<BNLOAD, DG, 2>(p); }
+template <bool BNLOAD>
+__global__ __launch_bounds__(768) void conv3x3_c64_roles3_kernel(const Params p) { conv3x3_c64_stream_body<BNLOAD, false, 3>(p); }
+
 bool stream3_supports(const Params &p) {
     if (!(p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.Cin == 64 && p.Cout == 64 && p.W == 64 && p.Kpad == 576 && p.B >= 128 &&
           p.H >= 16 && !p.x2 && !p.out_scale && !p.out_shift && !p.relu_out && !p.y32 && !p.os2 && !p.a_out && !p.res_s2))
@@ -597,10 +632,10 @@ bool stream3_supports(const Params &p) {
 }
 
 int launch_stream3(const Params &p, hipStream_t s) {
-    const dim3 grid((unsigned)(p.B < 256 ? p.B : 256)), block(512);
-    if (p.mask) hipLaunchKernelGGL((conv3x3_c64_stream_kernel<false, true>), grid, block, 0, s, p);
-    else if (p.in_scale) hipLaunchKernelGGL((conv3x3_c64_stream_kernel<true, false>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((conv3x3_c64_stream_kernel<false, false>), grid, block, 0, s, p);
+    const dim3 grid((unsigned)(p.B < 256 ? p.B : 256));
+    if (p.mask) hipLaunchKernelGGL((conv3x3_c64_stream_kernel<false, true>), grid, dim3(512), 0, s, p);      // data gradient: two roles
+    else if (p.in_scale) hipLaunchKernelGGL((conv3x3_c64_roles3_kernel<true>), grid, dim3(768), 0, s, p);    // on-load form: three roles
+    else hipLaunchKernelGGL((conv3x3_c64_stream_kernel<false, false>), grid, dim3(512), 0, s, p);
     return check_launch("conv3x3_c64_stream_kernel");
 }
 

@@ -157,7 +157,8 @@ def _conv_kernel_name(d, dt, mode):
     if tile == 10:
         return "mhe::conv::conv_tail_kernel<false>"
     if tile == 9:
-        return "mhe::conv::conv3x3_c64_stream_kernel<%s, false>" % ("true" if mode == 1 else "false")
+        # (BatchNorm on load: the three-role form; plain: two roles)
+        return "mhe::conv::conv3x3_c64_roles3_kernel<true>" if mode == 1 else "mhe::conv::conv3x3_c64_stream_kernel<false, false>"
     if tile == 8:
         return "mhe::conv::conv1x1_stream_kernel<%d, %d, %s, false>" % (d.Cin // 64, 64 if (d.Cin == 64 and d.Cout == 64) else 256 if d.Cin <= 128 else 128, "true" if mode == 1 else "false")
     if tile == 13:
