@@ -1019,6 +1019,40 @@ int mhe_chamfer_bwd_f32(const float *points, const float *scale, const float *ro
 int mhe_render_mesh_f32(const float *verts, const int *faces, const float *scale, const float *trans, const float *zscale, const float *target,
                         float *mask, float *depth, float *iou_sums, int R, int B, int V, int F, int S, int anti_aliasing, float far, void *stream);
 
+/* Silhouette distance of the projected hand mesh to the image's hand mask, and its reverse (csrc/silhouette.hip; the reference has no
+ * counterpart: its renderer is commented out, hand/ManoLayer.py:40 - the contract below is this project's own).  Normalised image coordinates
+ * as mhe_render_mesh_f32: pixel (row i, col j) of the S x S grid has its centre at c = ((2j+1)/S - 1, (2i+1)/S - 1) and is the square of
+ * half-width 1/S around it.  Rows are sample-major, r = n B + b.
+ * mhe_silhouette_pixels: mask [B,H,H], bytes (mask_is_float = 0: a byte other than 0 counts as 1; torch's bool / uint8) or f32 in [0,1]
+ *   (mask_is_float = 1) -> pixels [B,S*S] int32 and count [B] int32: the grid pixels whose k x k box (k = H / S) has a mean >= 0.5 (evaluated
+ *   as sum >= k^2 / 2 with the sum in f64), packed (i << 16) | j, in row-major order, count[b] of them; the rest of an image's list is -1.
+ *   1 <= S <= MHE_SILHOUETTE_MAX_SIZE, H a multiple of S, H <= MHE_SILHOUETTE_MAX_MASK.  One workgroup per image, a workgroup prefix sum fixes
+ *   the order.  Nothing on the host reads the count: the three entries can be captured into one HIP graph.
+ * mhe_silhouette_dist_f32: verts [R,V,3], logs_t [R,3] = (log s, tx, ty), pixels and count of the call above -> dist [R]; optional
+ *   parts [R,2] = (inside, cover), idx_v [R,V] int32, idx_m [R,S*S] int32.  With p_v = exp(log s) v_xy + t and M_b the kept pixels of image b,
+ *     inside[r] = (1/V) sum_v min_m sqrt(max(|p_vx - c_mx| - 1/S, 0)^2 + max(|p_vy - c_my| - 1/S, 0)^2)     (0 inside the mask)
+ *     cover[r]  = (1/|M_b|) sum_m min_v |c_m - p_v|,     dist[r] = inside[r] + cover[r]
+ *   idx_v[r][v] = the position in M_b's list of the pixel that attains vertex v's minimum, idx_m[r][m] = the vertex that attains the m-th
+ *   listed pixel's; ties go to the lowest index; idx_m is -1 past count[b].  An empty list: dist = inside = cover = 0, idx_v = -1.  A row with
+ *   a non-finite projected vertex: dist = inside = cover = NaN (whatever its image's list holds), its indices stay in range and are otherwise
+ *   unspecified; other rows are not disturbed.  1 <= V <= MHE_SILHOUETTE_MAX_VERTS, N B < 2^31.  count is clamped to 0 .. S^2 on the device.
+ *   The values do not depend on whether the indices are asked for.
+ * mhe_silhouette_dist_bwd_f32: the same inputs, idx_v and idx_m of the forward call, g_dist [R] -> g_verts [R,V,3], g_logs_t [R,3]:
+ *     g_p_v = g_dist[r] ( (1/V) grad d(p_v, c_idx_v[r][v]) + (1/|M_b|) sum_{m: idx_m[r][m] = v} u(p_v - c_m) ),   u(x) = x / |x|, u(0) = 0,
+ *     g_verts[r][v] = (e^(log s) g_p_vx, e^(log s) g_p_vy, 0),  g_logs_t[r] = (sum_v g_p_v . (e^(log s) v_xy), sum_v g_p_vx, sum_v g_p_vy);
+ *   grad d is the box distance's gradient, 0 where the distance is 0.  Zeros for a row of an image with an empty list and for a row with a
+ *   non-finite projected vertex.  An index outside its range contributes nothing and is never used as an address.  The mask gets no gradient.
+ * All: pair evaluations in f32 (squared distances compared, one square root per minimum), every sum in f64 in a fixed order, no atomics: two
+ *   calls give the same bits; no allocation, no workspace; outputs must not overlap inputs or each other (MHE_ERR_ARG before any launch). */
+#define MHE_SILHOUETTE_MAX_SIZE 64
+#define MHE_SILHOUETTE_MAX_MASK 4096
+#define MHE_SILHOUETTE_MAX_VERTS 778
+int mhe_silhouette_pixels(const void *mask, int mask_is_float, int *pixels, int *count, int B, int H, int S, void *stream);
+int mhe_silhouette_dist_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, float *dist, float *parts, int *idx_v,
+                            int *idx_m, int N, int B, int V, int S, void *stream);
+int mhe_silhouette_dist_bwd_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *idx_v, const int *idx_m,
+                                const float *g_dist, float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

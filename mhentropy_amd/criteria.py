@@ -3,7 +3,8 @@
 block runs in one HIP kernel (csrc/metrics.hip), the Procrustes alignment of the aligned
 evaluation in csrc/procrustes.hip.  chamfer_dist (hand/criteria.py:18-39) and the selection
 it was written for (chamfer_select) run on csrc/chamfer.hip; silhouette_iou scores the hypotheses' meshes against the image's hand mask
-on csrc/render.hip."""
+on csrc/render.hip; silhouette_dist, the differentiable distance of the projected mesh to that mask, and silhouette_select run on
+csrc/silhouette.hip."""
 import torch
 from torch import nn
 
@@ -95,6 +96,30 @@ def _rank(dist):
     return torch.sort(dist, dim=0, stable=True)
 
 
+def _select_shape(who, name, src, Q):
+    """the checks every selection shares -> (N, B) of src = output[name], an (N, B, ...) tensor"""
+    if src.dim() < 3:
+        raise ValueError(f"{who}: output[{name!r}] must be (N, B, ...), got {tuple(src.shape)}")
+    N, B = src.shape[:2]
+    if not isinstance(Q, int) or not 1 <= Q <= N:
+        raise ValueError(f"{who}: Q={Q!r} outside 1..N={N}")
+    return N, B
+
+
+def _cut(output, dist, Q, key):
+    """rank dist (N, B) and cut every (N, B, ...) tensor of `output` to its Q best hypotheses per image; 'faces' and 'image' pass through.
+    Added: `key` (Q, B), the distances, and `key`_index (Q, B) int64, the hypotheses kept."""
+    N, B = dist.shape
+    val, order = _rank(dist)
+    keep, cols = order[:Q], torch.arange(B, device=order.device)
+    out = {}
+    for k, v in output.items():
+        cut = isinstance(v, torch.Tensor) and k not in ("faces", "image") and v.dim() >= 2 and tuple(v.shape[:2]) == (N, B)
+        out[k] = v[keep, cols] if cut else v
+    out[key], out[key + "_index"] = val[:Q], keep
+    return out
+
+
 def chamfer_select(output, target, Q=1, points="xyz"):
     """Keep, per image, the Q hypotheses of a sample() output that lie closest to the image's object (chamfer_dist of the joints
     output['xyz'], or of the mesh output['verts'] with points='verts'), closest first, ties to the lower n.  Every (N, B, ...) tensor of
@@ -105,20 +130,87 @@ def chamfer_select(output, target, Q=1, points="xyz"):
     if points not in output:
         raise ValueError(f"chamfer_select: output has no {points!r}")
     src = output[points]
-    if src.dim() < 3:
-        raise ValueError(f"chamfer_select: output[{points!r}] must be (N, B, ...), got {tuple(src.shape)}")
-    N, B = src.shape[:2]
-    if not isinstance(Q, int) or not 1 <= Q <= N:
-        raise ValueError(f"chamfer_select: Q={Q!r} outside 1..N={N}")
+    N, B = _select_shape("chamfer_select", points, src, Q)
     with torch.no_grad():
-        val, order = _rank(chamfer_dist(src.detach().reshape(N, B, -1, 3), target))
-    keep, cols = order[:Q], torch.arange(B, device=order.device)
-    out = {}
-    for k, v in output.items():
-        cut = isinstance(v, torch.Tensor) and k not in ("faces", "image") and v.dim() >= 2 and tuple(v.shape[:2]) == (N, B)
-        out[k] = v[keep, cols] if cut else v
-    out["chamfer"], out["chamfer_index"] = val[:Q], keep
-    return out
+        dist = chamfer_dist(src.detach().reshape(N, B, -1, 3), target)
+    return _cut(output, dist, Q, "chamfer")
+
+
+def _silhouette_operands(verts, logs_t, hand_mask, size):
+    """the checks of silhouette_dist that need no device -> (verts [N,B,V,3], logs_t [N,B,3], hand_mask [B,H,H], size)"""
+    who = "silhouette_dist"
+    if not isinstance(verts, torch.Tensor) or verts.dim() not in (3, 4) or (verts.dim() == 4 and verts.shape[-1] != 3) or verts[0, 0].numel() % 3:
+        raise ValueError(f"{who}: verts must be (N, B, V*3) or (N, B, V, 3), got {tuple(getattr(verts, 'shape', ()))}")
+    N, B = verts.shape[:2]
+    V = verts[0, 0].numel() // 3
+    if not 1 <= V <= ops.SILHOUETTE_MAX_VERTS:
+        raise ValueError(f"{who}: V={V} vertices per hypothesis (1..{ops.SILHOUETTE_MAX_VERTS})")
+    if not isinstance(logs_t, torch.Tensor) or tuple(logs_t.shape) != (N, B, 3):
+        raise ValueError(f"{who}: logs_t must be (N, B, 3) = ({N}, {B}, 3), got {tuple(getattr(logs_t, 'shape', ()))}")
+    if not isinstance(hand_mask, torch.Tensor) or hand_mask.dim() != 3 or hand_mask.shape[0] != B or hand_mask.shape[1] != hand_mask.shape[2]:
+        raise ValueError(f"{who}: hand_mask must be (B, H, H) with B={B}, got {tuple(getattr(hand_mask, 'shape', ()))}")
+    if not isinstance(size, int) or not 1 <= size <= ops.SILHOUETTE_MAX_SIZE:
+        raise ValueError(f"{who}: size={size!r} (1..{ops.SILHOUETTE_MAX_SIZE})")
+    H = hand_mask.shape[1]
+    if H < size or H % size:
+        raise ValueError(f"{who}: hand_mask is {H} x {H}, not a multiple of size={size}")
+    if hand_mask.dtype not in (torch.bool, torch.uint8, torch.float32):
+        hand_mask = hand_mask.float()
+    return verts.reshape(N, B, V, 3).float().contiguous(), logs_t.float().contiguous(), hand_mask.contiguous(), size
+
+
+class _Silhouette(torch.autograd.Function):
+    """(dist, parts) of ops.silhouette_dist; the gradient of dist reaches verts and logs_t (parts is returned for reading only).  The argmin
+    buffers are asked for only when one of them requires grad."""
+    @staticmethod
+    def forward(ctx, verts, logs_t, pixels, count):
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dist, parts, idx_v, idx_m = ops.silhouette_dist(verts, logs_t, pixels, count, want_idx=True)
+            ctx.save_for_backward(verts, logs_t, pixels, count, idx_v, idx_m)
+        else:
+            dist, parts = ops.silhouette_dist(verts, logs_t, pixels, count)
+        ctx.mark_non_differentiable(parts)
+        return dist, parts
+
+    @staticmethod
+    def backward(ctx, g_dist, _g_parts):
+        g_verts, g_logs_t = ops.silhouette_dist_bwd(*ctx.saved_tensors, g_dist.contiguous())
+        return g_verts, g_logs_t, None, None
+
+
+def silhouette_dist(verts, logs_t, hand_mask, size=64, parts=False):
+    """Distance of every hypothesis' projected mesh to its image's hand mask: verts (N, B, V*3) or (N, B, V, 3) and logs_t (N, B, 3) =
+    (log s, tx, ty) of a sample() output, hand_mask (B, H, H) bool or float in [0, 1] (the input pipeline's target['hand_mask']) -> (N, B)
+    f32; with parts=True (dist, inside, cover).  In the normalised image coordinates of silhouette_iou (pixel (i, j) of the size x size grid is
+    the square of half-width 1/size around ((2j+1)/size - 1, (2i+1)/size - 1)): H must be a multiple of `size`, the mask is box-averaged
+    down to (size, size) and the pixels with a mean >= 0.5 are kept; with p_v = exp(log s) v_xy + t,
+        inside = mean over the vertices of the distance from p_v to the nearest kept pixel square (0 inside the mask: pulls the mesh in)
+        cover  = mean over the kept pixels of the distance from the pixel's centre to the nearest p_v (pulls the mesh over the whole mask)
+        dist   = inside + cover
+    Exact (no soft rasteriser) and deterministic; ties go to the lowest index.  An image with an empty mask gives 0 and a zero gradient,
+    a row with a non-finite projected vertex NaN and a zero gradient.  Differentiable with respect to verts and logs_t (the z column of the
+    vertices and the mask get none; inside and cover are returned detached).  Runs on csrc/silhouette.hip, nothing on the host reads the
+    pixel count: the call can be captured into a HIP graph.  HIP tensors only (MheError otherwise); ValueError for a bad rank or shape, H not
+    a multiple of size, V outside 1..778.  The training term (a get_loss keyword) is not built yet: it needs the reverse of the mesh."""
+    v, lt, mask, size = _silhouette_operands(verts, logs_t, hand_mask, size)
+    pixels, count = ops.silhouette_pixels(mask, size)
+    dist, pt = _Silhouette.apply(v, lt, pixels, count)
+    return (dist, pt[..., 0], pt[..., 1]) if parts else dist
+
+
+def silhouette_select(output, target, Q=1, size=64):
+    """chamfer_select with silhouette_dist: keep, per image, the Q hypotheses of a sample() output whose mesh (output['verts'] under
+    output['logs_t']) lies closest to target['hand_mask'], closest first, ties to the lower n.  Every (N, B, ...) tensor of `output` is cut
+    to (Q, B, ...); 'faces' and 'image' pass through.  Added: 'silhouette' (Q, B), the distances, and 'silhouette_index' (Q, B) int64."""
+    for k in ("verts", "logs_t"):
+        if k not in output:
+            raise ValueError(f"silhouette_select: output has no {k!r}")
+    if "hand_mask" not in target:
+        raise ValueError("silhouette_select: target has no 'hand_mask'")
+    N, B = _select_shape("silhouette_select", "verts", output["verts"], Q)
+    with torch.no_grad():
+        dist = silhouette_dist(output["verts"].detach(), output["logs_t"].detach(), target["hand_mask"], size=size)
+    return _cut(output, dist, Q, "silhouette")
 
 
 def silhouette_iou(verts, logs_t, faces, hand_mask, size=64):

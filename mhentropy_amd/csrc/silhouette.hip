@@ -1,0 +1,370 @@
+// Silhouette distance of the projected hand mesh to the image's hand mask, and its reverse (criteria.silhouette_dist, ops.silhouette_*).
+//   p_v = exp(log s) v_xy + t;  pixel (i, j) of the S x S grid: centre c = ((2j+1)/S - 1, (2i+1)/S - 1), the square of half-width 1/S around it
+//   inside = mean_v min_m box(p_v, c_m),  cover = mean_m min_v |c_m - p_v|,  dist = inside + cover,  m over the kept pixels M_b of the image
+// The contract is written at the declarations in include/mhe.h.  f32 pair evaluations, squared distances compared and one square root per
+// minimum, ties to the lowest index; every sum runs in a fixed order in f64 (a thread's own terms, the wave's butterfly, the four waves in
+// order) and nothing is atomic: two launches give the same bits.  The pixel count never leaves the device.
+#include "common.h"
+
+namespace mhe { namespace silhouette {
+
+constexpr int NT = 256, NW = NT / 64;                   // threads / waves of a workgroup
+constexpr int SMAX = MHE_SILHOUETTE_MAX_SIZE, PMAX = SMAX * SMAX;
+constexpr int VMAX = MHE_SILHOUETTE_MAX_VERTS;
+constexpr int KV = (VMAX + NT - 1) / NT;                // vertices of one thread (v = k NT + tid)
+constexpr int KM = 4, TM = NT * KM;                     // kept pixels of one thread; of one round of the cover direction
+constexpr int KPIX = PMAX / NT;                         // grid pixels of one thread of the pixel-list kernel
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ float2 centre(int packed, float fS) {
+    const int i = packed >> 16, j = packed & 0xffff;
+    return make_float2((float)(2 * j + 1) / fS - 1.f, (float)(2 * i + 1) / fS - 1.f);
+}
+
+__device__ __forceinline__ float box_sq(float px, float py, const float2 &c, float h) {
+    const float ax = fmaxf(fabsf(px - c.x) - h, 0.f), ay = fmaxf(fabsf(py - c.y) - h, 0.f);
+    return fmaf(ay, ay, ax * ax);
+}
+
+// Mask -> kept pixels of image b = blockIdx.x in row-major order.  A thread owns `per` consecutive grid pixels, box-sums each in f64 (bytes
+// count as 0 / 1) and keeps it when 2 sum >= k^2, i.e. mean >= 0.5; the workgroup's exclusive prefix sum of the threads' counts fixes where
+// a thread's pixels go.  The list's tail is -1.
+template <typename T>
+__global__ __launch_bounds__(NT) void pixels_kernel(const T *__restrict__ mask, int *__restrict__ pixels, int *__restrict__ count, int H, int S) {
+    __shared__ int wtot[NW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    const int P = S * S, per = (P + NT - 1) / NT, k = H / S;
+    const int p0 = min(P, tid * per), p1 = min(P, p0 + per);
+    const T *img = mask + (size_t)b * H * H;
+    const double half = 0.5 * (double)k * (double)k;
+    unsigned keep = 0;
+    for (int p = p0; p < p1; ++p) {
+        const int i = p / S, j = p - i * S;
+        double s = 0.0;
+        for (int y = 0; y < k; ++y) {
+            const T *row = img + (size_t)(i * k + y) * H + (size_t)j * k;
+            for (int x = 0; x < k; ++x) s += sizeof(T) == 1 ? (row[x] != (T)0 ? 1.0 : 0.0) : (double)row[x];
+        }
+        if (s >= half) keep |= 1u << (p - p0);
+    }
+    const int mine = __popc(keep);
+    int incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    int off = incl - mine, total = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        if (w < wave) off += wtot[w];
+        total += wtot[w];
+    }
+    int *out = pixels + (size_t)b * P;
+    for (int p = p0; p < p1; ++p)
+        if (keep >> (p - p0) & 1u) {
+            const int i = p / S;
+            out[off++] = (i << 16) | (p - i * S);
+        }
+    for (int q = total + tid; q < P; q += NT) out[q] = -1;
+    if (tid == 0) count[b] = total;
+}
+
+// min over the image's M kept pixels (LDS, every lane reads the same centre: a broadcast) for K vertices held in registers
+template <bool IDX, int K>
+__device__ __forceinline__ void scan_pixels(const float2 *pc, int M, float h, const float *px, const float *py, float *m1, int *i1) {
+#pragma unroll 4
+    for (int m = 0; m < M; ++m) {
+        const float2 c = pc[m];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float d = box_sq(px[k], py[k], c, h);
+            if (IDX) { if (d < m1[k]) { m1[k] = d; i1[k] = m; } }
+            else m1[k] = fminf(m1[k], d);
+        }
+    }
+}
+
+// min over the row's V projected vertices (LDS, broadcast) for K kept pixels held in registers
+template <bool IDX, int K>
+__device__ __forceinline__ void scan_verts(const float2 *pv, int V, const float *cx, const float *cy, float *m2, int *i2) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) { m2[k] = __builtin_inff(); i2[k] = 0; }
+#pragma unroll 4
+    for (int v = 0; v < V; ++v) {
+        const float2 p = pv[v];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const float dx = cx[k] - p.x, dy = cy[k] - p.y, d = fmaf(dy, dy, dx * dx);
+            if (IDX) { if (d < m2[k]) { m2[k] = d; i2[k] = v; } }
+            else m2[k] = fminf(m2[k], d);
+        }
+    }
+}
+
+// Forward, one workgroup per row r = n B + b.  The row's vertices are projected once (registers of their thread, and LDS for the cover
+// direction), the image's kept pixels are decoded once into LDS as centres; both directional minima are taken from LDS.  The count is
+// clamped to 0 .. S^2 before it bounds anything.  A non-finite projected vertex makes the row NaN (the flag, not the minima, carries it:
+// fminf would drop the NaN); an empty list makes it 0.
+template <bool IDX>
+__global__ __launch_bounds__(NT) void dist_kernel(const float *__restrict__ verts, const float *__restrict__ logs_t, const int *__restrict__ pixels,
+                                                  const int *__restrict__ count, float *__restrict__ dist, float *__restrict__ parts,
+                                                  int *__restrict__ idx_v, int *__restrict__ idx_m, int B, int V, int S) {
+    __shared__ float2 pc[PMAX];
+    __shared__ float2 pv[KV * NT];
+    __shared__ double red[2][NW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t r = blockIdx.x;
+    const int b = (int)(r % (size_t)B), P = S * S, M = min(max(count[b], 0), P);
+    const float fS = (float)S, h = 1.f / fS;
+    const float es = expf(logs_t[r * 3]), tx = logs_t[r * 3 + 1], ty = logs_t[r * 3 + 2];
+
+    float px[KV], py[KV], m1[KV];
+    int i1[KV];
+    int bad = 0;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+        const int v = k * NT + tid;
+        px[k] = py[k] = 0.f;
+        m1[k] = __builtin_inff();
+        i1[k] = 0;
+        if (v < V) {
+            const float *p = verts + (r * V + v) * 3;
+            px[k] = fmaf(es, p[0], tx); py[k] = fmaf(es, p[1], ty);
+            bad |= !(isfinite(px[k]) && isfinite(py[k]));
+            pv[v] = make_float2(px[k], py[k]);
+        }
+    }
+    for (int m = tid; m < M; m += NT) pc[m] = centre(pixels[(size_t)b * P + m], fS);
+    bad = __syncthreads_or(bad);
+
+    // mesh -> mask
+    switch ((V + NT - 1) / NT) {
+#define MHE_CASE(K) case K: scan_pixels<IDX, K>(pc, M, h, px, py, m1, i1); break;
+        MHE_CASE(1) MHE_CASE(2) MHE_CASE(3) MHE_CASE(4)
+#undef MHE_CASE
+    }
+    static_assert(KV == 4, "the switch above covers 1 .. KV vertices per thread");
+    double s_in = 0.0, s_co = 0.0;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+        const int v = k * NT + tid;
+        if (v < V) {
+            s_in += (double)sqrtf(m1[k]);
+            if (IDX && idx_v) idx_v[r * V + v] = M ? i1[k] : -1;
+        }
+    }
+    // mask -> mesh, rounds of TM kept pixels
+    for (int t0 = 0; t0 < M; t0 += TM) {
+        const int tm = min(TM, M - t0);
+        float cx[KM], cy[KM], m2[KM];
+        int i2[KM];
+#pragma unroll
+        for (int k = 0; k < KM; ++k) {
+            const int m = k * NT + tid;
+            const float2 c = m < tm ? pc[t0 + m] : make_float2(0.f, 0.f);
+            cx[k] = c.x; cy[k] = c.y;
+        }
+        switch ((tm + NT - 1) / NT) {
+#define MHE_CASE(K) case K: scan_verts<IDX, K>(pv, V, cx, cy, m2, i2); break;
+            MHE_CASE(1) MHE_CASE(2) MHE_CASE(3) MHE_CASE(4)
+#undef MHE_CASE
+        }
+        static_assert(KM == 4, "the switch above covers 1 .. KM pixels per thread");
+#pragma unroll
+        for (int k = 0; k < KM; ++k) {
+            const int m = k * NT + tid;
+            if (m < tm) {
+                s_co += (double)sqrtf(m2[k]);
+                if (IDX && idx_m) idx_m[r * P + t0 + m] = i2[k];
+            }
+        }
+    }
+    s_in = wave_sum(s_in); s_co = wave_sum(s_co);
+    if (lane == 0) { red[0][wave] = s_in; red[1][wave] = s_co; }
+    __syncthreads();
+    if (tid == 0) {
+        float I = 0.f, Cv = 0.f;
+        if (M) {
+            I = (float)((((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]) / (double)V);
+            Cv = (float)((((red[1][0] + red[1][1]) + red[1][2]) + red[1][3]) / (double)M);
+        }
+        float D = I + Cv;
+        if (bad) I = Cv = D = __builtin_nanf("");
+        dist[r] = D;
+        if (parts) { parts[r * 2] = I; parts[r * 2 + 1] = Cv; }
+    }
+    if (IDX && idx_m)
+        for (int m = M + tid; m < P; m += NT) idx_m[r * P + m] = -1;
+}
+
+// Reverse, one workgroup per row.  The thread that owns vertex v (tid = v mod NT, slot v / NT) walks the row's pixel -> vertex list from LDS
+// in ascending m and adds the unit vectors of the pixels that chose v to its own registers: a fixed order, nothing atomic.  An index outside
+// its range contributes nothing and is never used as an address.  u(0) = 0.  A row with a non-finite projected vertex, or of an image with
+// an empty list, gets zeros.
+__global__ __launch_bounds__(NT) void dist_bwd_kernel(const float *__restrict__ verts, const float *__restrict__ logs_t, const int *__restrict__ pixels,
+                                                      const int *__restrict__ count, const int *__restrict__ idx_v, const int *__restrict__ idx_m,
+                                                      const float *__restrict__ g_dist, float *__restrict__ g_verts, float *__restrict__ g_logs_t, int B,
+                                                      int V, int S) {
+    __shared__ int pk[PMAX];
+    __shared__ int ti[PMAX];
+    __shared__ double red[3][NW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t r = blockIdx.x;
+    const int b = (int)(r % (size_t)B), P = S * S, M = min(max(count[b], 0), P);
+    const float fS = (float)S, h = 1.f / fS;
+    const float es = expf(logs_t[r * 3]), tx = logs_t[r * 3 + 1], ty = logs_t[r * 3 + 2];
+
+    float vx[KV], vy[KV], px[KV], py[KV];
+    int bad = 0;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+        const int v = k * NT + tid;
+        vx[k] = vy[k] = px[k] = py[k] = 0.f;
+        if (v < V) {
+            const float *p = verts + (r * V + v) * 3;
+            vx[k] = p[0]; vy[k] = p[1];
+            px[k] = fmaf(es, vx[k], tx); py[k] = fmaf(es, vy[k], ty);
+            bad |= !(isfinite(px[k]) && isfinite(py[k]));
+        }
+    }
+    for (int m = tid; m < M; m += NT) { pk[m] = pixels[(size_t)b * P + m]; ti[m] = idx_m[r * P + m]; }
+    bad = __syncthreads_or(bad);
+    if (bad || M == 0) {
+#pragma unroll
+        for (int k = 0; k < KV; ++k) {
+            const int v = k * NT + tid;
+            if (v < V) { float *g = g_verts + (r * V + v) * 3; g[0] = 0.f; g[1] = 0.f; g[2] = 0.f; }
+        }
+        if (tid < 3) g_logs_t[r * 3 + tid] = 0.f;
+        return;
+    }
+
+    double gx[KV], gy[KV];
+#pragma unroll
+    for (int k = 0; k < KV; ++k) gx[k] = gy[k] = 0.0;
+    for (int m = 0; m < M; ++m) {
+        const int t = ti[m];
+        if ((t & (NT - 1)) == tid && (unsigned)t < (unsigned)V) {
+            const int slot = t / NT;
+            float qx = px[0], qy = py[0];
+#pragma unroll
+            for (int k = 1; k < KV; ++k) if (slot == k) { qx = px[k]; qy = py[k]; }
+            const float2 c = centre(pk[m], fS);
+            const float dx = qx - c.x, dy = qy - c.y, q = fmaf(dy, dy, dx * dx);
+            if (q > 0.f) {
+                const float inv = 1.f / sqrtf(q);
+#pragma unroll
+                for (int k = 0; k < KV; ++k) if (slot == k) { gx[k] += (double)(dx * inv); gy[k] += (double)(dy * inv); }
+            }
+        }
+    }
+
+    const double gd = (double)g_dist[r], wV = 1.0 / (double)V, wM = 1.0 / (double)M;
+    double s_l = 0.0, s_x = 0.0, s_y = 0.0;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+        const int v = k * NT + tid;
+        if (v < V) {
+            float ux = 0.f, uy = 0.f;
+            const int iv = idx_v[r * V + v];
+            if ((unsigned)iv < (unsigned)M) {
+                const float2 c = centre(pk[iv], fS);
+                const float dx = px[k] - c.x, dy = py[k] - c.y;
+                const float ax = fmaxf(fabsf(dx) - h, 0.f), ay = fmaxf(fabsf(dy) - h, 0.f), q = fmaf(ay, ay, ax * ax);
+                if (q > 0.f) {
+                    const float inv = 1.f / sqrtf(q);
+                    ux = copysignf(ax, dx) * inv; uy = copysignf(ay, dy) * inv;
+                }
+            }
+            const double gpx = gd * ((double)ux * wV + gx[k] * wM), gpy = gd * ((double)uy * wV + gy[k] * wM);
+            float *g = g_verts + (r * V + v) * 3;
+            g[0] = (float)((double)es * gpx); g[1] = (float)((double)es * gpy); g[2] = 0.f;
+            s_l += gpx * (double)(es * vx[k]) + gpy * (double)(es * vy[k]);
+            s_x += gpx; s_y += gpy;
+        }
+    }
+    s_l = wave_sum(s_l); s_x = wave_sum(s_x); s_y = wave_sum(s_y);
+    if (lane == 0) { red[0][wave] = s_l; red[1][wave] = s_x; red[2][wave] = s_y; }
+    __syncthreads();
+    if (tid < 3) g_logs_t[r * 3 + tid] = (float)(((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3]);
+}
+
+}}  // namespace mhe::silhouette
+
+using namespace mhe;
+
+// the shared argument checks of the forward and the reverse; R = N B rows
+static int silhouette_args(const char *who, const void *verts, const void *logs_t, const void *pixels, const void *count, int N, int B, int V, int S) {
+    MHE_REQUIRE(verts && logs_t && pixels && count, "%s: null pointer", who);
+    MHE_REQUIRE(N > 0 && B > 0, "%s: N=%d B=%d", who, N, B);
+    MHE_REQUIRE(V >= 1 && V <= silhouette::VMAX, "%s: V=%d (V in 1..%d)", who, V, silhouette::VMAX);
+    MHE_REQUIRE(S >= 1 && S <= silhouette::SMAX, "%s: S=%d (S in 1..%d)", who, S, silhouette::SMAX);
+    MHE_REQUIRE((long)N * B <= 0x7fffffffL, "%s: N*B=%ld rows (at most 2^31 - 1)", who, (long)N * B);
+    return MHE_OK;
+}
+
+extern "C" int mhe_silhouette_pixels(const void *mask, int mask_is_float, int *pixels, int *count, int B, int H, int S, void *stream) {
+    MHE_REQUIRE(mask && pixels && count, "mhe_silhouette_pixels: null pointer");
+    MHE_REQUIRE(mask_is_float == 0 || mask_is_float == 1, "mhe_silhouette_pixels: mask_is_float=%d (0: bytes, 1: f32)", mask_is_float);
+    MHE_REQUIRE(B > 0, "mhe_silhouette_pixels: B=%d", B);
+    MHE_REQUIRE(S >= 1 && S <= silhouette::SMAX, "mhe_silhouette_pixels: S=%d (S in 1..%d)", S, silhouette::SMAX);
+    MHE_REQUIRE(H >= S && H % S == 0 && H <= MHE_SILHOUETTE_MAX_MASK, "mhe_silhouette_pixels: H=%d (a multiple of S=%d, at most %d)", H, S,
+                MHE_SILHOUETTE_MAX_MASK);
+    const size_t nm = (size_t)B * H * H * (mask_is_float ? 4 : 1), np = (size_t)B * S * S * 4, nc = (size_t)B * 4;
+    MHE_REQUIRE(disjoint(pixels, np, mask, nm) && disjoint(count, nc, mask, nm) && disjoint(pixels, np, count, nc),
+                "mhe_silhouette_pixels: pixels, count and mask overlap");
+    static_assert(silhouette::KPIX <= 32, "a thread's kept pixels are one 32-bit word");
+    if (mask_is_float)
+        hipLaunchKernelGGL(silhouette::pixels_kernel<float>, dim3((unsigned)B), dim3(silhouette::NT), 0, (hipStream_t)stream, (const float *)mask, pixels,
+                           count, H, S);
+    else
+        hipLaunchKernelGGL(silhouette::pixels_kernel<unsigned char>, dim3((unsigned)B), dim3(silhouette::NT), 0, (hipStream_t)stream,
+                           (const unsigned char *)mask, pixels, count, H, S);
+    return check_launch("silhouette::pixels_kernel");
+}
+
+extern "C" int mhe_silhouette_dist_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, float *dist, float *parts, int *idx_v,
+                                       int *idx_m, int N, int B, int V, int S, void *stream) {
+    if (int st = silhouette_args("mhe_silhouette_dist_f32", verts, logs_t, pixels, count, N, B, V, S)) return st;
+    MHE_REQUIRE(dist, "mhe_silhouette_dist_f32: null pointer (dist)");
+    const size_t R = (size_t)N * B, P = (size_t)S * S;
+    struct { const void *p; size_t n; } in[4] = {{verts, R * V * 12}, {logs_t, R * 12}, {pixels, (size_t)B * P * 4}, {count, (size_t)B * 4}},
+                                        out[4] = {{dist, R * 4}, {parts, R * 8}, {idx_v, R * V * 4}, {idx_m, R * P * 4}};
+    for (int o = 0; o < 4; ++o) {
+        for (int i = 0; i < 4; ++i)
+            MHE_REQUIRE(disjoint(out[o].p, out[o].n, in[i].p, in[i].n), "mhe_silhouette_dist_f32: output %d overlaps input %d", o, i);
+        for (int q = 0; q < o; ++q)
+            MHE_REQUIRE(disjoint(out[o].p, out[o].n, out[q].p, out[q].n), "mhe_silhouette_dist_f32: outputs %d and %d overlap", q, o);
+    }
+    if (idx_v || idx_m)
+        hipLaunchKernelGGL(silhouette::dist_kernel<true>, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, dist,
+                           parts, idx_v, idx_m, B, V, S);
+    else
+        hipLaunchKernelGGL(silhouette::dist_kernel<false>, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, dist,
+                           parts, idx_v, idx_m, B, V, S);
+    return check_launch("silhouette::dist_kernel");
+}
+
+extern "C" int mhe_silhouette_dist_bwd_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *idx_v, const int *idx_m,
+                                           const float *g_dist, float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream) {
+    if (int st = silhouette_args("mhe_silhouette_dist_bwd_f32", verts, logs_t, pixels, count, N, B, V, S)) return st;
+    MHE_REQUIRE(idx_v && idx_m && g_dist && g_verts && g_logs_t, "mhe_silhouette_dist_bwd_f32: null pointer (idx_v, idx_m, g_dist, g_verts, g_logs_t)");
+    const size_t R = (size_t)N * B, P = (size_t)S * S;
+    struct { const void *p; size_t n; } in[7] = {{verts, R * V * 12}, {logs_t, R * 12}, {pixels, (size_t)B * P * 4}, {count, (size_t)B * 4},
+                                                 {idx_v, R * V * 4}, {idx_m, R * P * 4}, {g_dist, R * 4}};
+    for (int i = 0; i < 7; ++i)
+        MHE_REQUIRE(disjoint(g_verts, R * V * 12, in[i].p, in[i].n) && disjoint(g_logs_t, R * 12, in[i].p, in[i].n),
+                    "mhe_silhouette_dist_bwd_f32: an output overlaps input %d", i);
+    MHE_REQUIRE(disjoint(g_verts, R * V * 12, g_logs_t, R * 12), "mhe_silhouette_dist_bwd_f32: g_verts and g_logs_t overlap");
+    hipLaunchKernelGGL(silhouette::dist_bwd_kernel, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, idx_v,
+                       idx_m, g_dist, g_verts, g_logs_t, B, V, S);
+    return check_launch("silhouette::dist_bwd_kernel");
+}

@@ -636,6 +636,69 @@ def chamfer_bwd(points, scale, root, obj, count, idx_p, idx_o, g_dist, unit=1000
     return g_points
 
 
+SILHOUETTE_MAX_SIZE, SILHOUETTE_MAX_VERTS = 64, 778          # MHE_SILHOUETTE_MAX_SIZE / _MAX_VERTS of include/mhe.h
+
+
+def silhouette_pixels(hand_mask, size=64):
+    """kept pixels of every image's hand mask (include/mhe.h, mhe_silhouette_pixels): hand_mask [B,H,H] bool / uint8 (non-zero counts as 1) or
+    float32 in [0,1], H a multiple of size -> pixels [B,size*size] int32, packed (i << 16) | j in row-major order and -1 past the count, and
+    count [B] int32, which stays on the device"""
+    if not isinstance(hand_mask, torch.Tensor) or hand_mask.dim() != 3 or hand_mask.shape[1] != hand_mask.shape[2]:
+        raise _lib.MheError("silhouette_pixels.hand_mask: expected a [B,H,H] tensor")
+    B, H, S = hand_mask.shape[0], hand_mask.shape[1], int(size)
+    if hand_mask.dtype not in (torch.bool, torch.uint8, torch.float32):
+        raise _lib.MheError(f"silhouette_pixels.hand_mask: expected bool, uint8 or float32, got {hand_mask.dtype}")
+    _chk(hand_mask, hand_mask.dtype, "silhouette_pixels.hand_mask")
+    if not 1 <= S <= SILHOUETTE_MAX_SIZE or B < 1 or H < S or H % S:
+        raise ValueError(f"silhouette_pixels: B={B} H={H} size={S} (B >= 1, size in 1..{SILHOUETTE_MAX_SIZE}, H a multiple of size)")
+    pixels = torch.empty(B, S * S, device=hand_mask.device, dtype=torch.int32)
+    count = torch.empty(B, device=hand_mask.device, dtype=torch.int32)
+    launch("mhe_silhouette_pixels", hand_mask, int(hand_mask.dtype == torch.float32), pixels, count, B, H, S)
+    return pixels, count
+
+
+def _silhouette_operands(verts, logs_t, pixels, count, who):
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 4 or verts.shape[-1] != 3:
+        raise _lib.MheError(f"{who}.verts: expected an [N,B,V,3] tensor")
+    if not isinstance(pixels, torch.Tensor) or pixels.dim() != 2:
+        raise _lib.MheError(f"{who}.pixels: expected a [B,size*size] tensor")
+    N, B, V = verts.shape[:3]
+    P = pixels.shape[1]
+    S = int(round(P ** 0.5))
+    if S * S != P or not 1 <= S <= SILHOUETTE_MAX_SIZE:
+        raise ValueError(f"{who}: pixels has {P} columns, not size*size with size in 1..{SILHOUETTE_MAX_SIZE}")
+    if not 1 <= V <= SILHOUETTE_MAX_VERTS:
+        raise ValueError(f"{who}: V={V} vertices (1..{SILHOUETTE_MAX_VERTS})")
+    _chk(verts, torch.float32, f"{who}.verts"); _chk(logs_t, torch.float32, f"{who}.logs_t", (N, B, 3))
+    _chk(pixels, torch.int32, f"{who}.pixels", (B, P)); _chk(count, torch.int32, f"{who}.count", (B,))
+    return N, B, V, S
+
+
+def silhouette_dist(verts, logs_t, pixels, count, want_idx=False):
+    """silhouette distance of every hypothesis' projected vertices to its image's kept pixels (include/mhe.h, mhe_silhouette_dist_f32): verts
+    [N,B,V,3], logs_t [N,B,3] = (log s, tx, ty), pixels / count of silhouette_pixels -> dist [N,B], parts [N,B,2] = (inside, cover);
+    want_idx: also the argmins idx_v [N,B,V] and idx_m [N,B,size*size] (int32) that silhouette_dist_bwd reads"""
+    N, B, V, S = _silhouette_operands(verts, logs_t, pixels, count, "silhouette_dist")
+    dev = verts.device
+    dist = torch.empty(N, B, device=dev, dtype=torch.float32)
+    parts = torch.empty(N, B, 2, device=dev, dtype=torch.float32)
+    idx_v = torch.empty(N, B, V, device=dev, dtype=torch.int32) if want_idx else None
+    idx_m = torch.empty(N, B, S * S, device=dev, dtype=torch.int32) if want_idx else None
+    launch("mhe_silhouette_dist_f32", verts, logs_t, pixels, count, dist, parts, idx_v, idx_m, N, B, V, S)
+    return (dist, parts, idx_v, idx_m) if want_idx else (dist, parts)
+
+
+def silhouette_dist_bwd(verts, logs_t, pixels, count, idx_v, idx_m, g_dist):
+    """reverse of silhouette_dist's dist (mhe_silhouette_dist_bwd_f32): idx_v / idx_m of the forward call, g_dist [N,B] -> g_verts [N,B,V,3]
+    (its z column is zero), g_logs_t [N,B,3]"""
+    N, B, V, S = _silhouette_operands(verts, logs_t, pixels, count, "silhouette_dist_bwd")
+    _chk(idx_v, torch.int32, "silhouette_dist_bwd.idx_v", (N, B, V)); _chk(idx_m, torch.int32, "silhouette_dist_bwd.idx_m", (N, B, S * S))
+    _chk(g_dist, torch.float32, "silhouette_dist_bwd.g_dist", (N, B))
+    g_verts, g_logs_t = torch.empty_like(verts), torch.empty_like(logs_t)
+    launch("mhe_silhouette_dist_bwd_f32", verts, logs_t, pixels, count, idx_v, idx_m, g_dist, g_verts, g_logs_t, N, B, V, S)
+    return g_verts, g_logs_t
+
+
 RENDER_OUTPUTS = ("mask", "depth", "iou_sums")
 
 
