@@ -254,6 +254,26 @@ int mhe_mano_decode_f32(const float *th45, const float *det, const float *crop_u
  * verts [R,778,3] -> joints [R,21,3] (the wrapper's 'joints' output, unused by MHEnt). */
 int mhe_mano_regress_joints_f32(const float *verts, const float *tables, float *joints, int R, void *stream);
 
+/* Reverse of mhe_mano_verts_f32 (and of the mesh and joints_mm outputs of mhe_mano_decode_f32): g_verts [R,778,3] = dL/dverts of the mode the
+ * forward ran in (mm_mode != 0: ManoLayer's mesh in mm; 0: normalised) -> g_z [R,61] in z's column order (th3, th45, beta, log s, t).  The
+ * mesh does not depend on the camera: columns 58..60 are written as 0.  g_joints_mm [R,63] or NULL: dL/djoints_mm (mm, centred, RHD order),
+ * added to the adjoints of the posed joints.  z, tables as for mhe_mano_verts_f32.
+ *   Launches: the forward's pose pass (z -> workspace rows), the reverse's coefficient-fastest tables (made from the blob's vertex section on
+ *   every call: no hidden state), the skinning reverse (csrc/mano_skin_bwd.hip: exact-f32 matrix-core reductions over the vertices, the row's
+ *   output scale and the adjoints of centre / root / bone inside the same pass), the pose chain's reverse (csrc/mano_bwd.hip: one wavefront per
+ *   hypothesis, the chain mhe_mano_joints_bwd_f32 walks).  No atomics, every sum in a fixed order: two calls give the same bits.  g_verts is
+ *   read for rows < R and vertices < 778 only.
+ *   No allocation and no host synchronisation: the call can be captured into a HIP graph.  workspace: mhe_mano_verts_bwd_workspace_floats(R)
+ *   floats, caller-owned, overwritten.  MHE_ERR_ARG before any launch for a null z / tables / g_verts / g_z / workspace, R < 1, or when g_z or
+ *   the workspace overlaps an input or each other. */
+size_t mhe_mano_verts_bwd_workspace_floats(int R);
+int mhe_mano_verts_bwd_f32(const float *z, const float *tables, const float *g_verts, const float *g_joints_mm, float *g_z,
+                           float *workspace, int R, int mm_mode, void *stream);
+/* Transpose of mhe_mano_regress_joints_f32 (J_regressor rows, the five tip vertices, the RHD reorder): g_joints [R,21,3] -> g_verts
+ * [R,778,3], written, or added to when accumulate != 0.  One thread per vertex, fixed-order sums, no atomics.  No allocation, no host
+ * synchronisation.  MHE_ERR_ARG before the launch for a null pointer, R < 1 or g_verts overlapping an input. */
+int mhe_mano_regress_joints_bwd_f32(const float *g_joints, const float *tables, float *g_verts, int R, int accumulate, void *stream);
+
 /* mean over the N hypotheses of each image and the ELBO
  * (hand/network.py:793,801-808): rows [N*B] -> [B].
  *   q_log_p[b] = mean_n log_p_rows[n*B+b];  h[b] = mean_n -log_q_rows[n*B+b];

@@ -49,6 +49,44 @@ class _ManoBuffers(nn.Module):
         self.register_buffer("th_selected_comps", f(np.asarray(t["hands_components"])[:ncomps]))
 
 
+class _ManoMesh(torch.autograd.Function):
+    """the hand mesh as a differentiable function of z [R,61] = [th3, th45, beta, log s, t] (the camera columns do not reach it).
+    wrapper=False: ops.mano_verts(z, blob, mm) -> verts.  wrapper=True: what ManoLayer.forward launches -> (mesh, joints, mano_joints).
+    backward: ops.mano_verts_bwd (csrc/mano_skin_bwd.hip, csrc/mano_bwd.hip); `joints` reaches the mesh through ops.mano_regress_joints_bwd."""
+
+    @staticmethod
+    def forward(ctx, z, blob, mm, wrapper):
+        z = z.detach().contiguous()
+        ctx.save_for_backward(z, blob)
+        ctx.mm, ctx.wrapper = True if wrapper else bool(mm), wrapper
+        if not wrapper:
+            return ops.mano_verts(z, blob, mm=mm)
+        return _wrapper_outputs(z[:, :48], z[:, 48:58].contiguous(), blob)
+
+    @staticmethod
+    def backward(ctx, g_mesh, g_joints=None, g_mano_joints=None):
+        z, blob = ctx.saved_tensors
+        R = z.shape[0]
+        g_mesh = torch.zeros(R, 778, 3, device=z.device) if g_mesh is None else g_mesh.contiguous().float()
+        g_jmm = None
+        if ctx.wrapper:
+            if g_joints is not None:
+                g_mesh = ops.mano_regress_joints_bwd(g_joints.contiguous().float(), blob, out=g_mesh.clone())
+            if g_mano_joints is not None:
+                g_jmm = g_mano_joints.contiguous().float().view(R, 63)
+        return ops.mano_verts_bwd(z, blob, g_mesh, mm=ctx.mm, g_joints_mm=g_jmm), None, None, None
+
+
+def _wrapper_outputs(theta, beta, blob):
+    """(mesh, joints, mano_joints) of reference hand/ManoLayer.py:45-60 for contiguous theta (R,48) and beta (R,10)"""
+    R = beta.shape[0]
+    det = torch.zeros(R, 16, device=beta.device, dtype=torch.float32)
+    det[:, :3], det[:, 3:13] = theta[:, :3], beta
+    o = ops.mano_joints(theta[:, 3:].contiguous(), det, blob, want=("joints_mm", "mesh_mm"))
+    mesh = o["mesh_mm"]
+    return mesh, ops.mano_regress_joints(mesh, blob), o["joints_mm"].view(R, 21, 3)
+
+
 class ManoLayer(nn.Module):
     def __init__(self, MANO_dir="./mano/", flat_hand_mean=True, ncomps=45, use_pca=False, n_latent=None,
                  skeidx="FreiHand", output_size=256, mask_sz=256, tables=None):
@@ -88,18 +126,23 @@ class ManoLayer(nn.Module):
         return self._blob[1]
 
     def forward(self, z=None, beta=None, theta=None):
-        """reference hand/ManoLayer.py:45-60 -> {'beta','theta','mesh','joints','mano_joints'}"""
+        """reference hand/ManoLayer.py:45-60 -> {'beta','theta','mesh','joints','mano_joints'}.  When beta or theta requires grad, mesh, joints
+        and mano_joints carry it (_ManoMesh); otherwise the same launches run outside autograd."""
         if beta is None or theta is None:
             raise NotImplementedError("latent->MANO regressors are out of scope; pass beta= and theta=")
         beta, theta = beta.reshape(-1, 10).contiguous(), theta.reshape(-1, 48).contiguous()
-        R = beta.shape[0]
-        det = torch.zeros(R, 16, device=beta.device, dtype=torch.float32)
-        det[:, :3], det[:, 3:13] = theta[:, :3], beta
         blob = self.table_blob()
-        o = ops.mano_joints(theta[:, 3:].contiguous(), det, blob, want=("joints_mm", "mesh_mm"))
-        mesh = o["mesh_mm"]
-        return {"beta": beta, "theta": theta, "mesh": mesh, "joints": ops.mano_regress_joints(mesh, blob),
-                "mano_joints": o["joints_mm"].view(R, 21, 3)}
+        if torch.is_grad_enabled() and (beta.requires_grad or theta.requires_grad):
+            z = torch.cat([theta, beta, theta.new_zeros(beta.shape[0], 3)], 1)
+            mesh, joints, mano_joints = _ManoMesh.apply(z, blob, True, True)
+        else:
+            mesh, joints, mano_joints = _wrapper_outputs(theta, beta, blob)
+        return {"beta": beta, "theta": theta, "mesh": mesh, "joints": joints, "mano_joints": mano_joints}
+
+    def verts(self, z, mm=False):
+        """the full mesh (R,778,3) of z (R,61) as ops.mano_verts gives it - normalised like xyz, or ManoLayer's mesh in mm with mm=True -
+        differentiable with respect to z (the camera columns 58..60 take a zero gradient)"""
+        return _ManoMesh.apply(z, self.table_blob(), mm, False)
 
     @staticmethod
     def batch_orth_proj(joint, scale_camera, trans_camera, image_size: int = 256, inv_norm=True):

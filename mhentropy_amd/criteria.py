@@ -191,7 +191,8 @@ def silhouette_dist(verts, logs_t, hand_mask, size=64, parts=False):
     a row with a non-finite projected vertex NaN and a zero gradient.  Differentiable with respect to verts and logs_t (the z column of the
     vertices and the mask get none; inside and cover are returned detached).  Runs on csrc/silhouette.hip, nothing on the host reads the
     pixel count: the call can be captured into a HIP graph.  HIP tensors only (MheError otherwise); ValueError for a bad rank or shape, H not
-    a multiple of size, V outside 1..778.  The training term (a get_loss keyword) is not built yet: it needs the reverse of the mesh."""
+    a multiple of size, V outside 1..778.  The reverse of the mesh exists (ManoLayer.verts carries the gradient on to z: ops.mano_verts_bwd); the training term
+    (a get_loss keyword) is not built yet."""
     v, lt, mask, size = _silhouette_operands(verts, logs_t, hand_mask, size)
     pixels, count = ops.silhouette_pixels(mask, size)
     dist, pt = _Silhouette.apply(v, lt, pixels, count)

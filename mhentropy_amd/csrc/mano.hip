@@ -541,8 +541,7 @@ __global__ __launch_bounds__(256) void mano_skin_kernel(const float *__restrict_
 // ManoLayer.xyz_from_vertice (hand/ManoLayer.py:141-148,108-139): 16 joints regressed
 // from the mesh + 5 tip vertices, FreiHand order, then the RHD reorder (:54-56).
 // One workgroup per hypothesis; wave w handles joints w, w+4, ...
-__device__ constexpr int kWrapJointMap[16] = {0, 5, 6, 7, 9, 10, 11, 17, 18, 19, 13, 14, 15, 1, 2, 3};   // mano id -> FreiHand id
-__device__ constexpr int kWrapTipVert[5] = {744, 320, 443, 555, 672};                                    // FreiHand ids 4,8,12,16,20
+// (kWrapJointMap, kWrapTipVert: mano_joint_pass.h, shared with the transpose in mano_bwd.hip)
 __global__ __launch_bounds__(256) void regress_joints_kernel(const float *__restrict__ verts, const float *__restrict__ tables,
                                                              float *__restrict__ joints, int R) {
     __shared__ float kp[21 * 3];
@@ -687,16 +686,21 @@ extern "C" int mhe_mano_joints_chamfer_f32(const float *th45, const float *det, 
 
 extern "C" size_t mhe_mano_verts_workspace_floats(int R) { return R > 0 ? mhe_mano_skin_split_floats() + (size_t)R * mano::WS_STRIDE : 0; }
 
+// z [R,61] -> the workspace rows the skinning kernels and the skinning reverse (mano_skin_bwd.hip) read
+int mhe_mano_pose_rows(const float *z, const float *tables, float *rows, int R, hipStream_t stream) {
+    const size_t lds = (mano::JOINT_FLOATS + 4 * mano::SCRATCH) * sizeof(float);
+    const int pb = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
+    hipLaunchKernelGGL(mano::mano_pose_kernel, dim3(pb), dim3(256), lds, stream, z, tables, rows, R);
+    return check_launch("mano_pose_kernel");
+}
+
 extern "C" int mhe_mano_verts_f32(const float *z, const float *tables, float *verts, float *workspace, int R, int mm_mode,
                                   void *stream) {
     MHE_REQUIRE(z && tables && verts && workspace, "mhe_mano_verts_f32: null pointer");
     MHE_REQUIRE(R > 0, "mhe_mano_verts_f32: R=%d", R);
     constexpr int HB = 16;
-    const size_t lds = (mano::JOINT_FLOATS + 4 * mano::SCRATCH) * sizeof(float);
-    const int pb = (R + 3) / 4 < 2048 ? (R + 3) / 4 : 2048;
     float *rows = workspace + mhe_mano_skin_split_floats();
-    hipLaunchKernelGGL(mano::mano_pose_kernel, dim3(pb), dim3(256), lds, (hipStream_t)stream, z, tables, rows, R);
-    if (int rc = check_launch("mano_pose_kernel")) return rc;
+    if (int rc = mhe_mano_pose_rows(z, tables, rows, R, (hipStream_t)stream)) return rc;
     // 1 (default): both products on the matrix cores from bf16 pieces (mano_skin.hip); 0: the round-1 kernel, one thread per vertex (A/B runs)
     static const int mfma = getenv("MHE_MANO_SKIN_MFMA") ? atoi(getenv("MHE_MANO_SKIN_MFMA")) : 1;
     if (mfma) return mhe_mano_skin_mfma(rows, tables, workspace, verts, R, mm_mode, (hipStream_t)stream);

@@ -12,7 +12,10 @@ namespace mhe { namespace mano {
 // pre[ JOINT_REORDER[ FREIHAND2RHD[k] ] ]   (manolayer.py:260, utils.py:15, ManoLayer.py:54-56)
 static __device__ constexpr int kJointReorder[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
 static __device__ constexpr int kFreihand2Rhd[21] = {0, 4, 3, 2, 1, 8, 7, 6, 5, 12, 11, 10, 9, 16, 15, 14, 13, 20, 19, 18, 17};
-constexpr int kCenterPre = 4;     // kJointReorder[center_idx = 9]   (manolayer.py:262-266)
+// the wrapper's re-regression (regress_joints_kernel and its transpose; hand/ManoLayer.py:108-148)
+static __device__ constexpr int kWrapJointMap[16] = {0, 5, 6, 7, 9, 10, 11, 17, 18, 19, 13, 14, 15, 1, 2, 3};   // mano id -> FreiHand id
+static __device__ constexpr int kWrapTipVert[5] = {744, 320, 443, 555, 672};                                    // FreiHand ids 4,8,12,16,20
+constexpr int kCenterPre = 4;    // kJointReorder[center_idx = 9]   (manolayer.py:262-266)
 constexpr int kRootIdx = 12;      // hand/network.py:477
 constexpr int kNormIdx = 11;      // hand/network.py:478
 // likelihoods a loss-pass kernel evaluates (template argument; the `mods` bit set of mhe_mano_joints_mods_f32)

@@ -527,6 +527,33 @@ def mano_regress_joints(verts, tables):
     return j
 
 
+def mano_verts_bwd(z, tables, g_verts, mm=False, g_joints_mm=None):
+    """reverse of mano_verts (and of mano_joints' mesh_mm / joints_mm with mm=True): g_verts [R,778,3] = dL/dverts of the same mode,
+    g_joints_mm [R,63] | None = dL/djoints_mm -> g_z [R,61] in z's column order; the camera columns 58..60 are 0 (mhe_mano_verts_bwd_f32)"""
+    R = z.shape[0]
+    _chk(z, torch.float32, "mano_verts_bwd.z", (R, 61))
+    _chk(tables, torch.float32, "mano_verts_bwd.tables", (_lib.lib().mhe_mano_table_floats(),))
+    _chk(g_verts, torch.float32, "mano_verts_bwd.g_verts", (R, 778, 3))
+    if g_joints_mm is not None:
+        _chk(g_joints_mm, torch.float32, "mano_verts_bwd.g_joints_mm", (R, 63))
+    g_z = torch.empty(R, 61, device=z.device, dtype=torch.float32)
+    ws = torch.empty(_lib.lib().mhe_mano_verts_bwd_workspace_floats(R), device=z.device, dtype=torch.float32)
+    launch("mhe_mano_verts_bwd_f32", z, tables, g_verts, g_joints_mm, g_z, ws, R, int(mm))
+    return g_z
+
+
+def mano_regress_joints_bwd(g_joints, tables, out=None):
+    """transpose of mano_regress_joints: g_joints [R,21,3] -> g_verts [R,778,3]; added to `out` when given (mhe_mano_regress_joints_bwd_f32)"""
+    R = g_joints.shape[0]
+    _chk(g_joints, torch.float32, "regress_bwd.g_joints", (R, 21, 3))
+    _chk(tables, torch.float32, "regress_bwd.tables", (_lib.lib().mhe_mano_table_floats(),))
+    if out is not None:
+        _chk(out, torch.float32, "regress_bwd.out", (R, 778, 3))
+    g_verts = torch.empty(R, 778, 3, device=g_joints.device, dtype=torch.float32) if out is None else out
+    launch("mhe_mano_regress_joints_bwd_f32", g_joints, tables, g_verts, R, int(out is not None))
+    return g_verts
+
+
 def elbo_reduce(log_p_rows, log_q_rows, N, B):
     dev = log_p_rows.device
     _chk(log_p_rows, torch.float32, "elbo.log_p_rows", (N * B,))
