@@ -69,7 +69,8 @@ const char *mhe_last_error(void);
 int mhe_linear_f32(const float *X, const float *W, const float *bias, float *Y,
                    int M, int N, int K, int act, void *stream);
 /* the M <= 256, K % 64 == 0 specialisation mhe_linear_f32 dispatches to (one workgroup per 16 output
- * columns, K split over its 4 waves): the shapes of the per-image heads. */
+ * columns, K split over its 4 waves): the shapes of the per-image heads.  M <= 64, <= 128 and <= 256 take kernels holding 4, 8 and 16 row
+ * tiles per wave; M > 64 with fewer than 512 column groups (N < 8177) runs the 4-tile kernel over 64-row slices instead. */
 int mhe_linear_skinny_f32(const float *X, const float *W, const float *bias, float *Y,
                           int M, int N, int K, int act, void *stream);
 /* the same, also writing the result as bf16 (Y_bf16 [M,N]): BasicEnc.l1's feature (hand/network.py:121) feeds the flow's conditioning
@@ -819,7 +820,10 @@ int mhe_glow_glu_residual_f32(float *H, const void *T, int t_dtype, const float 
 int mhe_glow_coupling_f32(const float *u, const float *params, float *y, float *logdet, long R, int dim, int first,
                           int n_transform, int inverse, void *stream);
 int mhe_pad64_f32(const float *x, float *xp, long R, int dim, void *stream);
-/* reverse stages of the sampling direction (train step of the Glow branch; formulas in csrc/glow.hip) */
+/* reverse stages of the sampling direction (train step of the Glow branch; formulas in csrc/glow.hip).
+ * mhe_glow_coupling_inv_bwd_f32: dim <= 64, every row of v, params, g_y, g_v, g_params at pitch 64; all 64 columns of g_v and g_params are
+ * WRITTEN (g_v zero from dim on, g_params zero from 2 n_transform on); g_log_p [B] is per image, row r reads g_log_p[r % B] * q_weight
+ * (NULL: none). */
 int mhe_glow_coupling_inv_bwd_f32(const float *v, const float *params, const float *g_y, const float *g_log_p, float q_weight,
                                   float *g_v, float *g_params, long R, int B, int dim, int first, int n_transform, void *stream);
 int mhe_glow_glu_bwd_f32(const float *g_h, const void *t3, const float *gate, long gate_stride, void *g_t3, float *g_gate_rows,
@@ -829,7 +833,8 @@ int mhe_relu_bwd_add_f32(float *acc, const void *g, const float *h, long n, int 
 int mhe_glow_finish_f32(const float *z_padded, const float *v_padded, const float *logdet, float *v_out, float *log_prob,
                         long R, int dim, float sign, float logdet_const, void *stream);
 /* ... with the log-determinant constant read from the device: log_prob = base(z) + sign * logdet[r] + sum(const_parts[0 .. n_parts)) - a captured
- * HIP graph then follows the parameters from step to step */
+ * HIP graph then follows the parameters from step to step.  (Evaluated as sign * (logdet[r] + sum_i sign * const_parts[i]), sign = +-1: bit-equal
+ * to mhe_glow_finish_f32 with logdet_const = sign * const_parts[0] when n_parts = 1.)  1 <= n_parts <= 64. */
 int mhe_glow_finish_dev_f32(const float *z_padded, const float *v_padded, const float *logdet, float *v_out, float *log_prob,
                             long R, int dim, float sign, const float *const_parts, int n_parts, void *stream);
 /* Per-image reverse stages of the one-launch Glow kernel's tape (csrc/glow.hip; sample-major rows r = n B + b, C columns, bf16 tensors [N B][C]):
