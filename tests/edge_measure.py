@@ -1,5 +1,5 @@
 """The collect / print / assert pattern of the kernel-edge suites (test_gpu_forward_edges.py, test_gpu_reverse_edges.py,
-test_gpu_glow_edges.py).  A helper module, not a test."""
+test_gpu_glow_edges.py, test_gpu_flow_edges.py).  A helper module, not a test."""
 import numpy as np
 
 from conftest import assert_close
