@@ -270,6 +270,13 @@ int mhe_mano_regress_joints_f32(const float *verts, const float *tables, float *
 size_t mhe_mano_verts_bwd_workspace_floats(int R);
 int mhe_mano_verts_bwd_f32(const float *z, const float *tables, const float *g_verts, const float *g_joints_mm, float *g_z,
                            float *workspace, int R, int mm_mode, void *stream);
+/* Adds the adjoint of z into the two buffers the loss pass' reverse (mhe_mano_joints_*bwd_f32) has written - z is a gather of (det, th45),
+ * mano_pose_kernel: g_th45[r] += g_z[r][3:48], g_det_rows[r][0:3] += g_z[r][0:3], g_det_rows[r][3:13] += g_z[r][48:58] and, when g_logs_t
+ * [R,3] is not NULL, g_det_rows[r][13:16] += g_logs_t[r].  g_z [R,61] as mhe_mano_verts_bwd_f32 writes it: its columns 58..60 (zero by that
+ * contract) are not read.  One thread per element, one add each: two calls on the same buffers give the same bits.  No allocation, no host
+ * synchronisation.  MHE_ERR_ARG before the launch for a null g_z / g_th45 / g_det_rows, R < 1, or g_th45 / g_det_rows overlapping an input or
+ * each other. */
+int mhe_mano_z_grad_add_f32(const float *g_z, const float *g_logs_t, float *g_th45, float *g_det_rows, int R, void *stream);
 /* Transpose of mhe_mano_regress_joints_f32 (J_regressor rows, the five tip vertices, the RHD reorder): g_joints [R,21,3] -> g_verts
  * [R,778,3], written, or added to when accumulate != 0.  One thread per vertex, fixed-order sums, no atomics.  No allocation, no host
  * synchronisation.  MHE_ERR_ARG before the launch for a null pointer, R < 1 or g_verts overlapping an input. */
@@ -1077,6 +1084,17 @@ int mhe_silhouette_dist_f32(const float *verts, const float *logs_t, const int *
                             int *idx_m, int N, int B, int V, int S, void *stream);
 int mhe_silhouette_dist_bwd_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *idx_v, const int *idx_m,
                                 const float *g_dist, float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream);
+/* mhe_silhouette_dist_grad_f32: forward and reverse of every row in one launch, no index tensor (the training term, get_loss(sil_w=...)).
+ *   dist [R] (or NULL: not written), g_verts [R,V,3] and g_logs_t [R,3] are what mhe_silhouette_dist_f32 (with idx_v and idx_m) followed by
+ *   mhe_silhouette_dist_bwd_f32 write for the same inputs and g_dist [R]: the tie rule (lowest index), an empty pixel list -> zeros, a row with
+ *   a non-finite projected vertex -> dist NaN and zero gradients (other rows undisturbed), count clamped to 0 .. S^2 on the device, the z
+ *   column of g_verts 0.  One workgroup per row: a vertex's (min, argmin pixel) stays in its owner's registers, every kept pixel's argmin
+ *   vertex goes to a 16-bit list in LDS that the owners walk in ascending m after a barrier - the pair evaluations, the two minima and the walk
+ *   are the device functions of the two kernels above.  No atomics, every sum f64 in their fixed order: two calls give the same bits.  No
+ *   allocation, no workspace, no host read: the call can be captured into a HIP graph.  MHE_ERR_ARG before the launch for a null pointer (dist
+ *   excepted), a shape out of range (as above), or outputs overlapping inputs or each other. */
+int mhe_silhouette_dist_grad_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const float *g_dist, float *dist,
+                                 float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream);
 
 #ifdef __cplusplus
 }

@@ -136,6 +136,19 @@ def chamfer_select(output, target, Q=1, points="xyz"):
     return _cut(output, dist, Q, "chamfer")
 
 
+def silhouette_mask_checks(hand_mask, B, size, who="silhouette_dist"):
+    """the mask's half of silhouette_dist's shape checks, shared with the training term (MHEnt.get_loss(sil_w=...)): hand_mask (B, H, H) with
+    H a multiple of size, size an int in 1..64.  B None: taken from the mask."""
+    if not isinstance(hand_mask, torch.Tensor) or hand_mask.dim() != 3 or (B is not None and hand_mask.shape[0] != B) or \
+            hand_mask.shape[1] != hand_mask.shape[2]:
+        raise ValueError(f"{who}: hand_mask must be (B, H, H){'' if B is None else f' with B={B}'}, got {tuple(getattr(hand_mask, 'shape', ()))}")
+    if not isinstance(size, int) or not 1 <= size <= ops.SILHOUETTE_MAX_SIZE:
+        raise ValueError(f"{who}: size={size!r} (1..{ops.SILHOUETTE_MAX_SIZE})")
+    H = hand_mask.shape[1]
+    if H < size or H % size:
+        raise ValueError(f"{who}: hand_mask is {H} x {H}, not a multiple of size={size}")
+
+
 def _silhouette_operands(verts, logs_t, hand_mask, size):
     """the checks of silhouette_dist that need no device -> (verts [N,B,V,3], logs_t [N,B,3], hand_mask [B,H,H], size)"""
     who = "silhouette_dist"
@@ -147,13 +160,7 @@ def _silhouette_operands(verts, logs_t, hand_mask, size):
         raise ValueError(f"{who}: V={V} vertices per hypothesis (1..{ops.SILHOUETTE_MAX_VERTS})")
     if not isinstance(logs_t, torch.Tensor) or tuple(logs_t.shape) != (N, B, 3):
         raise ValueError(f"{who}: logs_t must be (N, B, 3) = ({N}, {B}, 3), got {tuple(getattr(logs_t, 'shape', ()))}")
-    if not isinstance(hand_mask, torch.Tensor) or hand_mask.dim() != 3 or hand_mask.shape[0] != B or hand_mask.shape[1] != hand_mask.shape[2]:
-        raise ValueError(f"{who}: hand_mask must be (B, H, H) with B={B}, got {tuple(getattr(hand_mask, 'shape', ()))}")
-    if not isinstance(size, int) or not 1 <= size <= ops.SILHOUETTE_MAX_SIZE:
-        raise ValueError(f"{who}: size={size!r} (1..{ops.SILHOUETTE_MAX_SIZE})")
-    H = hand_mask.shape[1]
-    if H < size or H % size:
-        raise ValueError(f"{who}: hand_mask is {H} x {H}, not a multiple of size={size}")
+    silhouette_mask_checks(hand_mask, B, size, who)
     if hand_mask.dtype not in (torch.bool, torch.uint8, torch.float32):
         hand_mask = hand_mask.float()
     return verts.reshape(N, B, V, 3).float().contiguous(), logs_t.float().contiguous(), hand_mask.contiguous(), size
@@ -191,8 +198,9 @@ def silhouette_dist(verts, logs_t, hand_mask, size=64, parts=False):
     a row with a non-finite projected vertex NaN and a zero gradient.  Differentiable with respect to verts and logs_t (the z column of the
     vertices and the mask get none; inside and cover are returned detached).  Runs on csrc/silhouette.hip, nothing on the host reads the
     pixel count: the call can be captured into a HIP graph.  HIP tensors only (MheError otherwise); ValueError for a bad rank or shape, H not
-    a multiple of size, V outside 1..778.  The reverse of the mesh exists (ManoLayer.verts carries the gradient on to z: ops.mano_verts_bwd); the training term
-    (a get_loss keyword) is not built yet."""
+    a multiple of size, V outside 1..778.  The reverse of the mesh exists (ManoLayer.verts carries the gradient on to z: ops.mano_verts_bwd), and
+    the training term is MHEnt.get_loss(sil_w=...): log_p -= sil_w * mean_n of this distance, whose reverse (ops.silhouette_dist_grad) holds the
+    argmins in registers and LDS instead of the two index tensors this function's autograd node keeps."""
     v, lt, mask, size = _silhouette_operands(verts, logs_t, hand_mask, size)
     pixels, count = ops.silhouette_pixels(mask, size)
     dist, pt = _Silhouette.apply(v, lt, pixels, count)

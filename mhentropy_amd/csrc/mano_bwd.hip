@@ -390,7 +390,25 @@ __global__ __launch_bounds__(256) void mano_verts_bwd_kernel(const float *__rest
     }
 }
 
-// transpose of regress_joints_kernel (mano.hip): g_verts[v] (+)= sum_j J_regressor[j][v] g_kp[map(j)] + g_kp[tip] at the five tip vertices,
+// z is a gather of (det, th45) (mano_pose_kernel: th3 = det[0:3], th45, beta = det[3:13], (log s, t) = det[13:16]): the adjoint of z, with
+// its camera columns taken from g_logs_t, is added to the two buffers the loss pass' reverse wrote.  One thread per column of a row, one add.
+__global__ __launch_bounds__(256) void mano_z_grad_add_kernel(const float *__restrict__ g_z, const float *__restrict__ g_logs_t,
+                                                              float *__restrict__ g_th45, float *__restrict__ g_det_rows, int R) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)R * 61) return;
+    const size_t r = i / 61;
+    const int c = (int)(i - r * 61);
+    if (c >= 58) {
+        if (g_logs_t) g_det_rows[r * 16 + 13 + (c - 58)] += g_logs_t[r * 3 + (c - 58)];
+        return;
+    }
+    const float g = g_z[i];
+    if (c < 3) g_det_rows[r * 16 + c] += g;
+    else if (c < 48) g_th45[r * 45 + (c - 3)] += g;
+    else g_det_rows[r * 16 + 3 + (c - 48)] += g;
+}
+
+// transpose of regress_joints_kernel (mano.hip): g_verts[v] (+)=sum_j J_regressor[j][v] g_kp[map(j)] + g_kp[tip] at the five tip vertices,
 // g_kp = g_joints with the RHD reorder undone.  One workgroup per hypothesis, one thread per vertex: a fixed-order sum, no atomics
 __global__ __launch_bounds__(256) void regress_joints_bwd_kernel(const float *__restrict__ g_joints, const float *__restrict__ tables,
                                                                  float *__restrict__ g_verts, int R, int accumulate) {
@@ -516,6 +534,20 @@ extern "C" int mhe_mano_verts_bwd_f32(const float *z, const float *tables, const
     const size_t lds = (mano::JOINT_FLOATS + 4 * (mano::SCRATCH + mano::A_SCRATCH)) * sizeof(float);
     hipLaunchKernelGGL(mano::mano_verts_bwd_kernel, dim3(blocks), dim3(256), lds, st, z, tables, adj, g_joints_mm, g_z, R);
     return check_launch("mano_verts_bwd_kernel");
+}
+
+extern "C" int mhe_mano_z_grad_add_f32(const float *g_z, const float *g_logs_t, float *g_th45, float *g_det_rows, int R, void *stream) {
+    const char *who = "mhe_mano_z_grad_add_f32";
+    MHE_REQUIRE(g_z && g_th45 && g_det_rows, "%s: null pointer (g_z, g_th45, g_det_rows)", who);
+    MHE_REQUIRE(R > 0, "%s: R=%d", who, R);
+    const size_t nz = (size_t)R * 61 * 4, nl = (size_t)R * 12, n45 = (size_t)R * 45 * 4, nd = (size_t)R * 16 * 4;
+    MHE_REQUIRE(disjoint(g_th45, n45, g_z, nz) && disjoint(g_th45, n45, g_logs_t, nl) && disjoint(g_det_rows, nd, g_z, nz) &&
+                    disjoint(g_det_rows, nd, g_logs_t, nl) && disjoint(g_th45, n45, g_det_rows, nd),
+                "%s: g_th45 and g_det_rows must not overlap the inputs or each other", who);
+    const size_t n = (size_t)R * 61;
+    hipLaunchKernelGGL(mano::mano_z_grad_add_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g_z, g_logs_t, g_th45,
+                       g_det_rows, R);
+    return check_launch("mano_z_grad_add_kernel");
 }
 
 extern "C" int mhe_mano_regress_joints_bwd_f32(const float *g_joints, const float *tables, float *g_verts, int R, int accumulate, void *stream) {

@@ -109,6 +109,82 @@ __device__ __forceinline__ void scan_verts(const float2 *pv, int V, const float 
     }
 }
 
+// u(p - c): the unit vector from centre c to the vertex at (qx, qy) the pixel chose; false (nothing to add) at distance 0
+__device__ __forceinline__ bool cover_unit(float qx, float qy, const float2 &c, float &ux, float &uy) {
+    const float dx = qx - c.x, dy = qy - c.y, q = fmaf(dy, dy, dx * dx);
+    if (!(q > 0.f)) return false;
+    const float inv = 1.f / sqrtf(q);
+    ux = dx * inv; uy = dy * inv;
+    return true;
+}
+
+// gradient of the box distance of the vertex at (qx, qy) to the pixel of centre c, 0 where the distance is 0
+__device__ __forceinline__ void box_unit(float qx, float qy, const float2 &c, float h, float &ux, float &uy) {
+    const float dx = qx - c.x, dy = qy - c.y;
+    const float ax = fmaxf(fabsf(dx) - h, 0.f), ay = fmaxf(fabsf(dy) - h, 0.f), q = fmaf(ay, ay, ax * ax);
+    ux = uy = 0.f;
+    if (q > 0.f) {
+        const float inv = 1.f / sqrtf(q);
+        ux = copysignf(ax, dx) * inv; uy = copysignf(ay, dy) * inv;
+    }
+}
+
+// The gather walk of the reverse: the thread that owns vertex v (tid = v mod NT, slot v / NT) walks the row's pixel -> vertex list in ascending
+// m and adds the unit vectors of the pixels that chose v to its own registers.  vert_of(m): the listed vertex (an index outside 0 .. V-1
+// contributes nothing and is never used as an address), centre_of(m): the pixel's centre.
+struct ListGlobal {                // dist_bwd_kernel: idx_m and the packed pixels, staged in LDS
+    const int *ti, *pk;
+    float fS;
+    __device__ __forceinline__ int vert_of(int m) const { return ti[m]; }
+    __device__ __forceinline__ float2 centre_of(int m) const { return centre(pk[m], fS); }
+};
+struct ListLocal {                 // dist_grad_kernel: the 16-bit list and the decoded centres of its own forward
+    const unsigned short *lv;
+    const float2 *pc;
+    __device__ __forceinline__ int vert_of(int m) const { return (int)lv[m]; }
+    __device__ __forceinline__ float2 centre_of(int m) const { return pc[m]; }
+};
+
+template <typename List>
+__device__ __forceinline__ void gather_walk(int M, int V, int tid, const float *px, const float *py, const List list, double *gx, double *gy) {
+#pragma unroll
+    for (int k = 0; k < KV; ++k) gx[k] = gy[k] = 0.0;
+    for (int m = 0; m < M; ++m) {
+        const int t = list.vert_of(m);
+        if ((t & (NT - 1)) == tid && (unsigned)t < (unsigned)V) {
+            const int slot = t / NT;
+            float qx = px[0], qy = py[0];
+#pragma unroll
+            for (int k = 1; k < KV; ++k) { qx = slot == k ? px[k] : qx; qy = slot == k ? py[k] : qy; }
+            float ux, uy;
+            if (cover_unit(qx, qy, list.centre_of(m), ux, uy)) {
+#pragma unroll
+                for (int k = 0; k < KV; ++k) { gx[k] = slot == k ? gx[k] + (double)ux : gx[k]; gy[k] = slot == k ? gy[k] + (double)uy : gy[k]; }
+            }
+        }
+    }
+}
+
+// g_p_v of one vertex from its two halves (u: the box gradient to its own pixel, (gx, gy): the walk's sum), its g_verts row and its terms of
+// the three sums of g_logs_t
+__device__ __forceinline__ void finish_vertex(float ux, float uy, double gx, double gy, double gd, double wV, double wM, float es, float vx, float vy,
+                                              float *g, double &s_l, double &s_x, double &s_y) {
+    const double gpx = gd * ((double)ux * wV + gx * wM), gpy = gd * ((double)uy * wV + gy * wM);
+    g[0] = (float)((double)es * gpx); g[1] = (float)((double)es * gpy); g[2] = 0.f;
+    s_l += gpx * (double)(es * vx) + gpy * (double)(es * vy);
+    s_x += gpx; s_y += gpy;
+}
+
+// the row's (inside, cover) from the four waves' partial sums, in order; (0, 0) for an empty list
+__device__ __forceinline__ float2 row_parts(const double (*red)[NW], int V, int M) {
+    float I = 0.f, Cv = 0.f;
+    if (M) {
+        I = (float)((((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]) / (double)V);
+        Cv = (float)((((red[1][0] + red[1][1]) + red[1][2]) + red[1][3]) / (double)M);
+    }
+    return make_float2(I, Cv);
+}
+
 // Forward, one workgroup per row r = n B + b.  The row's vertices are projected once (registers of their thread, and LDS for the cover
 // direction), the image's kept pixels are decoded once into LDS as centres; both directional minima are taken from LDS.  The count is
 // clamped to 0 .. S^2 before it bounds anything.  A non-finite projected vertex makes the row NaN (the flag, not the minima, carries it:
@@ -191,12 +267,8 @@ __global__ __launch_bounds__(NT) void dist_kernel(const float *__restrict__ vert
     if (lane == 0) { red[0][wave] = s_in; red[1][wave] = s_co; }
     __syncthreads();
     if (tid == 0) {
-        float I = 0.f, Cv = 0.f;
-        if (M) {
-            I = (float)((((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]) / (double)V);
-            Cv = (float)((((red[1][0] + red[1][1]) + red[1][2]) + red[1][3]) / (double)M);
-        }
-        float D = I + Cv;
+        const float2 ic = row_parts(red, V, M);
+        float I = ic.x, Cv = ic.y, D = I + Cv;
         if (bad) I = Cv = D = __builtin_nanf("");
         dist[r] = D;
         if (parts) { parts[r * 2] = I; parts[r * 2 + 1] = Cv; }
@@ -248,24 +320,7 @@ __global__ __launch_bounds__(NT) void dist_bwd_kernel(const float *__restrict__ 
     }
 
     double gx[KV], gy[KV];
-#pragma unroll
-    for (int k = 0; k < KV; ++k) gx[k] = gy[k] = 0.0;
-    for (int m = 0; m < M; ++m) {
-        const int t = ti[m];
-        if ((t & (NT - 1)) == tid && (unsigned)t < (unsigned)V) {
-            const int slot = t / NT;
-            float qx = px[0], qy = py[0];
-#pragma unroll
-            for (int k = 1; k < KV; ++k) if (slot == k) { qx = px[k]; qy = py[k]; }
-            const float2 c = centre(pk[m], fS);
-            const float dx = qx - c.x, dy = qy - c.y, q = fmaf(dy, dy, dx * dx);
-            if (q > 0.f) {
-                const float inv = 1.f / sqrtf(q);
-#pragma unroll
-                for (int k = 0; k < KV; ++k) if (slot == k) { gx[k] += (double)(dx * inv); gy[k] += (double)(dy * inv); }
-            }
-        }
-    }
+    gather_walk(M, V, tid, px, py, ListGlobal{ti, pk, fS}, gx, gy);
 
     const double gd = (double)g_dist[r], wV = 1.0 / (double)V, wM = 1.0 / (double)M;
     double s_l = 0.0, s_x = 0.0, s_y = 0.0;
@@ -275,26 +330,126 @@ __global__ __launch_bounds__(NT) void dist_bwd_kernel(const float *__restrict__ 
         if (v < V) {
             float ux = 0.f, uy = 0.f;
             const int iv = idx_v[r * V + v];
-            if ((unsigned)iv < (unsigned)M) {
-                const float2 c = centre(pk[iv], fS);
-                const float dx = px[k] - c.x, dy = py[k] - c.y;
-                const float ax = fmaxf(fabsf(dx) - h, 0.f), ay = fmaxf(fabsf(dy) - h, 0.f), q = fmaf(ay, ay, ax * ax);
-                if (q > 0.f) {
-                    const float inv = 1.f / sqrtf(q);
-                    ux = copysignf(ax, dx) * inv; uy = copysignf(ay, dy) * inv;
-                }
-            }
-            const double gpx = gd * ((double)ux * wV + gx[k] * wM), gpy = gd * ((double)uy * wV + gy[k] * wM);
-            float *g = g_verts + (r * V + v) * 3;
-            g[0] = (float)((double)es * gpx); g[1] = (float)((double)es * gpy); g[2] = 0.f;
-            s_l += gpx * (double)(es * vx[k]) + gpy * (double)(es * vy[k]);
-            s_x += gpx; s_y += gpy;
+            if ((unsigned)iv < (unsigned)M) box_unit(px[k], py[k], centre(pk[iv], fS), h, ux, uy);
+            finish_vertex(ux, uy, gx[k], gy[k], gd, wV, wM, es, vx[k], vy[k], g_verts + (r * V + v) * 3, s_l, s_x, s_y);
         }
     }
     s_l = wave_sum(s_l); s_x = wave_sum(s_x); s_y = wave_sum(s_y);
     if (lane == 0) { red[0][wave] = s_l; red[1][wave] = s_x; red[2][wave] = s_y; }
     __syncthreads();
     if (tid < 3) g_logs_t[r * 3 + tid] = (float)(((red[tid][0] + red[tid][1]) + red[tid][2]) + red[tid][3]);
+}
+
+// Forward and reverse of one row in one launch: what dist_kernel<true> followed by dist_bwd_kernel write, without the two index tensors.  The
+// vertex's own (min, argmin pixel) stays in the registers of its owner; every kept pixel's argmin vertex (V <= 778: 16 bits) goes to an LDS
+// list in the rounds of the forward, and after the barrier the owners walk that list as dist_bwd_kernel walks idx_m.  The centres the walk
+// needs are the decoded ones of the forward.  dist may be null.
+__global__ __launch_bounds__(NT) void dist_grad_kernel(const float *__restrict__ verts, const float *__restrict__ logs_t, const int *__restrict__ pixels,
+                                                       const int *__restrict__ count, const float *__restrict__ g_dist, float *__restrict__ dist,
+                                                       float *__restrict__ g_verts, float *__restrict__ g_logs_t, int B, int V, int S) {
+    __shared__ float2 pc[PMAX];
+    __shared__ float2 pv[KV * NT];
+    __shared__ unsigned short lv[PMAX];
+    __shared__ double red[2][NW];
+    __shared__ double red3[3][NW];
+    static_assert(VMAX <= 0xffff, "a listed vertex is 16 bits");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t r = blockIdx.x;
+    const int b = (int)(r % (size_t)B), P = S * S, M = min(max(count[b], 0), P);
+    const float fS = (float)S, h = 1.f / fS;
+    const float es = expf(logs_t[r * 3]), tx = logs_t[r * 3 + 1], ty = logs_t[r * 3 + 2];
+
+    float vx[KV], vy[KV], px[KV], py[KV], m1[KV];
+    int i1[KV];
+    int bad = 0;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+        const int v = k * NT + tid;
+        vx[k] = vy[k] = px[k] = py[k] = 0.f;
+        m1[k] = __builtin_inff();
+        i1[k] = 0;
+        if (v < V) {
+            const float *p = verts + (r * V + v) * 3;
+            vx[k] = p[0]; vy[k] = p[1];
+            px[k] = fmaf(es, vx[k], tx); py[k] = fmaf(es, vy[k], ty);
+            bad |= !(isfinite(px[k]) && isfinite(py[k]));
+            pv[v] = make_float2(px[k], py[k]);
+        }
+    }
+    for (int m = tid; m < M; m += NT) pc[m] = centre(pixels[(size_t)b * P + m], fS);
+    bad = __syncthreads_or(bad);
+    if (bad || M == 0) {
+#pragma unroll
+        for (int k = 0; k < KV; ++k) {
+            const int v = k * NT + tid;
+            if (v < V) { float *g = g_verts + (r * V + v) * 3; g[0] = 0.f; g[1] = 0.f; g[2] = 0.f; }
+        }
+        if (tid < 3) g_logs_t[r * 3 + tid] = 0.f;
+        if (tid == 0 && dist) dist[r] = bad ? __builtin_nanf("") : 0.f;
+        return;
+    }
+
+    // mesh -> mask: (min, argmin) of the thread's own vertices
+    switch ((V + NT - 1) / NT) {
+#define MHE_CASE(K) case K: scan_pixels<true, K>(pc, M, h, px, py, m1, i1); break;
+        MHE_CASE(1) MHE_CASE(2) MHE_CASE(3) MHE_CASE(4)
+#undef MHE_CASE
+    }
+    double s_in = 0.0, s_co = 0.0;
+#pragma unroll
+    for (int k = 0; k < KV; ++k)
+        if (k * NT + tid < V) s_in += (double)sqrtf(m1[k]);
+    // mask -> mesh, rounds of TM kept pixels: the argmin vertex of pixel m to the LDS list
+    for (int t0 = 0; t0 < M; t0 += TM) {
+        const int tm = min(TM, M - t0);
+        float cx[KM], cy[KM], m2[KM];
+        int i2[KM];
+#pragma unroll
+        for (int k = 0; k < KM; ++k) {
+            const int m = k * NT + tid;
+            const float2 c = m < tm ? pc[t0 + m] : make_float2(0.f, 0.f);
+            cx[k] = c.x; cy[k] = c.y;
+        }
+        switch ((tm + NT - 1) / NT) {
+#define MHE_CASE(K) case K: scan_verts<true, K>(pv, V, cx, cy, m2, i2); break;
+            MHE_CASE(1) MHE_CASE(2) MHE_CASE(3) MHE_CASE(4)
+#undef MHE_CASE
+        }
+#pragma unroll
+        for (int k = 0; k < KM; ++k) {
+            const int m = k * NT + tid;
+            if (m < tm) {
+                s_co += (double)sqrtf(m2[k]);
+                lv[t0 + m] = (unsigned short)i2[k];
+            }
+        }
+    }
+    s_in = wave_sum(s_in); s_co = wave_sum(s_co);
+    if (lane == 0) { red[0][wave] = s_in; red[1][wave] = s_co; }
+    __syncthreads();                       // the sums and the list
+    if (tid == 0 && dist) {
+        const float2 ic = row_parts(red, V, M);
+        dist[r] = ic.x + ic.y;
+    }
+
+    double gx[KV], gy[KV];
+    gather_walk(M, V, tid, px, py, ListLocal{lv, pc}, gx, gy);
+
+    const double gd = (double)g_dist[r], wV = 1.0 / (double)V, wM = 1.0 / (double)M;
+    double s_l = 0.0, s_x = 0.0, s_y = 0.0;
+#pragma unroll
+    for (int k = 0; k < KV; ++k) {
+        const int v = k * NT + tid;
+        if (v < V) {
+            float ux, uy;
+            box_unit(px[k], py[k], pc[i1[k]], h, ux, uy);
+            finish_vertex(ux, uy, gx[k], gy[k], gd, wV, wM, es, vx[k], vy[k], g_verts + (r * V + v) * 3, s_l, s_x, s_y);
+        }
+    }
+    s_l = wave_sum(s_l); s_x = wave_sum(s_x); s_y = wave_sum(s_y);
+    if (lane == 0) { red3[0][wave] = s_l; red3[1][wave] = s_x; red3[2][wave] = s_y; }
+    __syncthreads();
+    if (tid < 3) g_logs_t[r * 3 + tid] = (float)(((red3[tid][0] + red3[tid][1]) + red3[tid][2]) + red3[tid][3]);
 }
 
 }}  // namespace mhe::silhouette
@@ -367,4 +522,22 @@ extern "C" int mhe_silhouette_dist_bwd_f32(const float *verts, const float *logs
     hipLaunchKernelGGL(silhouette::dist_bwd_kernel, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, idx_v,
                        idx_m, g_dist, g_verts, g_logs_t, B, V, S);
     return check_launch("silhouette::dist_bwd_kernel");
+}
+
+extern "C" int mhe_silhouette_dist_grad_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const float *g_dist, float *dist,
+                                            float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream) {
+    if (int st = silhouette_args("mhe_silhouette_dist_grad_f32", verts, logs_t, pixels, count, N, B, V, S)) return st;
+    MHE_REQUIRE(g_dist && g_verts && g_logs_t, "mhe_silhouette_dist_grad_f32: null pointer (g_dist, g_verts, g_logs_t)");
+    const size_t R = (size_t)N * B, P = (size_t)S * S;
+    struct { const void *p; size_t n; } in[5] = {{verts, R * V * 12}, {logs_t, R * 12}, {pixels, (size_t)B * P * 4}, {count, (size_t)B * 4}, {g_dist, R * 4}},
+                                        out[3] = {{dist, R * 4}, {g_verts, R * V * 12}, {g_logs_t, R * 12}};
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 5; ++i)
+            MHE_REQUIRE(disjoint(out[o].p, out[o].n, in[i].p, in[i].n), "mhe_silhouette_dist_grad_f32: output %d overlaps input %d", o, i);
+        for (int q = 0; q < o; ++q)
+            MHE_REQUIRE(disjoint(out[o].p, out[o].n, out[q].p, out[q].n), "mhe_silhouette_dist_grad_f32: outputs %d and %d overlap", q, o);
+    }
+    hipLaunchKernelGGL(silhouette::dist_grad_kernel, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, g_dist,
+                       dist, g_verts, g_logs_t, B, V, S);
+    return check_launch("silhouette::dist_grad_kernel");
 }

@@ -14,6 +14,9 @@ Extensions (all optional, defaults reproduce the reference):
     set False to run the reference's two-pass form,
   * `chamfer_w=` / the attribute `MHEnt.chamfer_w` (0.0): the weight of the hand-object Chamfer term the reference has behind a literal
     `use_chamfer_loss = False` (hand/network.py:821-826, its w_chamfer = 10): log_p -= chamfer_w * chamfer, new key 'chamfer' (B,) in mm.
+  * `sil_w=` / the attribute `MHEnt.sil_w` (0.0): the weight of the silhouette term the reference only prepared for (`mask_sz=64`,
+    hand/network.py:363; its renderer is commented out): log_p -= sil_w * silhouette, new key 'silhouette' (B,), the mean over the hypotheses
+    of criteria.silhouette_dist of the mesh against y['hand_mask'] at grid size `MHEnt.sil_size` (64).
 The `q_z_giv_i_model='glow'` branch (hand/network.py:342-344,736-742) runs on mhentropy_amd/glow.py's ConditionalGlow - a
 restatement of the published nflows algorithm, parity UNPINNED (the third-party class is absent from the reference tree).
 Dead reference branches (VAE prior, GT evidences) raise NotImplementedError.  The renderer (hand/network.py:528-558, whose third-party
@@ -124,6 +127,8 @@ class MHEnt(nn.Module):
         self.loss_N = 10                        # network.py:780
         self.fused_entropy = True
         self.chamfer_w = 0.0                    # network.py:821-826: use_chamfer_loss = False as shipped; its w_chamfer is 10
+        self.sil_w = 0.0                        # the silhouette term (no reference counterpart: its renderer is commented out)
+        self.sil_size = 64                      # network.py:363: mask_sz
 
     # ---- pieces ---------------------------------------------------------------
     def _det(self, feat):
@@ -163,24 +168,58 @@ class MHEnt(nn.Module):
         scale, root, obj, count = chamfer_target_operands(y, who="get_loss(chamfer_w)")
         return w, (scale.float(), root.float(), obj.float(), count)
 
+    def sil_operands(self, y, sil_w=None, B=None):
+        """(weight, (pixels, count) | None) of the silhouette term for the target y: sil_w None falls back to self.sil_w; a weight of 0 is
+        the term off (None, nothing launched).  y['hand_mask'] (B, H, H) (B None: whatever the mask has) bool / uint8 / float32 with H a multiple of self.sil_size; the shape
+        checks are criteria.silhouette_dist's, on the host, before any launch; the kept-pixel list (ops.silhouette_pixels) is the one launch."""
+        w = float(self.sil_w if sil_w is None else sil_w)
+        if not w >= 0.0:
+            raise ValueError(f"get_loss: sil_w={w} (>= 0)")
+        if w == 0.0:
+            return 0.0, None
+        if "hand_mask" not in y:
+            raise ValueError("get_loss(sil_w > 0) needs the mask target y['hand_mask'] (B, H, H)")
+        from .criteria import silhouette_mask_checks
+        mask = y["hand_mask"]
+        silhouette_mask_checks(mask, B, int(self.sil_size), who="get_loss(sil_w)")
+        if mask.dtype not in (torch.bool, torch.uint8, torch.float32):
+            raise ValueError(f"get_loss(sil_w): y['hand_mask'] must be bool, uint8 or float32, got {mask.dtype}")
+        return w, ops.silhouette_pixels(mask.contiguous(), int(self.sil_size))
+
+    def silhouette_rows(self, z, sil, N, B):
+        """the silhouette term's forward on the loss pass' z [N*B,61]: the normalised mesh (ops.mano_verts), its distance to the kept pixels
+        sil = (pixels, count) without index tensors, the mean over the hypotheses -> (verts [N*B,778,3], logs_t [N*B,3], silhouette [B])"""
+        if sil[0].shape[0] != B:
+            raise ValueError(f"get_loss(sil_w): y['hand_mask'] has {sil[0].shape[0]} images, the batch {B}")
+        verts = ops.mano_verts(z, self.mano_dec.table_blob())
+        logs_t = z[:, 58:61].contiguous()
+        dist, _ = ops.silhouette_dist(verts.view(N, B, 778, 3), logs_t.view(N, B, 3), *sil)
+        return verts, logs_t, ops.elbo_reduce(dist.view(N * B), None, N, B)[0]
+
     # ---- reference surface ------------------------------------------------------
-    def _reverse_kld(self, y, x, mods=None, return_dict=True, N=None, noise=None, chamfer_w=None):
+    def _reverse_kld(self, y, x, mods=None, return_dict=True, N=None, noise=None, chamfer_w=None, sil_w=None):
         """reference hand/network.py:760-831.  mods: ['uv'] (None; weak supervision), ['xyz'] or ['xyz', 'uv'] (3D supervision,
         hand/CrossModalHand.py:354: adds the Laplace likelihood of the normalised joints against y['pose3d'], network.py:620-643).
         chamfer_w (None: self.chamfer_w) > 0: the Chamfer term of network.py:821-826 for N hypotheses - out['chamfer'][b] = mean_n of
         criteria.chamfer_dist of row n*B+b's joints against y['object_verts'] (y['object_count'], 'scale', 'original_pose3d'), and
-        log_p -= chamfer_w * chamfer; the other keys are not touched by it."""
+        log_p -= chamfer_w * chamfer; the other keys are not touched by it.
+        sil_w (None: self.sil_w) > 0: the silhouette term - out['silhouette'][b] = mean_n of criteria.silhouette_dist of row n*B+b's normalised
+        mesh (ops.mano_verts(z), the 'verts' of sample()) under logs_t = z[:, 58:61] against y['hand_mask'][b] at grid size self.sil_size, and
+        log_p -= sil_w * silhouette; the other keys are not touched by it.  Both terms may be on."""
         bits = ops.mods_bits(mods)
         if bits & ops.MODS_XYZ and "pose3d" not in y:
             raise ValueError("get_loss(mods=[..., 'xyz']) needs the 3D target y['pose3d'] (B, 63)")
         cw, cham = self.chamfer_operands(y, chamfer_w)
+        sw = float(self.sil_w if sil_w is None else sil_w)
         N = N or self.loss_N
         tr = getattr(self, "_trainer", None)
         if tr is not None and self.training and torch.is_grad_enabled():
             # a train.TrainStep is attached: the loss dict comes out as ONE autograd node whose backward is the
             # hand-written reverse pass, so the reference's `total_loss.backward()` works unchanged
             from .train import differentiable_get_loss
-            return differentiable_get_loss(tr, x, y, N=N, noise=noise, mods=bits, chamfer_w=cw)
+            return differentiable_get_loss(tr, x, y, N=N, noise=noise, mods=bits, chamfer_w=cw, sil_w=sw)
+        sw, sil = self.sil_operands(y, sw, None if x is None else x.shape[0])
+        want = ("log_p", "norms") + (("z",) if sil is not None else ())
         _, feat, _ = self.feat_extractor(x)
         B = feat.shape[0]
         if isinstance(self.q_z_giv_i, ConditionalGlow):      # entropy from the sampling pass itself (network.py:781-783,798-799)
@@ -195,15 +234,15 @@ class MHEnt(nn.Module):
         if cham is not None:
             o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(),
                                 y["crop_uv"].contiguous() if bits & ops.MODS_UV else None, y["vis"].contiguous(), self.b_2d,
-                                self.th45_ref_alpha, want=("log_p", "norms"), mods=bits, laplace_b_3d=self.b_3d, chamfer=cham,
+                                self.th45_ref_alpha, want=want, mods=bits, laplace_b_3d=self.b_3d, chamfer=cham,
                                 pose3d=y["pose3d"].contiguous().float() if bits & ops.MODS_XYZ else None)
         elif bits == ops.MODS_UV:
             o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(), y["crop_uv"].contiguous(),
-                                y["vis"].contiguous(), self.b_2d, self.th45_ref_alpha, want=("log_p", "norms"))
+                                y["vis"].contiguous(), self.b_2d, self.th45_ref_alpha, want=want)
         else:
             o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(),
                                 y["crop_uv"].contiguous() if bits & ops.MODS_UV else None, y["vis"].contiguous(), self.b_2d,
-                                self.th45_ref_alpha, want=("log_p", "norms"), pose3d=y["pose3d"].contiguous().float(), mods=bits,
+                                self.th45_ref_alpha, want=want, pose3d=y["pose3d"].contiguous().float(), mods=bits,
                                 laplace_b_3d=self.b_3d)
         q_log_p, h, log_p = ops.elbo_reduce(o["log_p"], log_q, N, B)
         out = {"th_norm": o["norms"][:, 0], "bt_norm": o["norms"][:, 1], "q_log_p_z_giv_y": q_log_p}
@@ -215,6 +254,9 @@ class MHEnt(nn.Module):
         if cham is not None:
             out["chamfer"] = ops.elbo_reduce(o["chamfer"], None, N, B)[0]          # mean over the N hypotheses
             out["log_p"] = out["log_p"] - cw * out["chamfer"]
+        if sil is not None:
+            out["silhouette"] = self.silhouette_rows(o["z"], sil, N, B)[2]
+            out["log_p"] = out["log_p"] - sw * out["silhouette"]
         if not return_dict:
             raise NotImplementedError
         return out

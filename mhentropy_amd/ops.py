@@ -384,8 +384,9 @@ MODS_UV, MODS_XYZ = 1, 2           # MHE_MODS_* of include/mhe.h
 def mods_bits(mods):
     """the reference's get_loss `mods` (hand/network.py:620-643; None means ['uv']) -> the MHE_MODS_* bit set.  'uv' and 'xyz' in any
     order; anything else (the dead p_ys branch) is not built.  The render mods 'm' / 'depth' are no likelihood here: MHEnt.sample(mods=)
-    takes them (ops.render_mesh, forward only) and the train step has no mask term.  Nor is the chamfer term a mod: its distance is ops.chamfer
-    / criteria.chamfer_dist, and the loss takes it through get_loss(chamfer_w=...) (mano_joints(chamfer=...))"""
+    takes them (ops.render_mesh, forward only).  Nor are the chamfer and the silhouette term mods: their distances are ops.chamfer /
+    criteria.chamfer_dist and ops.silhouette_dist / criteria.silhouette_dist, and the loss takes them through get_loss(chamfer_w=...)
+    (mano_joints(chamfer=...)) and get_loss(sil_w=...)"""
     if mods is None:
         return MODS_UV
     names = [mods] if isinstance(mods, str) else list(mods)
@@ -540,6 +541,17 @@ def mano_verts_bwd(z, tables, g_verts, mm=False, g_joints_mm=None):
     ws = torch.empty(_lib.lib().mhe_mano_verts_bwd_workspace_floats(R), device=z.device, dtype=torch.float32)
     launch("mhe_mano_verts_bwd_f32", z, tables, g_verts, g_joints_mm, g_z, ws, R, int(mm))
     return g_z
+
+
+def mano_z_grad_add(g_z, g_logs_t, g_th45, g_det_rows):
+    """adds the adjoint of z = gather(det, th45) into the loss pass' reverse buffers, in place (mhe_mano_z_grad_add_f32): g_z [R,61] of
+    mano_verts_bwd, g_logs_t [R,3] | None (the camera columns, det[13:16]), g_th45 [R,45], g_det_rows [R,16]"""
+    R = g_z.shape[0]
+    _chk(g_z, torch.float32, "mano_z_grad_add.g_z", (R, 61))
+    if g_logs_t is not None:
+        _chk(g_logs_t, torch.float32, "mano_z_grad_add.g_logs_t", (R, 3))
+    _chk(g_th45, torch.float32, "mano_z_grad_add.g_th45", (R, 45)); _chk(g_det_rows, torch.float32, "mano_z_grad_add.g_det_rows", (R, 16))
+    launch("mhe_mano_z_grad_add_f32", g_z, g_logs_t, g_th45, g_det_rows, R)
 
 
 def mano_regress_joints_bwd(g_joints, tables, out=None):
@@ -724,6 +736,17 @@ def silhouette_dist_bwd(verts, logs_t, pixels, count, idx_v, idx_m, g_dist):
     g_verts, g_logs_t = torch.empty_like(verts), torch.empty_like(logs_t)
     launch("mhe_silhouette_dist_bwd_f32", verts, logs_t, pixels, count, idx_v, idx_m, g_dist, g_verts, g_logs_t, N, B, V, S)
     return g_verts, g_logs_t
+
+
+def silhouette_dist_grad(verts, logs_t, pixels, count, g_dist, want_dist=False):
+    """silhouette_dist(want_idx=True) + silhouette_dist_bwd in one launch, without the two index tensors (mhe_silhouette_dist_grad_f32: the
+    argmins stay in registers and LDS): g_dist [N,B] -> (g_verts [N,B,V,3], g_logs_t [N,B,3]), with want_dist (dist [N,B], g_verts, g_logs_t)"""
+    N, B, V, S = _silhouette_operands(verts, logs_t, pixels, count, "silhouette_dist_grad")
+    _chk(g_dist, torch.float32, "silhouette_dist_grad.g_dist", (N, B))
+    dist = torch.empty(N, B, device=verts.device, dtype=torch.float32) if want_dist else None
+    g_verts, g_logs_t = torch.empty_like(verts), torch.empty_like(logs_t)
+    launch("mhe_silhouette_dist_grad_f32", verts, logs_t, pixels, count, g_dist, dist, g_verts, g_logs_t, N, B, V, S)
+    return (dist, g_verts, g_logs_t) if want_dist else (g_verts, g_logs_t)
 
 
 RENDER_OUTPUTS = ("mask", "depth", "iou_sums")

@@ -7,6 +7,7 @@ on synthetic batches (no dataset ships with this repository; the HO3D pipeline i
     python -m torch.distributed.run --nproc-per-node 8 -m mhentropy_amd.run ...      # one process per GPU, RCCL
     python -m mhentropy_amd.run --mods uv,xyz ...        # 3D-supervised training (hand/CrossModalHand.py:354, mods = ['xyz', 'uv'])
     python -m mhentropy_amd.run --chamfer-w 10 ...       # with the hand-object Chamfer term (hand/network.py:821-826, w_chamfer = 10)
+    python -m mhentropy_amd.run --sil-w 1 ...            # with the silhouette term (the mesh against the hand mask, MHEnt.get_loss(sil_w=...))
 """
 import argparse
 import json
@@ -57,9 +58,15 @@ def main(argv=None):
                     help="weight of the hand-object Chamfer term in the loss (hand/network.py:821-826: the reference's w_chamfer is 10, behind a "
                          "switch it ships off; 0 = off).  Synthetic objects (synth.object_targets) by default, the pipeline's object_verts "
                          "with object_count = the decoded samples' obj_count under --input-pipeline")
+    ap.add_argument("--sil-w", type=float, default=0.0,
+                    help="weight of the silhouette term in the loss (MHEnt.get_loss(sil_w=...): the distance of every hypothesis' projected mesh "
+                         "to the image's hand mask; 0 = off).  Synthetic masks around the target keypoints (synth.hand_masks) by default, the "
+                         "pipeline's hand_mask under --input-pipeline")
     args = ap.parse_args(argv)
     if args.chamfer_w < 0:
         raise SystemExit("--chamfer-w must be >= 0")
+    if not args.sil_w >= 0:
+        raise SystemExit("--sil-w must be >= 0")
     from . import ops
     mods = [m.strip() for m in args.mods.split(",") if m.strip()]
     ops.mods_bits(mods)                               # NotImplementedError for anything but uv / xyz, before any work
@@ -121,17 +128,20 @@ def main(argv=None):
                 x = torch.as_tensor(xn).cuda()
                 if args.chamfer_w > 0:
                     yn.update(synth.object_targets(args.seed + 1000 * rank + step, args.batch, with_count=True))
+                if args.sil_w > 0:
+                    yn["hand_mask"] = synth.hand_masks(args.seed + 1000 * rank + step, args.batch, crop_uv=yn["crop_uv"])
                 y = {k: torch.as_tensor(v).cuda() for k, v in yn.items()}
             model.training_step_start(step)
             if args.graph and not args.test_samples:
                 from .train import GraphedStep
                 yk = {k: y[k].contiguous() for k in ("crop_uv", "vis") + (("pose3d",) if "xyz" in mods else ()) +      # what the loss consumes
-                      (("object_verts", "object_count", "scale", "original_pose3d") if args.chamfer_w > 0 else ())}
+                      (("object_verts", "object_count", "scale", "original_pose3d") if args.chamfer_w > 0 else ()) +
+                      (("hand_mask",) if args.sil_w > 0 else ())}
                 if graphed is None or graphed_lr != trainer.lr:
                     # (re-)capture: GraphedStep's warm-up pass is one real step on this batch - it IS this iteration (replaying the
                     # same batch as well would apply two optimizer steps to it and advance Adam's count and the BatchNorm buffers twice)
                     sx, sy = x.clone(), {k: v.clone() for k, v in yk.items()}
-                    graphed, graphed_lr = GraphedStep(trainer, sx, sy, N=args.hyps, mods=mods, chamfer_w=args.chamfer_w), trainer.lr
+                    graphed, graphed_lr = GraphedStep(trainer, sx, sy, N=args.hyps, mods=mods, chamfer_w=args.chamfer_w, sil_w=args.sil_w), trainer.lr
                     out = graphed.warm_out
                 else:
                     sx.copy_(x)
@@ -139,7 +149,7 @@ def main(argv=None):
                         sy[k].copy_(v)
                     out = graphed.replay()
             else:
-                out = trainer.step(x, y, N=args.hyps, test_samples=args.test_samples, mods=mods, chamfer_w=args.chamfer_w)
+                out = trainer.step(x, y, N=args.hyps, test_samples=args.test_samples, mods=mods, chamfer_w=args.chamfer_w, sil_w=args.sil_w)
             with torch.no_grad():
                 total, losses, metrics = criterion(dict(out), y)
             meters["loss"].update(float(total))

@@ -185,6 +185,23 @@ def object_targets(seed=0, B=2, VO=256, with_count=False):
     return y
 
 
+def hand_masks(seed=0, B=2, H=64, crop_uv=None, image_size=256, with_image=True):
+    """Seeded hand masks (B, H, H) bool for the silhouette term (get_loss(sil_w=...), criteria.silhouette_dist), taken from the same seed's
+    batch() target so that the mask lies where the hand is (a random blob would only drag the camera): the union of the discs of radius 0.08,
+    in normalised image coordinates, around the 21 keypoints of crop_uv.  Pixel (i, j) is the square of half-width 1/H around
+    ((2j+1)/H - 1, (2i+1)/H - 1) and is kept when it meets a disc, so every keypoint inside the frame lies on a kept pixel and no image is
+    empty.  crop_uv (B, 42): the target to use instead of drawing batch(seed, B, image_size, with_image) again (batch() draws the image first:
+    the two flags must be the ones of the batch the masks go with)."""
+    if crop_uv is None:
+        crop_uv = batch(seed, B, image_size=image_size, with_image=with_image)[1]["crop_uv"]
+    kp = np.asarray(crop_uv, np.float64).reshape(B, 21, 2)
+    c = (2.0 * np.arange(H) + 1.0) / H - 1.0
+    ax = np.maximum(np.abs(kp[:, :, 0, None] - c[None, None, :]) - 1.0 / H, 0.0)          # (B, 21, H): columns, u
+    ay = np.maximum(np.abs(kp[:, :, 1, None] - c[None, None, :]) - 1.0 / H, 0.0)          # rows, v
+    d2 = ay[:, :, :, None] ** 2 + ax[:, :, None, :] ** 2                                    # (B, 21, H, H)
+    return (d2 <= 0.08 ** 2).any(1)
+
+
 def structured_images(seed=0, B=2, image_size=256):
     """Images with image-to-image structure (a smooth random field per image: random 4x4 / 16x16 colour patterns bilinearly enlarged, a
     per-image gain and offset, a little pixel noise), in [-1,1].  batch()'s default images are i.i.d. white noise: after global average pooling

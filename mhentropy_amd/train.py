@@ -726,13 +726,16 @@ class TrainStep:
         self._grad_ready(0)
 
     # ------------------------------------------------------------------ the step
-    def forward(self, x, y, noise=None, N=None, trunk_out=None, mods=None, chamfer_w=None):
+    def forward(self, x, y, noise=None, N=None, trunk_out=None, mods=None, chamfer_w=None, sil_w=None):
         """forward of MHEnt.get_loss (hand/network.py:760-831) keeping what the reverse pass needs.  Returns the get_loss dict.
         trunk_out (B, feat_dim) f32 (testing aid): stands in for the ResNet trunk's output, whose forward and reverse
         passes are then skipped - the reference's golden gradients are pinned from the trunk feature on.
         mods: get_loss's likelihoods (None = ['uv']; ['xyz'] / ['xyz', 'uv'] read y['pose3d'], hand/CrossModalHand.py:354).
         chamfer_w: get_loss's weight of the hand-object Chamfer term (None: the model's chamfer_w; > 0 reads y['object_verts'], 'scale',
-        'original_pose3d' and, if present, 'object_count'; 0 launches what the step launched without the argument)."""
+        'original_pose3d' and, if present, 'object_count'; 0 launches what the step launched without the argument).
+        sil_w: get_loss's weight of the silhouette term (None: the model's sil_w; > 0 reads y['hand_mask']; 0 launches what the step launched
+        without the argument).  Between forward and reverse the term keeps z, the mesh (N*B x 778 x 3 f32) and the kept-pixel list; no index
+        tensor exists: the reverse re-evaluates both minima (ops.silhouette_dist_grad)."""
         m = self.model
         N = N or m.loss_N
         bits = ops.mods_bits(mods) if not isinstance(mods, int) else mods
@@ -740,6 +743,10 @@ class TrainStep:
             raise ValueError("TrainStep.forward(mods=[..., 'xyz']) needs the 3D target y['pose3d'] (B, 63)")
         cw, cham = m.chamfer_operands(y, chamfer_w)
         B = x.shape[0] if trunk_out is None else trunk_out.shape[0]
+        if self.shard_hypotheses and float(m.sil_w if sil_w is None else sil_w) > 0:
+            raise NotImplementedError("hypothesis sharding with sil_w > 0: the masks of the other ranks' images are not gathered")
+        sw, sil = m.sil_operands(y, sil_w, B)
+        want = ("log_p", "norms") + (("z",) if sil is not None else ())
         self.arena.sync()     # someone else (torch.optim, load_state_dict) may have written the parameters
         f = self._trunk_forward(x.contiguous()) if trunk_out is None else trunk_out.contiguous()
         feat, feat_b = ops.linear(f, self.l1["w"], self.l1["b"], want_bf16=True) if self.flow_bf16 else (ops.linear(f, self.l1["w"], self.l1["b"]), None)
@@ -765,15 +772,18 @@ class TrainStep:
         cu, vis = y["crop_uv"].contiguous() if bits & ops.MODS_UV else None, y["vis"].contiguous()
         p3 = y["pose3d"].contiguous().float() if bits & ops.MODS_XYZ else None
         if cham is not None:
-            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=("log_p", "norms"), pose3d=p3, mods=bits,
+            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=want, pose3d=p3, mods=bits,
                                 laplace_b_3d=m.b_3d, chamfer=cham)
         elif bits == ops.MODS_UV:
-            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=("log_p", "norms"))
+            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=want)
         else:
-            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=("log_p", "norms"), pose3d=p3, mods=bits,
+            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=want, pose3d=p3, mods=bits,
                                 laplace_b_3d=m.b_3d)
         q_log_p, hq, log_p = ops.elbo_reduce(o["log_p"], log_q if m.entropy else None, N, B)
         ch = ops.elbo_reduce(o["chamfer"], None, N, B)[0] if cham is not None else None      # mean over the (local) hypotheses
+        sil_verts = sil_logs_t = sl = None
+        if sil is not None:         # mesh of the loss pass' z, distance without index tensors, mean over the hypotheses
+            sil_verts, sil_logs_t, sl = m.silhouette_rows(o["z"], sil, N, B)
         if hs is not None:
             # means over the local hypotheses -> sums -> all-reduce -> means over all K; each rank reports its own images
             part = torch.stack([q_log_p, hq] + ([ch] if ch is not None else [])) * (float(N) / N_all)
@@ -790,8 +800,11 @@ class TrainStep:
         if ch is not None:
             out["chamfer"] = ch
             out["log_p"] = out["log_p"] - cw * ch
+        if sl is not None:
+            out["silhouette"] = sl
+            out["log_p"] = out["log_p"] - sw * sl
         self.tape = {"f": f, "feat": feat, "hd": hd, "det": det, "th45": th45, "blob": blob, "cu": cu, "vis": vis,
-                     "p3": p3, "mods": bits, "cham": cham, "chamfer_w": cw, "N": N, "B": B, "trunk": trunk_out is None, "hs": hs, "B_own": B_own, "N_all": N_all, "feat_own": feat_own}
+                     "p3": p3, "mods": bits, "cham": cham, "chamfer_w": cw, "sil": sil, "sil_w": sw, "z": o.get("z"), "sil_verts": sil_verts, "sil_logs_t": sil_logs_t, "N": N, "B": B, "trunk": trunk_out is None, "hs": hs, "B_own": B_own, "N_all": N_all, "feat_own": feat_own}
         return out
 
     def backward(self, g_log_p=None):
@@ -811,6 +824,8 @@ class TrainStep:
             g_logp.copy_(g_log_p.reshape(B))
         g45, gdet_rows = self._mano_bwd(th45, det, t["blob"], t["cu"], t["vis"], g_logp, N_all, t["p3"], t["mods"], t.get("cham"),
                                         t.get("chamfer_w", 0.0))
+        if t.get("sil") is not None:
+            self._sil_bwd(t, g_logp, g45, gdet_rows)
         self.part.reverse(th45, g45, g_logp if m.entropy else None, N, B, N_all)
         # det head: gdet [B,16] -> padded [B,32]
         gdet = self.arena.buf("gdet", (B, 32)); gdet.zero_()
@@ -837,9 +852,9 @@ class TrainStep:
             self.G.mul_(1.0 / self.world)
             self._G_averaged = True        # optimizer_step() must not divide by world a second time
 
-    def forward_backward(self, x, y, noise=None, N=None, trunk_out=None, mods=None, chamfer_w=None):
+    def forward_backward(self, x, y, noise=None, N=None, trunk_out=None, mods=None, chamfer_w=None, sil_w=None):
         """forward + reverse pass of total = mean_b(-log_p[b]); fills self.G.  Returns the get_loss dict + 'total'."""
-        out = self.forward(x, y, noise=noise, N=N, trunk_out=trunk_out, mods=mods, chamfer_w=chamfer_w)
+        out = self.forward(x, y, noise=noise, N=N, trunk_out=trunk_out, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
         self.backward()
         out["total"] = -out["log_p"].mean()
         return out
@@ -866,6 +881,16 @@ class TrainStep:
             ops.launch("mhe_mano_joints_mods_bwd_f32", th45, det, cu, vis, p3, blob, g_logp, g45, rows, R, B, int(mods), float(self.model.b_2d),
                        float(self.model.b_3d), float(self.model.th45_ref_alpha), 1.0 / N)
         return g45, rows
+
+    def _sil_bwd(self, t, g_logp, g45, gdet_rows):
+        """reverse of log_p[b] -= sil_w mean_n dist[n B + b]: g_dist[r] = -sil_w g_logp[b] / N (one elementwise launch), both minima
+        re-evaluated with the gradients in the same launch, the mesh's reverse to z, z's adjoint added to the loss pass' two buffers"""
+        N, B = t["N"], t["B"]
+        g_dist = self.arena.buf("g_sil_dist", (N, B))
+        torch.mul(g_logp.view(1, B).expand(N, B), -float(t["sil_w"]) / t.get("N_all", N), out=g_dist)
+        g_verts, g_logs_t = ops.silhouette_dist_grad(t["sil_verts"].view(N, B, 778, 3), t["sil_logs_t"].view(N, B, 3), *t["sil"], g_dist)
+        g_z = ops.mano_verts_bwd(t["z"], t["blob"], g_verts.view(N * B, 778, 3))
+        ops.mano_z_grad_add(g_z, g_logs_t.view(N * B, 3), g45, gdet_rows)
 
     def optimizer_step(self):
         """all-reduce (sum) over ranks, clip_grad_norm_(max_norm) and Adam in one fused pass"""
@@ -895,14 +920,14 @@ class TrainStep:
         torch._foreach_lerp_([u.bn.running_var for u in units], var, BN_MOMENTUM)
         torch._foreach_add_([u.bn.num_batches_tracked for u in units], 1)
 
-    def step(self, x, y, noise=None, N=None, test_samples=0, temp=0.8, double_bn_update=True, mods=None, chamfer_w=None):
+    def step(self, x, y, noise=None, N=None, test_samples=0, temp=0.8, double_bn_update=True, mods=None, chamfer_w=None, sil_w=None):
         """one iteration of the reference's training loop (hand/CrossModalHand.py:353-361,455-470).  test_samples > 0
         adds its per-iteration metrics pass `sample(N=[n,n], temp=0.8, mods={uv,xyz,verts})` to the returned dict,
         from the conditioning feature of THIS forward.  The reference runs the encoder a second time on the same
         batch in train mode for it: same feature, but the BatchNorm running statistics advance twice per iteration -
         double_bn_update=True (default) reproduces that on the buffers, so checkpoints / eval-mode results match a
-        reference-trained model.  mods, chamfer_w: get_loss's likelihoods and Chamfer weight, as in forward()."""
-        out = self.forward_backward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w)
+        reference-trained model.  mods, chamfer_w, sil_w: get_loss's likelihoods, Chamfer and silhouette weights, as in forward()."""
+        out = self.forward_backward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
         if test_samples:
             if double_bn_update and self.tape["trunk"]:
                 self.second_bn_update()
@@ -919,20 +944,21 @@ class GraphedStep:
     (RCCL, async_op: it runs on the communicator's stream under the next graph's kernels), the next graph starts; the last
     graph (norm, clip, Adam, operand re-pack) is launched after the waits.  Six graphs and four collectives per step."""
 
-    def __init__(self, ts, x, y, noise=None, N=None, test_samples=0, criterion=None, mods=None, chamfer_w=None):
+    def __init__(self, ts, x, y, noise=None, N=None, test_samples=0, criterion=None, mods=None, chamfer_w=None, sil_w=None):
         """test_samples / criterion: the reference's whole iteration (hand/CrossModalHand.py:349-361,452-470) in the graph - the
         metrics pass sample(N=[n,n], temp=0.8) from this forward's feature and `criterion(out, y)` (MHEntLoss: 14 metrics);
         self.out then carries 'criterion' = (total, losses, metrics).  mods: get_loss's likelihoods (TrainStep.forward); with 'xyz'
         the graphs read y['pose3d'] - a new target is copied into that static tensor like the rest of the batch.  chamfer_w > 0 (None: the
         model's): y['object_verts'], 'scale', 'original_pose3d' and 'object_count' are static inputs in the same way; the count's range is
-        checked on the host by the warm-up step only (a capturing stream takes no host read: the kernels clamp it to 1..VO)"""
+        checked on the host by the warm-up step only (a capturing stream takes no host read: the kernels clamp it to 1..VO).  sil_w > 0
+        (None: the model's): y['hand_mask'] is a static input too; its kept-pixel list is rebuilt inside the graph on every replay"""
         if ts.shard_hypotheses:
             raise NotImplementedError("GraphedStep: the hypothesis-sharded forward has collectives inside the forward pass")
         self.ts, self.graphs, self.actions = ts, [], []
         _step = ts.step
 
         def step(x, y, noise=None, N=None):
-            out = _step(x, y, noise=noise, N=N, test_samples=test_samples, mods=mods, chamfer_w=chamfer_w)
+            out = _step(x, y, noise=noise, N=N, test_samples=test_samples, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
             if criterion is not None:
                 with torch.no_grad():
                     out["criterion"] = criterion(dict(out), y)
@@ -989,8 +1015,8 @@ class GraphedStep:
 class _LossFn(torch.autograd.Function):
     """MHEnt.get_loss as one autograd node: forward = TrainStep.forward, backward = TrainStep.backward(d loss / d log_p)."""
     @staticmethod
-    def forward(ctx, trainer, x, y, N, noise, mods, chamfer_w, *params):
-        out = trainer.forward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w)
+    def forward(ctx, trainer, x, y, N, noise, mods, chamfer_w, sil_w, *params):
+        out = trainer.forward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
         ctx.trainer, ctx.keys = trainer, list(out)
         vals = tuple(out[k] for k in ctx.keys)
         ctx.mark_non_differentiable(*[v for k, v in zip(ctx.keys, vals) if k != "log_p"])
@@ -1001,13 +1027,15 @@ class _LossFn(torch.autograd.Function):
         tr = ctx.trainer
         g = grads[ctx.keys.index("log_p")]
         tr.backward(None if g is None else g.contiguous().float())
-        return (None, None, None, None, None, None, None) + tuple(tr.grad_of(p) for p in tr.arena.params)
+        return (None, None, None, None, None, None, None, None) + tuple(tr.grad_of(p) for p in tr.arena.params)
 
 
-def differentiable_get_loss(trainer, x, y, N=None, noise=None, mods=None, chamfer_w=None):
-    w, _ = trainer.model.chamfer_operands(y, chamfer_w)
-    vals = _LossFn.apply(trainer, x, y, N, noise, mods, w, *trainer.arena.params)
-    return dict(zip(_LossFn_keys(trainer) + (["chamfer"] if w > 0 else []), vals))
+def differentiable_get_loss(trainer, x, y, N=None, noise=None, mods=None, chamfer_w=None, sil_w=None):
+    m = trainer.model
+    w, _ = m.chamfer_operands(y, chamfer_w)
+    sw = float(m.sil_w if sil_w is None else sil_w)       # (forward checks it with the mask, before any launch)
+    vals = _LossFn.apply(trainer, x, y, N, noise, mods, w, sw, *trainer.arena.params)
+    return dict(zip(_LossFn_keys(trainer) + (["chamfer"] if w > 0 else []) + (["silhouette"] if sw > 0 else []), vals))
 
 
 def _LossFn_keys(trainer):
