@@ -521,6 +521,25 @@ int mhe_procrustes_align_f32(const float *pred, const float *target, float *out,
 int mhe_topk_gather_f32(const float *score, const float *rows, int *idx_out, float *rows_out,
                         int N, int B, int Q, int D, void *stream);
 
+/* k-means quantisation of a hypothesis set (the n-quantised-best-of-M protocol; csrc/kmeans.hip, DESIGN.md "k-means quantisation"): per
+ * image b the N points points[(n*B+b)*D ..] (sample-major [N,B,D]) are clustered into Q groups and each group is reported by one of its
+ * members.  score [N,B] or NULL (log q) picks the first seed.  All distances are sum_d (p_d - c_d)^2 in f32 in ascending d.
+ *   seeds: 0 = highest score, ties to the lower n (NULL: n = 0); k = the point farthest from its nearest earlier seed, ties to the lower n
+ *   at most `iters` Lloyd rounds: assign every point to its nearest centre (ties to the lower k); stop with converged = 1 when no
+ *     assignment changed (the first round always counts as changed); else every centre becomes the f32 mean of its members, summed in
+ *     ascending n; an emptied cluster keeps its centre.  Without a fixed point (iters = 0 included: the centres are the seed points) one
+ *     more assignment follows the last means, with converged = 0.
+ *   representative: the member nearest its centre, ties to the lower n; an empty cluster reports count 0 and the nearest of all N
+ *   order: count descending, ties to the lower representative (then to the lower seed number)
+ * index [Q,B] (hypothesis n), count [Q,B], assign [N,B] (the output slot 0..Q-1 of every point), centre [Q,B,D], converged [B].
+ * One workgroup per image with the image in LDS: mhe_kmeans_lds_bytes(N, Q, D) = 4 ((N + Q)(D | 1) + 2 N + 3 Q + 16) must not exceed
+ * mhe_kmeans_lds_limit() = 160 KiB, the LDS of one CU - MHE_ERR_ARG otherwise, there is no slower path.  Fixed summation order, no
+ * atomics: two calls give the same bits.  Every pointer must be device memory. */
+size_t mhe_kmeans_lds_limit(void);
+size_t mhe_kmeans_lds_bytes(int N, int Q, int D);
+int mhe_kmeans_select_f32(const float *points, const float *score, int *index, int *count, int *assign, float *centre,
+                          int *converged, int N, int B, int D, int Q, int iters, void *stream);
+
 /* ---- train step (hand/CrossModalHand.py:455-470: zero_grad; loss.backward(); clip; Adam) -------------
  * The reference differentiates the path with autograd; here every stage has a hand-written reverse
  * kernel.  Reverse of mhe_mano_joints_f32's log_p output: row r = n*B + b receives

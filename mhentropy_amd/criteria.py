@@ -4,7 +4,7 @@ block runs in one HIP kernel (csrc/metrics.hip), the Procrustes alignment of the
 evaluation in csrc/procrustes.hip.  chamfer_dist (hand/criteria.py:18-39) and the selection
 it was written for (chamfer_select) run on csrc/chamfer.hip; silhouette_iou scores the hypotheses' meshes against the image's hand mask
 on csrc/render.hip; silhouette_dist, the differentiable distance of the projected mesh to that mask, and silhouette_select run on
-csrc/silhouette.hip."""
+csrc/silhouette.hip; kmeans_select, which summarises the hypotheses by the representatives of Q k-means modes, runs on csrc/kmeans.hip."""
 import torch
 from torch import nn
 
@@ -220,6 +220,40 @@ def silhouette_select(output, target, Q=1, size=64):
     with torch.no_grad():
         dist = silhouette_dist(output["verts"].detach(), output["logs_t"].detach(), target["hand_mask"], size=size)
     return _cut(output, dist, Q, "silhouette")
+
+
+def kmeans_select(output, Q, points="xyz", iters=10, score=None):
+    """Summarise a sample() output by Q distinct, weighted hypotheses per image (the n-quantised-best-of-M protocol): the N hypotheses are
+    clustered by k-means on output[points] ('xyz', the joints, or 'verts', the mesh) and each cluster is kept as its member nearest the
+    cluster mean, largest cluster first (ops.kmeans_select; DESIGN.md "k-means quantisation" has the algorithm and its tie rules).  score:
+    an (N, B) tensor or the name of one in `output` (log q) - the first seed is the hypothesis of highest score, hypothesis 0 without it.
+    Every (N, B, ...) tensor of `output` is cut to (Q, B, ...) at the representatives; 'faces' and 'image' pass through.  Added:
+    'kmeans_index' (Q, B) int64, the hypotheses kept, 'kmeans_count' (Q, B) int64, the cluster sizes (their share of N is the weight of
+    each answer), 'kmeans_assign' (N, B) int32, the position in the output of every hypothesis' cluster, and 'kmeans_converged' (B,) int32."""
+    if points not in ("xyz", "verts"):
+        raise ValueError(f"kmeans_select: points={points!r} (xyz or verts)")
+    if points not in output:
+        raise ValueError(f"kmeans_select: output has no {points!r}")
+    src = output[points]
+    N, B = _select_shape("kmeans_select", points, src, Q)
+    if isinstance(score, str):
+        if score not in output:
+            raise ValueError(f"kmeans_select: output has no {score!r} to take the score from")
+        score = output[score]
+    if score is not None:
+        if not isinstance(score, torch.Tensor) or score.numel() != N * B or tuple(score.shape) not in ((N, B), (N * B,)):
+            raise ValueError(f"kmeans_select: score must be (N, B) = ({N}, {B}), got {tuple(getattr(score, 'shape', ()))}")
+        score = score.detach().reshape(N, B).float().contiguous()
+    with torch.no_grad():
+        km = ops.kmeans_select(src.detach().reshape(N, B, -1).float().contiguous(), Q, score=score, iters=iters)
+    keep, cols = km["index"], torch.arange(B, device=km["index"].device)
+    out = {}
+    for k, v in output.items():
+        cut = isinstance(v, torch.Tensor) and k not in ("faces", "image") and v.dim() >= 2 and tuple(v.shape[:2]) == (N, B)
+        out[k] = v[keep, cols] if cut else v
+    out["kmeans_index"], out["kmeans_count"] = keep, km["count"].long()
+    out["kmeans_assign"], out["kmeans_converged"] = km["assign"], km["converged"]
+    return out
 
 
 def silhouette_iou(verts, logs_t, faces, hand_mask, size=64):

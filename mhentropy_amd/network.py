@@ -268,14 +268,21 @@ class MHEnt(nn.Module):
         """reference hand/network.py:838-844."""
         return self.log_prob(y, x, div_type=div_type, mods=mods, return_dict=return_dict, **kw)
 
-    def sample(self, x, N: Union[int, list] = 5, temp=0.5, mods=None, y=None, noise=None, feat=None):
+    def sample(self, x, N: Union[int, list] = 5, temp=0.5, mods=None, y=None, noise=None, feat=None, quant="log_q", quant_iters=10):
         """reference hand/network.py:846-883 -> th_bt (N,B,58), logs_t (N,B,3), verts (N,B,2334),
         xyz (N,B,63), uv (N,B,42) in pixels, faces.  mods may also hold 'm' and / or 'depth' (hand/network.py:541-558): mask / depth
         (N,B,64,64) of every hypothesis' mesh through ManoLayer.render - camera exp(logs_t[0]), logs_t[1:], depth scaled by the normaliser
-        |J11 - J12| of the un-normalised joints.  The default mods (None) returns what it always did."""
+        |J11 - J12| of the un-normalised joints.  The default mods (None) returns what it always did.
+        quant: how N = [M, n] with n < M cuts the M hypotheses drawn to n.  'log_q' (default) is the reference's: the n most likely.
+        'kmeans' is the n-quantised-best-of-M protocol: the M hypotheses' normalised root-relative joints (a joints-only decode) are
+        clustered into n modes (ops.kmeans_select, seeded by log q, at most quant_iters Lloyd rounds), the member nearest each mode's mean
+        is kept and decoded, largest mode first; the result gains quant_index (n, B) int64, the hypotheses kept, and quant_count (n, B)
+        int64, the sizes of their modes.  With N an int or n == M it is ignored, as N_quant is."""
         N_quant = N
         if isinstance(N, (list, tuple)):
             N, N_quant = N
+        if quant not in ("log_q", "kmeans"):
+            raise ValueError(f"sample: quant={quant!r} (log_q or kmeans)")
         out = {}
         if y is not None and "image" in y:
             out["image"] = y["image"]
@@ -290,7 +297,14 @@ class MHEnt(nn.Module):
                 th45, log_q = self.q_z_giv_i.sample_with_log_prob(z0, feat)
             else:
                 th45 = self.q_z_giv_i.forward_p(z0, cond=feat)
-        if N_quant < N:         # keep the N_quant most likely hypotheses per image (network.py:866-871)
+        if N_quant < N and quant == "kmeans":       # keep one representative of each of N_quant modes per image
+            xyz = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(), inv_norm=True, image_size=float(self.image_size),
+                                  want=("xyz",))["xyz"]
+            km = ops.kmeans_select(xyz.view(N, B, 63), N_quant, score=log_q.view(N, B), iters=quant_iters)
+            th45 = th45.view(N, B, 45)[km["index"], torch.arange(B, device=th45.device)].reshape(N_quant * B, 45)
+            out["quant_index"], out["quant_count"] = km["index"], km["count"].long()
+            N = N_quant
+        elif N_quant < N:       # keep the N_quant most likely hypotheses per image (network.py:866-871)
             _, th45 = ops.topk_gather(log_q, th45, N, B, N_quant)
             N = N_quant
         mods = {"xyz", "uv", "verts"} if mods is None else set(mods)

@@ -586,6 +586,40 @@ def topk_gather(score, rows, N, B, Q):
     return idx, out
 
 
+def kmeans_select(points, Q, score=None, iters=10):
+    """k-means quantisation of a hypothesis set (include/mhe.h, mhe_kmeans_select_f32; DESIGN.md "k-means quantisation"): points [N,B,D]
+    sample-major, score [N,B] or None (log q: the first seed is the row of highest score, row 0 without it), at most `iters` Lloyd rounds
+    from farthest-point seeds.  Returns a dict: index [Q,B] int64 (each cluster's representative hypothesis, the member nearest the mean),
+    count [Q,B] int32, assign [N,B] int32 (every row's cluster, as a position in the output order), centre [Q,B,D] f32, converged [B]
+    int32.  Clusters come largest first.  One launch, one workgroup per image with the image in LDS: ValueError, before any launch, when
+    (N, Q, D) does not fit the 160 KiB of a CU (kmeans_lds_bytes), for Q outside 1..N and for iters < 0."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 3 or 0 in points.shape:
+        raise ValueError(f"kmeans_select.points: expected a non-empty [N,B,D] tensor, got {tuple(getattr(points, 'shape', ()))}")
+    N, B, D = points.shape
+    if not isinstance(Q, int) or isinstance(Q, bool) or not 1 <= Q <= N:
+        raise ValueError(f"kmeans_select: Q={Q!r} outside 1..N={N}")
+    if not isinstance(iters, int) or isinstance(iters, bool) or iters < 0:
+        raise ValueError(f"kmeans_select: iters={iters!r} (an int >= 0)")
+    need, limit = kmeans_lds_bytes(N, Q, D), _lib.lib().mhe_kmeans_lds_limit()
+    if need > limit:
+        raise ValueError(f"kmeans_select: N={N}, Q={Q}, D={D} needs {need} bytes of LDS, over the {limit} (160 KiB) of one CU; there is no slower path")
+    _chk(points, torch.float32, "kmeans_select.points")
+    if score is not None:
+        _chk(score, torch.float32, "kmeans_select.score", (N, B))
+    dev = points.device
+    index, count = (torch.empty(Q, B, device=dev, dtype=torch.int32) for _ in range(2))
+    assign = torch.empty(N, B, device=dev, dtype=torch.int32)
+    centre = torch.empty(Q, B, D, device=dev, dtype=torch.float32)
+    converged = torch.empty(B, device=dev, dtype=torch.int32)
+    launch("mhe_kmeans_select_f32", points, score, index, count, assign, centre, converged, N, B, D, Q, iters)
+    return {"index": index.long(), "count": count, "assign": assign, "centre": centre, "converged": converged}
+
+
+def kmeans_lds_bytes(N, Q, D):
+    """the LDS one workgroup of kmeans_select takes for N points and Q centres of D coordinates (mhe_kmeans_lds_bytes)"""
+    return int(_lib.lib().mhe_kmeans_lds_bytes(int(N), int(Q), int(D)))
+
+
 def metrics(xyz, uv, pose3d, scale, crop_uv, vis):
     N, B = xyz.shape[:2]
     _chk(xyz, torch.float32, "metrics.xyz", (N, B, 63)); _chk(uv, torch.float32, "metrics.uv", (N, B, 42))

@@ -8,6 +8,7 @@ on synthetic batches (no dataset ships with this repository; the HO3D pipeline i
     python -m mhentropy_amd.run --mods uv,xyz ...        # 3D-supervised training (hand/CrossModalHand.py:354, mods = ['xyz', 'uv'])
     python -m mhentropy_amd.run --chamfer-w 10 ...       # with the hand-object Chamfer term (hand/network.py:821-826, w_chamfer = 10)
     python -m mhentropy_amd.run --sil-w 1 ...            # with the silhouette term (the mesh against the hand mask, MHEnt.get_loss(sil_w=...))
+    python -m mhentropy_amd.run --test-samples 200 --quant-samples 10 --quant kmeans ...      # metrics of 10 k-means modes of 200 hypotheses
 """
 import argparse
 import json
@@ -27,6 +28,12 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=64, help="images per GPU (configs/ho3d.yaml: 64)")
     ap.add_argument("--hyps", type=int, default=10, help="hypotheses per image in the loss (the reference hard-codes 10)")
     ap.add_argument("--test-samples", type=int, default=0, help="per-iteration metrics pass, training.test_samples (reference: 200)")
+    ap.add_argument("--quant-samples", type=int, default=0,
+                    help="cut the --test-samples hypotheses of the metrics pass to this many before the metrics, sample(N=[test_samples, "
+                         "quant_samples]): the metrics are then quantised best-of-M (0: keep them all)")
+    ap.add_argument("--quant", default="log_q", choices=["log_q", "kmeans"],
+                    help="how --quant-samples cuts: log_q keeps the most likely hypotheses (the reference's N_quant), kmeans clusters the "
+                         "hypotheses' joints into that many modes and keeps one representative of each (MHEnt.sample(quant='kmeans'))")
     ap.add_argument("--hidden", type=int, default=512)
     ap.add_argument("--flow-steps", type=int, default=6)
     ap.add_argument("--dtype", default="bf16", choices=["f32", "bf16"])
@@ -67,6 +74,8 @@ def main(argv=None):
         raise SystemExit("--chamfer-w must be >= 0")
     if not args.sil_w >= 0:
         raise SystemExit("--sil-w must be >= 0")
+    if args.quant_samples < 0:
+        raise SystemExit("--quant-samples must be >= 0")
     from . import ops
     mods = [m.strip() for m in args.mods.split(",") if m.strip()]
     ops.mods_bits(mods)                               # NotImplementedError for anything but uv / xyz, before any work
@@ -76,6 +85,8 @@ def main(argv=None):
         args.backbone, args.hidden, args.flow_steps = cfg.network.backbone, cfg.network.h_dims[0], cfg.network.num_steps
         args.batch, args.lr, args.milestones = cfg.training.batch_size, cfg.training.lr, list(cfg.training.milestones)
         args.test_samples = cfg.training.get("test_samples", args.test_samples)
+    if args.quant_samples > args.test_samples:
+        raise SystemExit(f"--quant-samples {args.quant_samples} is more than the {args.test_samples} hypotheses of --test-samples")
 
     rank, local_rank, world, dist = mdist.init()
     if not torch.cuda.is_available():
@@ -149,7 +160,8 @@ def main(argv=None):
                         sy[k].copy_(v)
                     out = graphed.replay()
             else:
-                out = trainer.step(x, y, N=args.hyps, test_samples=args.test_samples, mods=mods, chamfer_w=args.chamfer_w, sil_w=args.sil_w)
+                out = trainer.step(x, y, N=args.hyps, test_samples=args.test_samples, mods=mods, chamfer_w=args.chamfer_w, sil_w=args.sil_w,
+                                   test_quant=args.quant_samples, quant=args.quant)
             with torch.no_grad():
                 total, losses, metrics = criterion(dict(out), y)
             meters["loss"].update(float(total))

@@ -920,20 +920,22 @@ class TrainStep:
         torch._foreach_lerp_([u.bn.running_var for u in units], var, BN_MOMENTUM)
         torch._foreach_add_([u.bn.num_batches_tracked for u in units], 1)
 
-    def step(self, x, y, noise=None, N=None, test_samples=0, temp=0.8, double_bn_update=True, mods=None, chamfer_w=None, sil_w=None):
+    def step(self, x, y, noise=None, N=None, test_samples=0, temp=0.8, double_bn_update=True, mods=None, chamfer_w=None, sil_w=None,
+             test_quant=0, quant="log_q"):
         """one iteration of the reference's training loop (hand/CrossModalHand.py:353-361,455-470).  test_samples > 0
         adds its per-iteration metrics pass `sample(N=[n,n], temp=0.8, mods={uv,xyz,verts})` to the returned dict,
         from the conditioning feature of THIS forward.  The reference runs the encoder a second time on the same
         batch in train mode for it: same feature, but the BatchNorm running statistics advance twice per iteration -
         double_bn_update=True (default) reproduces that on the buffers, so checkpoints / eval-mode results match a
-        reference-trained model.  mods, chamfer_w, sil_w: get_loss's likelihoods, Chamfer and silhouette weights, as in forward()."""
+        reference-trained model.  mods, chamfer_w, sil_w: get_loss's likelihoods, Chamfer and silhouette weights, as in forward().
+        test_quant (0: test_samples) and quant: the metrics pass is sample(N=[test_samples, test_quant], quant=quant)."""
         out = self.forward_backward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
         if test_samples:
             if double_bn_update and self.tape["trunk"]:
                 self.second_bn_update()
             with torch.no_grad():
-                out.update(self.model.sample(None, N=[test_samples, test_samples], temp=temp, mods={"uv", "xyz", "verts"}, y=y,
-                                             feat=self.tape["feat_own"]))
+                out.update(self.model.sample(None, N=[test_samples, test_quant or test_samples], temp=temp, mods={"uv", "xyz", "verts"}, y=y,
+                                             feat=self.tape["feat_own"], quant=quant))
         self.optimizer_step()
         return out
 
