@@ -957,6 +957,9 @@ class GraphedStep:
         if ts.shard_hypotheses:
             raise NotImplementedError("GraphedStep: the hypothesis-sharded forward has collectives inside the forward pass")
         self.ts, self.graphs, self.actions = ts, [], []
+        # the graphs hold the ADDRESSES of their static inputs; the step itself keeps no reference to x (the trunk keeps its NHWC copy only).
+        # A caller that passes a temporary (x.clone()) would leave the graphs reading a freed block that the next allocation may take.
+        self.static = (x, y, noise)
         _step = ts.step
 
         def step(x, y, noise=None, N=None):
