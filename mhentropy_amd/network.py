@@ -32,6 +32,7 @@ from . import ops, resnet
 from .ManoLayer import ManoLayer
 from .flows import RealNVP
 from .glow import ConditionalGlow
+from .loss_terms import LossTerms
 
 
 class BasicEnc(nn.Module):
@@ -206,20 +207,14 @@ class MHEnt(nn.Module):
         sil_w (None: self.sil_w) > 0: the silhouette term - out['silhouette'][b] = mean_n of criteria.silhouette_dist of row n*B+b's normalised
         mesh (ops.mano_verts(z), the 'verts' of sample()) under logs_t = z[:, 58:61] against y['hand_mask'][b] at grid size self.sil_size, and
         log_p -= sil_w * silhouette; the other keys are not touched by it.  Both terms may be on."""
-        bits = ops.mods_bits(mods)
-        if bits & ops.MODS_XYZ and "pose3d" not in y:
-            raise ValueError("get_loss(mods=[..., 'xyz']) needs the 3D target y['pose3d'] (B, 63)")
-        cw, cham = self.chamfer_operands(y, chamfer_w)
-        sw = float(self.sil_w if sil_w is None else sil_w)
         N = N or self.loss_N
         tr = getattr(self, "_trainer", None)
         if tr is not None and self.training and torch.is_grad_enabled():
             # a train.TrainStep is attached: the loss dict comes out as ONE autograd node whose backward is the
             # hand-written reverse pass, so the reference's `total_loss.backward()` works unchanged
             from .train import differentiable_get_loss
-            return differentiable_get_loss(tr, x, y, N=N, noise=noise, mods=bits, chamfer_w=cw, sil_w=sw)
-        sw, sil = self.sil_operands(y, sw, None if x is None else x.shape[0])
-        want = ("log_p", "norms") + (("z",) if sil is not None else ())
+            return differentiable_get_loss(tr, x, y, N=N, noise=noise, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
+        terms = LossTerms(self, y, mods, chamfer_w, sil_w, None if x is None else x.shape[0])      # every host check, then the kept-pixel launch
         _, feat, _ = self.feat_extractor(x)
         B = feat.shape[0]
         if isinstance(self.q_z_giv_i, ConditionalGlow):      # entropy from the sampling pass itself (network.py:781-783,798-799)
@@ -231,32 +226,7 @@ class MHEnt(nn.Module):
             z0 = self._noise(N * B, 1.0, noise, feat.device)
             th45 = self.q_z_giv_i.forward_p(z0, cond=feat)
             log_q = self.q_z_giv_i.log_prob(th45, logvar=feat) if self.entropy else None       # network.py:801
-        if cham is not None:
-            o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(),
-                                y["crop_uv"].contiguous() if bits & ops.MODS_UV else None, y["vis"].contiguous(), self.b_2d,
-                                self.th45_ref_alpha, want=want, mods=bits, laplace_b_3d=self.b_3d, chamfer=cham,
-                                pose3d=y["pose3d"].contiguous().float() if bits & ops.MODS_XYZ else None)
-        elif bits == ops.MODS_UV:
-            o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(), y["crop_uv"].contiguous(),
-                                y["vis"].contiguous(), self.b_2d, self.th45_ref_alpha, want=want)
-        else:
-            o = ops.mano_joints(th45, self._det(feat), self.mano_dec.table_blob(),
-                                y["crop_uv"].contiguous() if bits & ops.MODS_UV else None, y["vis"].contiguous(), self.b_2d,
-                                self.th45_ref_alpha, want=want, pose3d=y["pose3d"].contiguous().float(), mods=bits,
-                                laplace_b_3d=self.b_3d)
-        q_log_p, h, log_p = ops.elbo_reduce(o["log_p"], log_q, N, B)
-        out = {"th_norm": o["norms"][:, 0], "bt_norm": o["norms"][:, 1], "q_log_p_z_giv_y": q_log_p}
-        if self.entropy:
-            out["h_q_z_giv_i"] = h
-            out["log_p"] = log_p
-        else:
-            out["log_p"] = q_log_p
-        if cham is not None:
-            out["chamfer"] = ops.elbo_reduce(o["chamfer"], None, N, B)[0]          # mean over the N hypotheses
-            out["log_p"] = out["log_p"] - cw * out["chamfer"]
-        if sil is not None:
-            out["silhouette"] = self.silhouette_rows(o["z"], sil, N, B)[2]
-            out["log_p"] = out["log_p"] - sw * out["silhouette"]
+        out = terms.reduce(terms.joints(th45, self._det(feat), self.mano_dec.table_blob()), log_q, N, B)
         if not return_dict:
             raise NotImplementedError
         return out

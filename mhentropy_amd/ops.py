@@ -435,48 +435,40 @@ def mano_joints(th45, det, tables, crop_uv=None, vis=None, laplace_b=0.03, th45_
     if pose3d is not None:
         _chk(pose3d, torch.float32, "mano.pose3d", (B, 63))
     bits = None if mods is None else (int(mods) if isinstance(mods, int) else mods_bits(mods))
+    mesh = [k for k in ("verts", "mesh_mm") if k in want]
     if chamfer is not None:
         VO = _chamfer_target(chamfer, B, "mano.chamfer")
         if vis is None:
             raise ValueError("mano_joints(chamfer=...): vis is required")
-        if "verts" in want or "mesh_mm" in want:
-            raise ValueError("mano_joints: the mesh outputs come from the uv-only pass (mods=None, chamfer=None)")
         bits = MODS_UV if bits is None else bits
-        shapes = {"z": (R, 61), "xyz": (R, 63), "uv": (R, 42), "terms": (R, 5), "log_p": (R,), "norms": (R, 2), "joints_mm": (R, 63)}
-        o = {k: (torch.empty(shapes[k], device=dev, dtype=torch.float32) if k in want else None) for k in shapes}
-        o["chamfer"] = torch.empty(R, device=dev, dtype=torch.float32)
-        launch("mhe_mano_joints_chamfer_f32", th45, det, crop_uv, vis, pose3d, tables, *chamfer, o["z"], o["xyz"], o["uv"], o["terms"], o["log_p"],
-               o["norms"], o["joints_mm"], o["chamfer"], R, B, VO, bits, float(laplace_b), float(laplace_b_3d), float(th45_alpha), int(inv_norm),
-               float(image_size))
-        return o
+    if mesh and bits is not None:
+        raise ValueError("mano_joints: the mesh outputs come from the uv-only pass (mods=None" + (")" if chamfer is None else ", chamfer=None)"))
+    if len(mesh) > 1:
+        raise ValueError("mano_joints: 'verts' or 'mesh_mm', one mesh per call")
     shapes = {"z": (R, 61), "xyz": (R, 63), "uv": (R, 42), "terms": (R, 4 if bits is None else 5), "log_p": (R,), "norms": (R, 2),
               "joints_mm": (R, 63)}
     o = {k: (torch.empty(shapes[k], device=dev, dtype=torch.float32) if k in want else None) for k in shapes}
-    if bits is not None:
-        if "verts" in want or "mesh_mm" in want:
-            raise ValueError("mano_joints: the mesh outputs come from the uv-only pass (mods=None)")
-        launch("mhe_mano_joints_mods_f32", th45, det, crop_uv, vis, pose3d, tables, o["z"], o["xyz"], o["uv"], o["terms"], o["log_p"], o["norms"], o["joints_mm"], R,
-               B, bits, float(laplace_b), float(laplace_b_3d), float(th45_alpha), int(inv_norm), float(image_size))
-        return o
-    if "verts" in want or "mesh_mm" in want:
-        if "verts" in want and "mesh_mm" in want:
-            raise ValueError("mano_joints: 'verts' or 'mesh_mm', one mesh per call")
-        key = "verts" if "verts" in want else "mesh_mm"
-        o[key] = torch.empty(R, 778, 3, device=dev, dtype=torch.float32)
+    outs = tuple(o.values())
+    lb, lb3, alpha, tail = float(laplace_b), float(laplace_b_3d), float(th45_alpha), (int(inv_norm), float(image_size))
+    # the four entries of the pass, each with its argument list: Chamfer target > likelihood bit set > mesh decode > the 4-term uv pass
+    if chamfer is not None:
+        o["chamfer"] = torch.empty(R, device=dev, dtype=torch.float32)
+        entry, args = "mhe_mano_joints_chamfer_f32", (th45, det, crop_uv, vis, pose3d, tables, *chamfer, *outs, o["chamfer"], R, B, VO, bits, lb, lb3, alpha, *tail)
+    elif bits is not None:
+        entry, args = "mhe_mano_joints_mods_f32", (th45, det, crop_uv, vis, pose3d, tables, *outs, R, B, bits, lb, lb3, alpha, *tail)
+    elif mesh:
+        o[mesh[0]] = torch.empty(R, 778, 3, device=dev, dtype=torch.float32)
         ws = torch.empty(_lib.lib().mhe_mano_verts_workspace_floats(R), device=dev, dtype=torch.float32)
-        launch("mhe_mano_decode_f32", th45, det, crop_uv, vis, tables, o["z"], o["xyz"], o["uv"], o["terms"], o["log_p"], o["norms"], o["joints_mm"], o[key], ws, R,
-               B, float(laplace_b), float(th45_alpha), int(inv_norm), float(image_size), int(key == "mesh_mm"))
-        return o
-    launch("mhe_mano_joints_f32", th45, det, crop_uv, vis, tables, o["z"], o["xyz"], o["uv"], o["terms"], o["log_p"], o["norms"], o["joints_mm"], R, B,
-           float(laplace_b), float(th45_alpha), int(inv_norm), float(image_size))
+        entry, args = "mhe_mano_decode_f32", (th45, det, crop_uv, vis, tables, *outs, o[mesh[0]], ws, R, B, lb, alpha, *tail, int(mesh[0] == "mesh_mm"))
+    else:
+        entry, args = "mhe_mano_joints_f32", (th45, det, crop_uv, vis, tables, *outs, R, B, lb, alpha, *tail)
+    launch(entry, *args)
     return o
 
 
-def mano_joints_bwd(th45, det, tables, crop_uv, vis, g_log_p, N, laplace_b=0.03, th45_alpha=50.0, pose3d=None, mods=None,
-                    laplace_b_3d=0.03, chamfer=None, chamfer_w=0.0):
-    """reverse of mano_joints' log_p: (d/d th45 [R,45], d/d det [B,16]) for d loss/d log_p[n*B+b] = g_log_p[b]/N;
-    mods / pose3d / laplace_b_3d as in mano_joints (crop_uv may be None when 'uv' is off).
-    chamfer (as in mano_joints) with chamfer_w: the reverse of log_p[r] - chamfer_w * chamfer[r] (mhe_mano_joints_chamfer_bwd_f32)"""
+def mano_joints_bwd_rows(th45, det, tables, crop_uv, vis, g_log_p, N, g_th45, g_rows, laplace_b=0.03, th45_alpha=50.0, pose3d=None, mods=None,
+                         laplace_b_3d=0.03, chamfer=None, chamfer_w=0.0):
+    """mano_joints_bwd into the caller's g_th45 [R,45] and g_rows [R,16]: d/d det stays one row per hypothesis -> (g_th45, g_rows)"""
     R, B = th45.shape[0], det.shape[0]
     _chk(th45, torch.float32, "mano_bwd.th45", (R, 45)); _chk(det, torch.float32, "mano_bwd.det", (B, 16))
     if crop_uv is not None or mods is None:
@@ -485,20 +477,28 @@ def mano_joints_bwd(th45, det, tables, crop_uv, vis, g_log_p, N, laplace_b=0.03,
     if pose3d is not None:
         _chk(pose3d, torch.float32, "mano_bwd.pose3d", (B, 63))
     _chk(g_log_p, torch.float32, "mano_bwd.g_log_p", (B,))
-    g_th45 = torch.empty(R, 45, device=th45.device, dtype=torch.float32)
-    g_rows = torch.empty(R, 16, device=th45.device, dtype=torch.float32)
+    _chk(g_th45, torch.float32, "mano_bwd.g_th45", (R, 45)); _chk(g_rows, torch.float32, "mano_bwd.g_rows", (R, 16))
+    bits = None if mods is None else (int(mods) if isinstance(mods, int) else mods_bits(mods))
+    lb, lb3, alpha = float(laplace_b), float(laplace_b_3d), float(th45_alpha)
     if chamfer is not None:
         VO = _chamfer_target(chamfer, B, "mano_bwd.chamfer")
-        bits = MODS_UV if mods is None else (int(mods) if isinstance(mods, int) else mods_bits(mods))
-        launch("mhe_mano_joints_chamfer_bwd_f32", th45, det, crop_uv, vis, pose3d, tables, *chamfer, g_log_p, g_th45, g_rows, R, B, VO, bits,
-               float(laplace_b), float(laplace_b_3d), float(th45_alpha), 1.0 / N, float(chamfer_w))
-    elif mods is None:
-        launch("mhe_mano_joints_bwd_f32", th45, det, crop_uv, vis, tables, g_log_p, g_th45, g_rows, R, B, float(laplace_b), float(th45_alpha), 1.0 / N)
+        launch("mhe_mano_joints_chamfer_bwd_f32", th45, det, crop_uv, vis, pose3d, tables, *chamfer, g_log_p, g_th45, g_rows, R, B, VO,
+               MODS_UV if bits is None else bits, lb, lb3, alpha, 1.0 / N, float(chamfer_w))
+    elif bits is None:
+        launch("mhe_mano_joints_bwd_f32", th45, det, crop_uv, vis, tables, g_log_p, g_th45, g_rows, R, B, lb, alpha, 1.0 / N)
     else:
-        bits = int(mods) if isinstance(mods, int) else mods_bits(mods)
-        launch("mhe_mano_joints_mods_bwd_f32", th45, det, crop_uv, vis, pose3d, tables, g_log_p, g_th45, g_rows, R, B, bits, float(laplace_b), float(laplace_b_3d),
-               float(th45_alpha), 1.0 / N)
-    return g_th45, sum_over_hypotheses(g_rows, N, B)
+        launch("mhe_mano_joints_mods_bwd_f32", th45, det, crop_uv, vis, pose3d, tables, g_log_p, g_th45, g_rows, R, B, bits, lb, lb3, alpha, 1.0 / N)
+    return g_th45, g_rows
+
+
+def mano_joints_bwd(th45, det, tables, crop_uv, vis, g_log_p, N, laplace_b=0.03, th45_alpha=50.0, pose3d=None, mods=None,
+                    laplace_b_3d=0.03, chamfer=None, chamfer_w=0.0):
+    """reverse of mano_joints' log_p: (d/d th45 [R,45], d/d det [B,16]) for d loss/d log_p[n*B+b] = g_log_p[b]/N;
+    mods / pose3d / laplace_b_3d as in mano_joints (crop_uv may be None when 'uv' is off).
+    chamfer (as in mano_joints) with chamfer_w: the reverse of log_p[r] - chamfer_w * chamfer[r] (mhe_mano_joints_chamfer_bwd_f32)"""
+    g_th45, g_rows = (torch.empty(th45.shape[0], c, device=th45.device, dtype=torch.float32) for c in (45, 16))
+    mano_joints_bwd_rows(th45, det, tables, crop_uv, vis, g_log_p, N, g_th45, g_rows, laplace_b, th45_alpha, pose3d, mods, laplace_b_3d, chamfer, chamfer_w)
+    return g_th45, sum_over_hypotheses(g_rows, N, det.shape[0])
 
 
 def sum_over_hypotheses(rows, N, B, out=None, accumulate=False, out_stride=0):

@@ -9,7 +9,7 @@ with total_loss = mean_b(-log_p[b]) (hand/criteria.py:55,173).
 There is no autograd graph here: `TrainStep` runs the forward of MHEnt.get_loss stage by stage keeping
 what the reverse pass needs (raw convolution outputs, post-activation tensors, BatchNorm batch
 statistics, the flow sample), then walks the stages backwards through hand-written reverse kernels:
-    loss -> MANO likelihood (mhe_mano_joints_bwd_f32; with the hand-object Chamfer term mhe_mano_joints_chamfer_bwd_f32) -> RealNVP couplings (re-evaluated layer by layer,
+    loss -> MANO likelihood and the optional terms of the call (loss_terms.LossTerms.joints_bwd) -> RealNVP couplings (re-evaluated layer by layer,
     csrc/flow_bwd.hip + mhe_conv_wgrad_nhwc) -> conditioning / det-head / l1 dense layers -> ResNet trunk
     (data gradients through the forward implicit-GEMM kernel on transposed, tap-flipped weights; weight
     gradients through mhe_conv_wgrad_nhwc; train-mode BatchNorm reverse) -> clip + Adam (one fused pass).
@@ -24,6 +24,7 @@ import torch
 
 from . import ops, resnet
 from .arena import OperandArena, _ceil
+from .loss_terms import LossTerms
 from .resnet import BN_EPS, BN_MOMENTUM
 from .train_flow import RealNVPPart, flow_stream_table  # noqa: F401  (flow_stream_table: named as train.flow_stream_table by its test)
 
@@ -738,15 +739,8 @@ class TrainStep:
         tensor exists: the reverse re-evaluates both minima (ops.silhouette_dist_grad)."""
         m = self.model
         N = N or m.loss_N
-        bits = ops.mods_bits(mods) if not isinstance(mods, int) else mods
-        if bits & ops.MODS_XYZ and "pose3d" not in y:
-            raise ValueError("TrainStep.forward(mods=[..., 'xyz']) needs the 3D target y['pose3d'] (B, 63)")
-        cw, cham = m.chamfer_operands(y, chamfer_w)
         B = x.shape[0] if trunk_out is None else trunk_out.shape[0]
-        if self.shard_hypotheses and float(m.sil_w if sil_w is None else sil_w) > 0:
-            raise NotImplementedError("hypothesis sharding with sil_w > 0: the masks of the other ranks' images are not gathered")
-        sw, sil = m.sil_operands(y, sil_w, B)
-        want = ("log_p", "norms") + (("z",) if sil is not None else ())
+        terms = LossTerms(m, y, mods, chamfer_w, sil_w, B, who="TrainStep.forward", sharded=self.shard_hypotheses)
         self.arena.sync()     # someone else (torch.optim, load_state_dict) may have written the parameters
         f = self._trunk_forward(x.contiguous()) if trunk_out is None else trunk_out.contiguous()
         feat, feat_b = ops.linear(f, self.l1["w"], self.l1["b"], want_bf16=True) if self.flow_bf16 else (ops.linear(f, self.l1["w"], self.l1["b"]), None)
@@ -758,9 +752,7 @@ class TrainStep:
             hs = HypothesisShards(self.dist, N)
             feat_own, feat = feat, hs.gather_rows(feat)                       # (world*B, 512): every image's conditioning feature
             feat_b = None
-            y = {k: hs.gather_rows(y[k]) for k in ("crop_uv", "vis") + (("pose3d",) if bits & ops.MODS_XYZ else ())}
-            if cham is not None:       # the object targets of every image: (scale, root, vertices, count) rows, rank-major like the features
-                cham = tuple(None if t is None else hs.gather_rows(t) for t in cham)
+            terms.gather(hs)
             if noise is not None:
                 noise = hs.gather_hypothesis_rows(noise.reshape(N * B, 45), B)
             lo, hi = hs.hypotheses()
@@ -769,42 +761,19 @@ class TrainStep:
         det = ops.linear(hd, self.d2["w"], self.d2["b"])[:, :16].contiguous()
         th45, log_q = self.part.sample(feat, feat_b, N, B, noise, lambda nz: m._noise(N * B, 1.0, nz, self.dev))
         blob = m.mano_dec.table_blob()
-        cu, vis = y["crop_uv"].contiguous() if bits & ops.MODS_UV else None, y["vis"].contiguous()
-        p3 = y["pose3d"].contiguous().float() if bits & ops.MODS_XYZ else None
-        if cham is not None:
-            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=want, pose3d=p3, mods=bits,
-                                laplace_b_3d=m.b_3d, chamfer=cham)
-        elif bits == ops.MODS_UV:
-            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=want)
-        else:
-            o = ops.mano_joints(th45, det, blob, cu, vis, m.b_2d, m.th45_ref_alpha, want=want, pose3d=p3, mods=bits,
-                                laplace_b_3d=m.b_3d)
-        q_log_p, hq, log_p = ops.elbo_reduce(o["log_p"], log_q if m.entropy else None, N, B)
-        ch = ops.elbo_reduce(o["chamfer"], None, N, B)[0] if cham is not None else None      # mean over the (local) hypotheses
-        sil_verts = sil_logs_t = sl = None
-        if sil is not None:         # mesh of the loss pass' z, distance without index tensors, mean over the hypotheses
-            sil_verts, sil_logs_t, sl = m.silhouette_rows(o["z"], sil, N, B)
+        o = terms.joints(th45, det, blob)
+        share = None
         if hs is not None:
-            # means over the local hypotheses -> sums -> all-reduce -> means over all K; each rank reports its own images
-            part = torch.stack([q_log_p, hq] + ([ch] if ch is not None else [])) * (float(N) / N_all)
-            hs.reduce_images(part)
-            own = slice(hs.rank * B_own, (hs.rank + 1) * B_own)
-            q_log_p, hq = part[0, own].contiguous(), part[1, own].contiguous()
-            log_p = hq + q_log_p
-            if ch is not None:
-                ch = part[2, own].contiguous()
-        out = {"th_norm": o["norms"][:, 0], "bt_norm": o["norms"][:, 1], "q_log_p_z_giv_y": q_log_p,
-               "log_p": log_p if m.entropy else q_log_p}
-        if m.entropy:
-            out["h_q_z_giv_i"] = hq
-        if ch is not None:
-            out["chamfer"] = ch
-            out["log_p"] = out["log_p"] - cw * ch
-        if sl is not None:
-            out["silhouette"] = sl
-            out["log_p"] = out["log_p"] - sw * sl
-        self.tape = {"f": f, "feat": feat, "hd": hd, "det": det, "th45": th45, "blob": blob, "cu": cu, "vis": vis,
-                     "p3": p3, "mods": bits, "cham": cham, "chamfer_w": cw, "sil": sil, "sil_w": sw, "z": o.get("z"), "sil_verts": sil_verts, "sil_logs_t": sil_logs_t, "N": N, "B": B, "trunk": trunk_out is None, "hs": hs, "B_own": B_own, "N_all": N_all, "feat_own": feat_own}
+            def share(q_log_p, hq, ch):
+                # means over the local hypotheses -> sums -> all-reduce -> means over all K; each rank reports its own images
+                part = torch.stack([q_log_p, hq] + ([ch] if ch is not None else [])) * (float(N) / N_all)
+                hs.reduce_images(part)
+                own = slice(hs.rank * B_own, (hs.rank + 1) * B_own)
+                return part[0, own].contiguous(), part[1, own].contiguous(), None if ch is None else part[2, own].contiguous()
+        out = terms.reduce(o, log_q if m.entropy else None, N, B, share)
+        self.tape = {"f": f, "feat": feat, "hd": hd, "det": det, "th45": th45, "blob": blob, "terms": terms, "sil": terms.sil, "z": o.get("z"),
+                     "sil_verts": terms.sil_verts, "sil_logs_t": terms.sil_logs_t, "N": N, "B": B, "trunk": trunk_out is None, "hs": hs, "B_own": B_own,
+                     "N_all": N_all, "feat_own": feat_own}
         return out
 
     def backward(self, g_log_p=None):
@@ -812,7 +781,7 @@ class TrainStep:
         total = mean_b(-log_p[b]) (hand/criteria.py:55,173); fills self.G."""
         m, t = self.model, self.tape
         N, B, f, feat, hd, det, th45 = t["N"], t["B"], t["f"], t["feat"], t["hd"], t["det"], t["th45"]
-        hs, B_own, N_all = t.get("hs"), t.get("B_own", B), t.get("N_all", N)
+        hs, B_own, N_all = t["hs"], t["B_own"], t["N_all"]
         self._wq = []                   # (a reverse pass that raised half way must not leave its queued weight gradients to the next one)
         self.raw.zero_()
         g_logp = self.arena.buf("g_logp", (B,))
@@ -822,9 +791,9 @@ class TrainStep:
             g_logp.copy_(hs.gather_rows(g_log_p.reshape(B_own).contiguous()))
         else:
             g_logp.copy_(g_log_p.reshape(B))
-        g45, gdet_rows = self._mano_bwd(th45, det, t["blob"], t["cu"], t["vis"], g_logp, N_all, t["p3"], t["mods"], t.get("cham"),
-                                        t.get("chamfer_w", 0.0))
-        if t.get("sil") is not None:
+        g45, gdet_rows = t["terms"].joints_bwd(th45, det, t["blob"], g_logp, N_all,
+                                               out=(self.arena.buf("g45", (N * B, 45)), self.arena.buf("gdet_rows", (N * B, 16))))
+        if t["sil"] is not None:
             self._sil_bwd(t, g_logp, g45, gdet_rows)
         self.part.reverse(th45, g45, g_logp if m.entropy else None, N, B, N_all)
         # det head: gdet [B,16] -> padded [B,32]
@@ -868,26 +837,12 @@ class TrainStep:
         self.model._trainer = self
         return self
 
-    def _mano_bwd(self, th45, det, blob, cu, vis, g_logp, N, p3=None, mods=ops.MODS_UV, cham=None, chamfer_w=0.0):
-        R, B = th45.shape[0], det.shape[0]
-        g45 = self.arena.buf("g45", (R, 45)); rows = self.arena.buf("gdet_rows", (R, 16))
-        if cham is not None:
-            ops.launch("mhe_mano_joints_chamfer_bwd_f32", th45, det, cu, vis, p3, blob, *cham, g_logp, g45, rows, R, B, cham[2].shape[1], int(mods),
-                       float(self.model.b_2d), float(self.model.b_3d), float(self.model.th45_ref_alpha), 1.0 / N, float(chamfer_w))
-        elif mods == ops.MODS_UV:
-            ops.launch("mhe_mano_joints_bwd_f32", th45, det, cu, vis, blob, g_logp, g45, rows, R, B, float(self.model.b_2d), float(self.model.th45_ref_alpha),
-                       1.0 / N)
-        else:
-            ops.launch("mhe_mano_joints_mods_bwd_f32", th45, det, cu, vis, p3, blob, g_logp, g45, rows, R, B, int(mods), float(self.model.b_2d),
-                       float(self.model.b_3d), float(self.model.th45_ref_alpha), 1.0 / N)
-        return g45, rows
-
     def _sil_bwd(self, t, g_logp, g45, gdet_rows):
         """reverse of log_p[b] -= sil_w mean_n dist[n B + b]: g_dist[r] = -sil_w g_logp[b] / N (one elementwise launch), both minima
         re-evaluated with the gradients in the same launch, the mesh's reverse to z, z's adjoint added to the loss pass' two buffers"""
         N, B = t["N"], t["B"]
         g_dist = self.arena.buf("g_sil_dist", (N, B))
-        torch.mul(g_logp.view(1, B).expand(N, B), -float(t["sil_w"]) / t.get("N_all", N), out=g_dist)
+        torch.mul(g_logp.view(1, B).expand(N, B), -t["terms"].sil_w / t["N_all"], out=g_dist)
         g_verts, g_logs_t = ops.silhouette_dist_grad(t["sil_verts"].view(N, B, 778, 3), t["sil_logs_t"].view(N, B, 3), *t["sil"], g_dist)
         g_z = ops.mano_verts_bwd(t["z"], t["blob"], g_verts.view(N * B, 778, 3))
         ops.mano_z_grad_add(g_z, g_logs_t.view(N * B, 3), g45, gdet_rows)
@@ -1032,16 +987,11 @@ class _LossFn(torch.autograd.Function):
         tr = ctx.trainer
         g = grads[ctx.keys.index("log_p")]
         tr.backward(None if g is None else g.contiguous().float())
-        return (None, None, None, None, None, None, None, None) + tuple(tr.grad_of(p) for p in tr.arena.params)
+        params = tr.arena.params
+        return (None,) * (len(ctx.needs_input_grad) - len(params)) + tuple(tr.grad_of(p) for p in params)     # one per input of forward
 
 
 def differentiable_get_loss(trainer, x, y, N=None, noise=None, mods=None, chamfer_w=None, sil_w=None):
-    m = trainer.model
-    w, _ = m.chamfer_operands(y, chamfer_w)
-    sw = float(m.sil_w if sil_w is None else sil_w)       # (forward checks it with the mask, before any launch)
-    vals = _LossFn.apply(trainer, x, y, N, noise, mods, w, sw, *trainer.arena.params)
-    return dict(zip(_LossFn_keys(trainer) + (["chamfer"] if w > 0 else []) + (["silhouette"] if sw > 0 else []), vals))
-
-
-def _LossFn_keys(trainer):
-    return ["th_norm", "bt_norm", "q_log_p_z_giv_y", "log_p"] + (["h_q_z_giv_i"] if trainer.model.entropy else [])
+    terms = LossTerms(trainer.model, y, mods, chamfer_w, sil_w, pixels=False)     # (forward checks the mask and lists its pixels, before any other launch)
+    vals = _LossFn.apply(trainer, x, y, N, noise, *terms.weights().values(), *trainer.arena.params)
+    return dict(zip(terms.keys(), vals))
