@@ -1114,6 +1114,30 @@ int mhe_silhouette_dist_bwd_f32(const float *verts, const float *logs_t, const i
  *   excepted), a shape out of range (as above), or outputs overlapping inputs or each other. */
 int mhe_silhouette_dist_grad_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const float *g_dist, float *dist,
                                  float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream);
+/* The same distance with an occluder mask (the object a hand holds): a pixel of the occluder is one where the mesh MAY project but need not.
+ * It excuses vertices and attracts nothing.  Per image b, M_b as above and O_b = the grid pixels whose occluder box mean is >= 0.5 and that
+ * are not in M_b, row-major:
+ *     inside[r] = (1/V) sum_v min_{m in M_b u O_b} box(p_v, c_m)     (0 inside the hand or the occluder)
+ *     cover[r]  = (1/|M_b|) sum_{m in M_b} min_v |c_m - p_v|          (unchanged: only hand pixels ask to be covered)
+ * mhe_silhouette_pixels_occ: mask and occluder [B,H,H], each bytes or f32 (mask_is_float, occluder_is_float) -> ONE list pixels [B,S*S]: M_b
+ *   first, then O_b, then the -1 tail (S*S ints suffice: the two sets are disjoint); count [B] = |M_b|, count_all [B] = |M_b| + |O_b|.  One
+ *   launch, one workgroup per image, two prefix sums (the occluder's offset by the hand total).  An all-zero occluder gives the pixels and
+ *   count of mhe_silhouette_pixels and count_all = count.
+ * mhe_silhouette_dist_occ_f32 / _dist_bwd_occ_f32 / _dist_grad_occ_f32: the three entries above with count_all [B] (not NULL) after count.
+ *   With M = count[b] clamped to 0 .. S^2 and M2 = count_all[b] clamped to M .. S^2: the vertices' minima run over list positions [0, M2),
+ *   the pixels' over [0, M); idx_v lies in [0, M2), idx_m keeps its rows [0, M) and -1 beyond.  Ties go to the lowest list position: at equal
+ *   distance a hand pixel wins over an occluder pixel.  The gradient of inside toward a chosen occluder pixel is the box gradient, as toward
+ *   a hand pixel.  M = 0: dist = inside = cover = 0, idx_v = -1 and zero gradients whatever O_b holds - an image with no visible hand teaches
+ *   nothing.  A non-finite projected vertex: NaN and zero gradients, as above.  count_all = count gives the bits of the entries above, in
+ *   every output.  Everything else - checks, determinism, no host read of either count - as above. */
+int mhe_silhouette_pixels_occ(const void *mask, int mask_is_float, const void *occluder, int occluder_is_float, int *pixels, int *count, int *count_all,
+                              int B, int H, int S, void *stream);
+int mhe_silhouette_dist_occ_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *count_all, float *dist,
+                                float *parts, int *idx_v, int *idx_m, int N, int B, int V, int S, void *stream);
+int mhe_silhouette_dist_bwd_occ_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *count_all, const int *idx_v,
+                                    const int *idx_m, const float *g_dist, float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream);
+int mhe_silhouette_dist_grad_occ_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *count_all,
+                                     const float *g_dist, float *dist, float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream);
 
 #ifdef __cplusplus
 }

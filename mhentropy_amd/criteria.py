@@ -149,8 +149,18 @@ def silhouette_mask_checks(hand_mask, B, size, who="silhouette_dist"):
         raise ValueError(f"{who}: hand_mask is {H} x {H}, not a multiple of size={size}")
 
 
-def _silhouette_operands(verts, logs_t, hand_mask, size):
-    """the checks of silhouette_dist that need no device -> (verts [N,B,V,3], logs_t [N,B,3], hand_mask [B,H,H], size)"""
+def silhouette_occluder_checks(occluder, hand_mask, who="silhouette_dist"):
+    """the occluder's shape checks, after the mask's: (B, H, H) like hand_mask -> the occluder, contiguous, bool / uint8 / float32 (any other
+    type is converted as the mask is)"""
+    if not isinstance(occluder, torch.Tensor) or occluder.dim() != 3 or tuple(occluder.shape) != tuple(hand_mask.shape):
+        raise ValueError(f"{who}: occluder must be (B, H, H) = {tuple(hand_mask.shape)} like hand_mask, got {tuple(getattr(occluder, 'shape', ()))}")
+    if occluder.dtype not in (torch.bool, torch.uint8, torch.float32):
+        occluder = occluder.float()
+    return occluder.contiguous()
+
+
+def _silhouette_operands(verts, logs_t, hand_mask, size, occluder=None):
+    """the checks of silhouette_dist that need no device -> (verts [N,B,V,3], logs_t [N,B,3], hand_mask [B,H,H], size, occluder [B,H,H] | None)"""
     who = "silhouette_dist"
     if not isinstance(verts, torch.Tensor) or verts.dim() not in (3, 4) or (verts.dim() == 4 and verts.shape[-1] != 3) or verts[0, 0].numel() % 3:
         raise ValueError(f"{who}: verts must be (N, B, V*3) or (N, B, V, 3), got {tuple(getattr(verts, 'shape', ()))}")
@@ -161,31 +171,35 @@ def _silhouette_operands(verts, logs_t, hand_mask, size):
     if not isinstance(logs_t, torch.Tensor) or tuple(logs_t.shape) != (N, B, 3):
         raise ValueError(f"{who}: logs_t must be (N, B, 3) = ({N}, {B}, 3), got {tuple(getattr(logs_t, 'shape', ()))}")
     silhouette_mask_checks(hand_mask, B, size, who)
+    if occluder is not None:
+        occluder = silhouette_occluder_checks(occluder, hand_mask, who)
     if hand_mask.dtype not in (torch.bool, torch.uint8, torch.float32):
         hand_mask = hand_mask.float()
-    return verts.reshape(N, B, V, 3).float().contiguous(), logs_t.float().contiguous(), hand_mask.contiguous(), size
+    return verts.reshape(N, B, V, 3).float().contiguous(), logs_t.float().contiguous(), hand_mask.contiguous(), size, occluder
 
 
 class _Silhouette(torch.autograd.Function):
     """(dist, parts) of ops.silhouette_dist; the gradient of dist reaches verts and logs_t (parts is returned for reading only).  The argmin
-    buffers are asked for only when one of them requires grad."""
+    buffers are asked for only when one of them requires grad.  count_all (None: no occluder section) is saved next to count."""
     @staticmethod
-    def forward(ctx, verts, logs_t, pixels, count):
+    def forward(ctx, verts, logs_t, pixels, count, count_all):
+        ctx.occ = count_all is not None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            dist, parts, idx_v, idx_m = ops.silhouette_dist(verts, logs_t, pixels, count, want_idx=True)
-            ctx.save_for_backward(verts, logs_t, pixels, count, idx_v, idx_m)
+            dist, parts, idx_v, idx_m = ops.silhouette_dist(verts, logs_t, pixels, count, want_idx=True, count_all=count_all)
+            ctx.save_for_backward(verts, logs_t, pixels, count, idx_v, idx_m, *((count_all,) if ctx.occ else ()))
         else:
-            dist, parts = ops.silhouette_dist(verts, logs_t, pixels, count)
+            dist, parts = ops.silhouette_dist(verts, logs_t, pixels, count, count_all=count_all)
         ctx.mark_non_differentiable(parts)
         return dist, parts
 
     @staticmethod
     def backward(ctx, g_dist, _g_parts):
-        g_verts, g_logs_t = ops.silhouette_dist_bwd(*ctx.saved_tensors, g_dist.contiguous())
-        return g_verts, g_logs_t, None, None
+        saved = ctx.saved_tensors
+        g_verts, g_logs_t = ops.silhouette_dist_bwd(*saved[:6], g_dist.contiguous(), count_all=saved[6] if ctx.occ else None)
+        return g_verts, g_logs_t, None, None, None
 
 
-def silhouette_dist(verts, logs_t, hand_mask, size=64, parts=False):
+def silhouette_dist(verts, logs_t, hand_mask, size=64, parts=False, occluder=None):
     """Distance of every hypothesis' projected mesh to its image's hand mask: verts (N, B, V*3) or (N, B, V, 3) and logs_t (N, B, 3) =
     (log s, tx, ty) of a sample() output, hand_mask (B, H, H) bool or float in [0, 1] (the input pipeline's target['hand_mask']) -> (N, B)
     f32; with parts=True (dist, inside, cover).  In the normalised image coordinates of silhouette_iou (pixel (i, j) of the size x size grid is
@@ -200,25 +214,39 @@ def silhouette_dist(verts, logs_t, hand_mask, size=64, parts=False):
     pixel count: the call can be captured into a HIP graph.  HIP tensors only (MheError otherwise); ValueError for a bad rank or shape, H not
     a multiple of size, V outside 1..778.  The reverse of the mesh exists (ManoLayer.verts carries the gradient on to z: ops.mano_verts_bwd), and
     the training term is MHEnt.get_loss(sil_w=...): log_p -= sil_w * mean_n of this distance, whose reverse (ops.silhouette_dist_grad) holds the
-    argmins in registers and LDS instead of the two index tensors this function's autograd node keeps."""
-    v, lt, mask, size = _silhouette_operands(verts, logs_t, hand_mask, size)
-    pixels, count = ops.silhouette_pixels(mask, size)
-    dist, pt = _Silhouette.apply(v, lt, pixels, count)
+    argmins in registers and LDS instead of the two index tensors this function's autograd node keeps.
+    occluder (B, H, H) with the mask's H, bool / uint8 / float (the input pipeline's target['object_mask']): the object in front of the hand.
+    Its kept pixels that are not hand pixels are where the mesh MAY project but need not: inside takes its minimum over the hand's and the
+    occluder's pixels (a vertex behind the object costs 0, and is pulled toward the object no more than toward the hand), cover stays the mean
+    over the hand's pixels alone (the occluder attracts nothing).  At equal distance the hand pixel is chosen.  An image with no hand pixel
+    gives 0 and a zero gradient whatever the occluder holds; an all-zero occluder gives the bits of occluder=None.  ValueError for an
+    occluder of another rank, B or H, before any launch."""
+    v, lt, mask, size, occ = _silhouette_operands(verts, logs_t, hand_mask, size, occluder)
+    lists = ops.silhouette_pixels(mask, size, occ)
+    dist, pt = _Silhouette.apply(v, lt, lists[0], lists[1], lists[2] if occ is not None else None)
     return (dist, pt[..., 0], pt[..., 1]) if parts else dist
 
 
-def silhouette_select(output, target, Q=1, size=64):
+def silhouette_select(output, target, Q=1, size=64, occluder=False):
     """chamfer_select with silhouette_dist: keep, per image, the Q hypotheses of a sample() output whose mesh (output['verts'] under
     output['logs_t']) lies closest to target['hand_mask'], closest first, ties to the lower n.  Every (N, B, ...) tensor of `output` is cut
-    to (Q, B, ...); 'faces' and 'image' pass through.  Added: 'silhouette' (Q, B), the distances, and 'silhouette_index' (Q, B) int64."""
+    to (Q, B, ...); 'faces' and 'image' pass through.  Added: 'silhouette' (Q, B), the distances, and 'silhouette_index' (Q, B) int64.
+    occluder: True reads target['object_mask'] (ValueError when it is absent), a tensor is used as given - silhouette_dist's occluder, so a
+    hypothesis is not ranked down for the fingers it puts behind the object."""
     for k in ("verts", "logs_t"):
         if k not in output:
             raise ValueError(f"silhouette_select: output has no {k!r}")
     if "hand_mask" not in target:
         raise ValueError("silhouette_select: target has no 'hand_mask'")
+    if occluder is True:
+        if "object_mask" not in target:
+            raise ValueError("silhouette_select(occluder=True): target has no 'object_mask'")
+        occluder = target["object_mask"]
+    elif occluder is False:
+        occluder = None
     N, B = _select_shape("silhouette_select", "verts", output["verts"], Q)
     with torch.no_grad():
-        dist = silhouette_dist(output["verts"].detach(), output["logs_t"].detach(), target["hand_mask"], size=size)
+        dist = silhouette_dist(output["verts"].detach(), output["logs_t"].detach(), target["hand_mask"], size=size, occluder=occluder)
     return _cut(output, dist, Q, "silhouette")
 
 

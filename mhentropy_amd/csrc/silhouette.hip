@@ -4,6 +4,9 @@
 // The contract is written at the declarations in include/mhe.h.  f32 pair evaluations, squared distances compared and one square root per
 // minimum, ties to the lowest index; every sum runs in a fixed order in f64 (a thread's own terms, the wave's butterfly, the four waves in
 // order) and nothing is atomic: two launches give the same bits.  The pixel count never leaves the device.
+// With an occluder (the _occ entries): O_b = the kept pixels of the occluder mask that are not in M_b, listed behind M_b in the same list
+// (count = |M_b|, count_all = |M_b| + |O_b|).  inside takes its minimum over M_b u O_b - a vertex on the occluder costs 0 - and cover stays
+// the mean over M_b alone: the occluder excuses vertices and attracts nothing.  |M_b| = 0 is the empty list whatever O_b holds.
 #include "common.h"
 
 namespace mhe { namespace silhouette {
@@ -35,12 +38,7 @@ __device__ __forceinline__ float box_sq(float px, float py, const float2 &c, flo
 // count as 0 / 1) and keeps it when 2 sum >= k^2, i.e. mean >= 0.5; the workgroup's exclusive prefix sum of the threads' counts fixes where
 // a thread's pixels go.  The list's tail is -1.
 template <typename T>
-__global__ __launch_bounds__(NT) void pixels_kernel(const T *__restrict__ mask, int *__restrict__ pixels, int *__restrict__ count, int H, int S) {
-    __shared__ int wtot[NW];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
-    const int P = S * S, per = (P + NT - 1) / NT, k = H / S;
-    const int p0 = min(P, tid * per), p1 = min(P, p0 + per);
-    const T *img = mask + (size_t)b * H * H;
+__device__ __forceinline__ unsigned kept_bits(const T *img, int H, int S, int k, int p0, int p1) {
     const double half = 0.5 * (double)k * (double)k;
     unsigned keep = 0;
     for (int p = p0; p < p1; ++p) {
@@ -52,13 +50,38 @@ __global__ __launch_bounds__(NT) void pixels_kernel(const T *__restrict__ mask, 
         }
         if (s >= half) keep |= 1u << (p - p0);
     }
-    const int mine = __popc(keep);
+    return keep;
+}
+
+// inclusive prefix sum of `mine` over the wave's lanes
+__device__ __forceinline__ int wave_incl(int mine, int lane) {
     int incl = mine;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
         const int up = __shfl_up(incl, o, 64);
         if (lane >= o) incl += up;
     }
+    return incl;
+}
+
+// a thread's kept pixels to the list from position off on; returns the position behind them
+__device__ __forceinline__ int put_pixels(int *out, int off, unsigned keep, int p0, int p1, int S) {
+    for (int p = p0; p < p1; ++p)
+        if (keep >> (p - p0) & 1u) {
+            const int i = p / S;
+            out[off++] = (i << 16) | (p - i * S);
+        }
+    return off;
+}
+
+template <typename T>
+__global__ __launch_bounds__(NT) void pixels_kernel(const T *__restrict__ mask, int *__restrict__ pixels, int *__restrict__ count, int H, int S) {
+    __shared__ int wtot[NW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    const int P = S * S, per = (P + NT - 1) / NT, k = H / S;
+    const int p0 = min(P, tid * per), p1 = min(P, p0 + per);
+    const unsigned keep = kept_bits(mask + (size_t)b * H * H, H, S, k, p0, p1);
+    const int mine = __popc(keep), incl = wave_incl(mine, lane);
     if (lane == 63) wtot[wave] = incl;
     __syncthreads();
     int off = incl - mine, total = 0;
@@ -68,13 +91,36 @@ __global__ __launch_bounds__(NT) void pixels_kernel(const T *__restrict__ mask, 
         total += wtot[w];
     }
     int *out = pixels + (size_t)b * P;
-    for (int p = p0; p < p1; ++p)
-        if (keep >> (p - p0) & 1u) {
-            const int i = p / S;
-            out[off++] = (i << 16) | (p - i * S);
-        }
+    put_pixels(out, off, keep, p0, p1, S);
     for (int q = total + tid; q < P; q += NT) out[q] = -1;
     if (tid == 0) count[b] = total;
+}
+
+// The two-mask form: the hand's kept pixels M_b, then the occluder's that are not the hand's (O_b), then the -1 tail - two prefix sums, the
+// occluder's offset by the hand total.  The sections are disjoint, so count_all <= S^2 and the list keeps its S^2 ints.
+template <typename T, typename U>
+__global__ __launch_bounds__(NT) void pixels_occ_kernel(const T *__restrict__ mask, const U *__restrict__ occ, int *__restrict__ pixels,
+                                                        int *__restrict__ count, int *__restrict__ count_all, int H, int S) {
+    __shared__ int wtot[2][NW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    const int P = S * S, per = (P + NT - 1) / NT, k = H / S;
+    const int p0 = min(P, tid * per), p1 = min(P, p0 + per);
+    const unsigned keep = kept_bits(mask + (size_t)b * H * H, H, S, k, p0, p1);
+    const unsigned okeep = kept_bits(occ + (size_t)b * H * H, H, S, k, p0, p1) & ~keep;
+    const int mine = __popc(keep), omine = __popc(okeep), incl = wave_incl(mine, lane), oincl = wave_incl(omine, lane);
+    if (lane == 63) { wtot[0][wave] = incl; wtot[1][wave] = oincl; }
+    __syncthreads();
+    int off = incl - mine, ooff = oincl - omine, total = 0, ototal = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        if (w < wave) { off += wtot[0][w]; ooff += wtot[1][w]; }
+        total += wtot[0][w]; ototal += wtot[1][w];
+    }
+    int *out = pixels + (size_t)b * P;
+    put_pixels(out, off, keep, p0, p1, S);
+    put_pixels(out, total + ooff, okeep, p0, p1, S);
+    for (int q = total + ototal + tid; q < P; q += NT) out[q] = -1;
+    if (tid == 0) { count[b] = total; count_all[b] = total + ototal; }
 }
 
 // min over the image's M kept pixels (LDS, every lane reads the same centre: a broadcast) for K vertices held in registers
@@ -185,20 +231,26 @@ __device__ __forceinline__ float2 row_parts(const double (*red)[NW], int V, int 
     return make_float2(I, Cv);
 }
 
+// The end of the image's list for the mesh -> mask scan: M (the hand section) without an occluder; with one, count_all clamped to M .. S^2 -
+// and 0 with no hand pixel: such an image is the empty list whatever its occluder holds.
+__device__ __forceinline__ int list_end(const int *count_all, int b, int M, int P) {
+    return count_all && M ? min(max(count_all[b], M), P) : M;
+}
+
 // Forward, one workgroup per row r = n B + b.  The row's vertices are projected once (registers of their thread, and LDS for the cover
 // direction), the image's kept pixels are decoded once into LDS as centres; both directional minima are taken from LDS.  The count is
 // clamped to 0 .. S^2 before it bounds anything.  A non-finite projected vertex makes the row NaN (the flag, not the minima, carries it:
 // fminf would drop the NaN); an empty list makes it 0.
 template <bool IDX>
 __global__ __launch_bounds__(NT) void dist_kernel(const float *__restrict__ verts, const float *__restrict__ logs_t, const int *__restrict__ pixels,
-                                                  const int *__restrict__ count, float *__restrict__ dist, float *__restrict__ parts,
-                                                  int *__restrict__ idx_v, int *__restrict__ idx_m, int B, int V, int S) {
+                                                  const int *__restrict__ count, const int *__restrict__ count_all, float *__restrict__ dist,
+                                                  float *__restrict__ parts, int *__restrict__ idx_v, int *__restrict__ idx_m, int B, int V, int S) {
     __shared__ float2 pc[PMAX];
     __shared__ float2 pv[KV * NT];
     __shared__ double red[2][NW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t r = blockIdx.x;
-    const int b = (int)(r % (size_t)B), P = S * S, M = min(max(count[b], 0), P);
+    const int b = (int)(r % (size_t)B), P = S * S, M = min(max(count[b], 0), P), M2 = list_end(count_all, b, M, P);
     const float fS = (float)S, h = 1.f / fS;
     const float es = expf(logs_t[r * 3]), tx = logs_t[r * 3 + 1], ty = logs_t[r * 3 + 2];
 
@@ -218,12 +270,12 @@ __global__ __launch_bounds__(NT) void dist_kernel(const float *__restrict__ vert
             pv[v] = make_float2(px[k], py[k]);
         }
     }
-    for (int m = tid; m < M; m += NT) pc[m] = centre(pixels[(size_t)b * P + m], fS);
+    for (int m = tid; m < M2; m += NT) pc[m] = centre(pixels[(size_t)b * P + m], fS);
     bad = __syncthreads_or(bad);
 
     // mesh -> mask
     switch ((V + NT - 1) / NT) {
-#define MHE_CASE(K) case K: scan_pixels<IDX, K>(pc, M, h, px, py, m1, i1); break;
+#define MHE_CASE(K) case K: scan_pixels<IDX, K>(pc, M2, h, px, py, m1, i1); break;
         MHE_CASE(1) MHE_CASE(2) MHE_CASE(3) MHE_CASE(4)
 #undef MHE_CASE
     }
@@ -282,15 +334,15 @@ __global__ __launch_bounds__(NT) void dist_kernel(const float *__restrict__ vert
 // its range contributes nothing and is never used as an address.  u(0) = 0.  A row with a non-finite projected vertex, or of an image with
 // an empty list, gets zeros.
 __global__ __launch_bounds__(NT) void dist_bwd_kernel(const float *__restrict__ verts, const float *__restrict__ logs_t, const int *__restrict__ pixels,
-                                                      const int *__restrict__ count, const int *__restrict__ idx_v, const int *__restrict__ idx_m,
-                                                      const float *__restrict__ g_dist, float *__restrict__ g_verts, float *__restrict__ g_logs_t, int B,
-                                                      int V, int S) {
+                                                      const int *__restrict__ count, const int *__restrict__ count_all,
+                                                      const int *__restrict__ idx_v, const int *__restrict__ idx_m, const float *__restrict__ g_dist,
+                                                      float *__restrict__ g_verts, float *__restrict__ g_logs_t, int B, int V, int S) {
     __shared__ int pk[PMAX];
     __shared__ int ti[PMAX];
     __shared__ double red[3][NW];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t r = blockIdx.x;
-    const int b = (int)(r % (size_t)B), P = S * S, M = min(max(count[b], 0), P);
+    const int b = (int)(r % (size_t)B), P = S * S, M = min(max(count[b], 0), P), M2 = list_end(count_all, b, M, P);
     const float fS = (float)S, h = 1.f / fS;
     const float es = expf(logs_t[r * 3]), tx = logs_t[r * 3 + 1], ty = logs_t[r * 3 + 2];
 
@@ -307,7 +359,10 @@ __global__ __launch_bounds__(NT) void dist_bwd_kernel(const float *__restrict__ 
             bad |= !(isfinite(px[k]) && isfinite(py[k]));
         }
     }
-    for (int m = tid; m < M; m += NT) { pk[m] = pixels[(size_t)b * P + m]; ti[m] = idx_m[r * P + m]; }
+    for (int m = tid; m < M2; m += NT) {
+        pk[m] = pixels[(size_t)b * P + m];
+        if (m < M) ti[m] = idx_m[r * P + m];
+    }
     bad = __syncthreads_or(bad);
     if (bad || M == 0) {
 #pragma unroll
@@ -330,7 +385,7 @@ __global__ __launch_bounds__(NT) void dist_bwd_kernel(const float *__restrict__ 
         if (v < V) {
             float ux = 0.f, uy = 0.f;
             const int iv = idx_v[r * V + v];
-            if ((unsigned)iv < (unsigned)M) box_unit(px[k], py[k], centre(pk[iv], fS), h, ux, uy);
+            if ((unsigned)iv < (unsigned)M2) box_unit(px[k], py[k], centre(pk[iv], fS), h, ux, uy);
             finish_vertex(ux, uy, gx[k], gy[k], gd, wV, wM, es, vx[k], vy[k], g_verts + (r * V + v) * 3, s_l, s_x, s_y);
         }
     }
@@ -345,8 +400,9 @@ __global__ __launch_bounds__(NT) void dist_bwd_kernel(const float *__restrict__ 
 // list in the rounds of the forward, and after the barrier the owners walk that list as dist_bwd_kernel walks idx_m.  The centres the walk
 // needs are the decoded ones of the forward.  dist may be null.
 __global__ __launch_bounds__(NT) void dist_grad_kernel(const float *__restrict__ verts, const float *__restrict__ logs_t, const int *__restrict__ pixels,
-                                                       const int *__restrict__ count, const float *__restrict__ g_dist, float *__restrict__ dist,
-                                                       float *__restrict__ g_verts, float *__restrict__ g_logs_t, int B, int V, int S) {
+                                                       const int *__restrict__ count, const int *__restrict__ count_all,
+                                                       const float *__restrict__ g_dist, float *__restrict__ dist, float *__restrict__ g_verts,
+                                                       float *__restrict__ g_logs_t, int B, int V, int S) {
     __shared__ float2 pc[PMAX];
     __shared__ float2 pv[KV * NT];
     __shared__ unsigned short lv[PMAX];
@@ -355,7 +411,7 @@ __global__ __launch_bounds__(NT) void dist_grad_kernel(const float *__restrict__
     static_assert(VMAX <= 0xffff, "a listed vertex is 16 bits");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t r = blockIdx.x;
-    const int b = (int)(r % (size_t)B), P = S * S, M = min(max(count[b], 0), P);
+    const int b = (int)(r % (size_t)B), P = S * S, M = min(max(count[b], 0), P), M2 = list_end(count_all, b, M, P);
     const float fS = (float)S, h = 1.f / fS;
     const float es = expf(logs_t[r * 3]), tx = logs_t[r * 3 + 1], ty = logs_t[r * 3 + 2];
 
@@ -376,7 +432,7 @@ __global__ __launch_bounds__(NT) void dist_grad_kernel(const float *__restrict__
             pv[v] = make_float2(px[k], py[k]);
         }
     }
-    for (int m = tid; m < M; m += NT) pc[m] = centre(pixels[(size_t)b * P + m], fS);
+    for (int m = tid; m < M2; m += NT) pc[m] = centre(pixels[(size_t)b * P + m], fS);
     bad = __syncthreads_or(bad);
     if (bad || M == 0) {
 #pragma unroll
@@ -391,7 +447,7 @@ __global__ __launch_bounds__(NT) void dist_grad_kernel(const float *__restrict__
 
     // mesh -> mask: (min, argmin) of the thread's own vertices
     switch ((V + NT - 1) / NT) {
-#define MHE_CASE(K) case K: scan_pixels<true, K>(pc, M, h, px, py, m1, i1); break;
+#define MHE_CASE(K) case K: scan_pixels<true, K>(pc, M2, h, px, py, m1, i1); break;
         MHE_CASE(1) MHE_CASE(2) MHE_CASE(3) MHE_CASE(4)
 #undef MHE_CASE
     }
@@ -486,58 +542,135 @@ extern "C" int mhe_silhouette_pixels(const void *mask, int mask_is_float, int *p
     return check_launch("silhouette::pixels_kernel");
 }
 
-extern "C" int mhe_silhouette_dist_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, float *dist, float *parts, int *idx_v,
-                                       int *idx_m, int N, int B, int V, int S, void *stream) {
-    if (int st = silhouette_args("mhe_silhouette_dist_f32", verts, logs_t, pixels, count, N, B, V, S)) return st;
-    MHE_REQUIRE(dist, "mhe_silhouette_dist_f32: null pointer (dist)");
+template <typename T>
+static void launch_pixels_occ(const T *mask, const void *occ, int occ_is_float, int *pixels, int *count, int *count_all, int B, int H, int S, void *stream) {
+    if (occ_is_float)
+        hipLaunchKernelGGL((silhouette::pixels_occ_kernel<T, float>), dim3((unsigned)B), dim3(silhouette::NT), 0, (hipStream_t)stream, mask,
+                           (const float *)occ, pixels, count, count_all, H, S);
+    else
+        hipLaunchKernelGGL((silhouette::pixels_occ_kernel<T, unsigned char>), dim3((unsigned)B), dim3(silhouette::NT), 0, (hipStream_t)stream, mask,
+                           (const unsigned char *)occ, pixels, count, count_all, H, S);
+}
+
+extern "C" int mhe_silhouette_pixels_occ(const void *mask, int mask_is_float, const void *occluder, int occluder_is_float, int *pixels, int *count,
+                                         int *count_all, int B, int H, int S, void *stream) {
+    MHE_REQUIRE(mask && occluder && pixels && count && count_all, "mhe_silhouette_pixels_occ: null pointer");
+    MHE_REQUIRE((mask_is_float == 0 || mask_is_float == 1) && (occluder_is_float == 0 || occluder_is_float == 1),
+                "mhe_silhouette_pixels_occ: mask_is_float=%d occluder_is_float=%d (0: bytes, 1: f32)", mask_is_float, occluder_is_float);
+    MHE_REQUIRE(B > 0, "mhe_silhouette_pixels_occ: B=%d", B);
+    MHE_REQUIRE(S >= 1 && S <= silhouette::SMAX, "mhe_silhouette_pixels_occ: S=%d (S in 1..%d)", S, silhouette::SMAX);
+    MHE_REQUIRE(H >= S && H % S == 0 && H <= MHE_SILHOUETTE_MAX_MASK, "mhe_silhouette_pixels_occ: H=%d (a multiple of S=%d, at most %d)", H, S,
+                MHE_SILHOUETTE_MAX_MASK);
+    const size_t px = (size_t)B * H * H, nc = (size_t)B * 4;
+    struct { const void *p; size_t n; } in[2] = {{mask, px * (mask_is_float ? 4 : 1)}, {occluder, px * (occluder_is_float ? 4 : 1)}},
+                                        out[3] = {{pixels, (size_t)B * S * S * 4}, {count, nc}, {count_all, nc}};
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 2; ++i)
+            MHE_REQUIRE(disjoint(out[o].p, out[o].n, in[i].p, in[i].n), "mhe_silhouette_pixels_occ: output %d overlaps input %d", o, i);
+        for (int q = 0; q < o; ++q)
+            MHE_REQUIRE(disjoint(out[o].p, out[o].n, out[q].p, out[q].n), "mhe_silhouette_pixels_occ: outputs %d and %d overlap", q, o);
+    }
+    if (mask_is_float)
+        launch_pixels_occ((const float *)mask, occluder, occluder_is_float, pixels, count, count_all, B, H, S, stream);
+    else
+        launch_pixels_occ((const unsigned char *)mask, occluder, occluder_is_float, pixels, count, count_all, B, H, S, stream);
+    return check_launch("silhouette::pixels_occ_kernel");
+}
+
+// The three distance entries and their _occ forms share their bodies: count_all is null for the former (occ = false) and required for the latter.
+static int dist_call(const char *who, bool occ, const float *verts, const float *logs_t, const int *pixels, const int *count, const int *count_all,
+                     float *dist, float *parts, int *idx_v, int *idx_m, int N, int B, int V, int S, void *stream) {
+    if (int st = silhouette_args(who, verts, logs_t, pixels, count, N, B, V, S)) return st;
+    MHE_REQUIRE(dist, "%s: null pointer (dist)", who);
+    MHE_REQUIRE(!occ || count_all, "%s: null pointer (count_all)", who);
     const size_t R = (size_t)N * B, P = (size_t)S * S;
-    struct { const void *p; size_t n; } in[4] = {{verts, R * V * 12}, {logs_t, R * 12}, {pixels, (size_t)B * P * 4}, {count, (size_t)B * 4}},
+    struct { const void *p; size_t n; } in[5] = {{verts, R * V * 12}, {logs_t, R * 12}, {pixels, (size_t)B * P * 4}, {count, (size_t)B * 4},
+                                                 {count_all, (size_t)B * 4}},
                                         out[4] = {{dist, R * 4}, {parts, R * 8}, {idx_v, R * V * 4}, {idx_m, R * P * 4}};
     for (int o = 0; o < 4; ++o) {
-        for (int i = 0; i < 4; ++i)
-            MHE_REQUIRE(disjoint(out[o].p, out[o].n, in[i].p, in[i].n), "mhe_silhouette_dist_f32: output %d overlaps input %d", o, i);
+        for (int i = 0; i < 5; ++i)
+            MHE_REQUIRE(disjoint(out[o].p, out[o].n, in[i].p, in[i].n), "%s: output %d overlaps input %d", who, o, i);
         for (int q = 0; q < o; ++q)
-            MHE_REQUIRE(disjoint(out[o].p, out[o].n, out[q].p, out[q].n), "mhe_silhouette_dist_f32: outputs %d and %d overlap", q, o);
+            MHE_REQUIRE(disjoint(out[o].p, out[o].n, out[q].p, out[q].n), "%s: outputs %d and %d overlap", who, q, o);
     }
     if (idx_v || idx_m)
-        hipLaunchKernelGGL(silhouette::dist_kernel<true>, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, dist,
-                           parts, idx_v, idx_m, B, V, S);
+        hipLaunchKernelGGL(silhouette::dist_kernel<true>, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count,
+                           count_all, dist, parts, idx_v, idx_m, B, V, S);
     else
-        hipLaunchKernelGGL(silhouette::dist_kernel<false>, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, dist,
-                           parts, idx_v, idx_m, B, V, S);
+        hipLaunchKernelGGL(silhouette::dist_kernel<false>, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count,
+                           count_all, dist, parts, idx_v, idx_m, B, V, S);
     return check_launch("silhouette::dist_kernel");
+}
+
+static int dist_bwd_call(const char *who, bool occ, const float *verts, const float *logs_t, const int *pixels, const int *count, const int *count_all,
+                         const int *idx_v, const int *idx_m, const float *g_dist, float *g_verts, float *g_logs_t, int N, int B, int V, int S,
+                         void *stream) {
+    if (int st = silhouette_args(who, verts, logs_t, pixels, count, N, B, V, S)) return st;
+    MHE_REQUIRE(idx_v && idx_m && g_dist && g_verts && g_logs_t, "%s: null pointer (idx_v, idx_m, g_dist, g_verts, g_logs_t)", who);
+    MHE_REQUIRE(!occ || count_all, "%s: null pointer (count_all)", who);
+    const size_t R = (size_t)N * B, P = (size_t)S * S;
+    struct { const void *p; size_t n; } in[8] = {{verts, R * V * 12}, {logs_t, R * 12}, {pixels, (size_t)B * P * 4}, {count, (size_t)B * 4},
+                                                 {idx_v, R * V * 4}, {idx_m, R * P * 4}, {g_dist, R * 4}, {count_all, (size_t)B * 4}};
+    for (int i = 0; i < 8; ++i)
+        MHE_REQUIRE(disjoint(g_verts, R * V * 12, in[i].p, in[i].n) && disjoint(g_logs_t, R * 12, in[i].p, in[i].n), "%s: an output overlaps input %d",
+                    who, i);
+    MHE_REQUIRE(disjoint(g_verts, R * V * 12, g_logs_t, R * 12), "%s: g_verts and g_logs_t overlap", who);
+    hipLaunchKernelGGL(silhouette::dist_bwd_kernel, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, count_all,
+                       idx_v, idx_m, g_dist, g_verts, g_logs_t, B, V, S);
+    return check_launch("silhouette::dist_bwd_kernel");
+}
+
+static int dist_grad_call(const char *who, bool occ, const float *verts, const float *logs_t, const int *pixels, const int *count, const int *count_all,
+                          const float *g_dist, float *dist, float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream) {
+    if (int st = silhouette_args(who, verts, logs_t, pixels, count, N, B, V, S)) return st;
+    MHE_REQUIRE(g_dist && g_verts && g_logs_t, "%s: null pointer (g_dist, g_verts, g_logs_t)", who);
+    MHE_REQUIRE(!occ || count_all, "%s: null pointer (count_all)", who);
+    const size_t R = (size_t)N * B, P = (size_t)S * S;
+    struct { const void *p; size_t n; } in[6] = {{verts, R * V * 12}, {logs_t, R * 12}, {pixels, (size_t)B * P * 4}, {count, (size_t)B * 4}, {g_dist, R * 4},
+                                                 {count_all, (size_t)B * 4}},
+                                        out[3] = {{dist, R * 4}, {g_verts, R * V * 12}, {g_logs_t, R * 12}};
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 6; ++i)
+            MHE_REQUIRE(disjoint(out[o].p, out[o].n, in[i].p, in[i].n), "%s: output %d overlaps input %d", who, o, i);
+        for (int q = 0; q < o; ++q)
+            MHE_REQUIRE(disjoint(out[o].p, out[o].n, out[q].p, out[q].n), "%s: outputs %d and %d overlap", who, q, o);
+    }
+    hipLaunchKernelGGL(silhouette::dist_grad_kernel, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, count_all,
+                       g_dist, dist, g_verts, g_logs_t, B, V, S);
+    return check_launch("silhouette::dist_grad_kernel");
+}
+
+extern "C" int mhe_silhouette_dist_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, float *dist, float *parts, int *idx_v,
+                                       int *idx_m, int N, int B, int V, int S, void *stream) {
+    return dist_call("mhe_silhouette_dist_f32", false, verts, logs_t, pixels, count, nullptr, dist, parts, idx_v, idx_m, N, B, V, S, stream);
+}
+
+extern "C" int mhe_silhouette_dist_occ_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *count_all, float *dist,
+                                           float *parts, int *idx_v, int *idx_m, int N, int B, int V, int S, void *stream) {
+    return dist_call("mhe_silhouette_dist_occ_f32", true, verts, logs_t, pixels, count, count_all, dist, parts, idx_v, idx_m, N, B, V, S, stream);
 }
 
 extern "C" int mhe_silhouette_dist_bwd_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *idx_v, const int *idx_m,
                                            const float *g_dist, float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream) {
-    if (int st = silhouette_args("mhe_silhouette_dist_bwd_f32", verts, logs_t, pixels, count, N, B, V, S)) return st;
-    MHE_REQUIRE(idx_v && idx_m && g_dist && g_verts && g_logs_t, "mhe_silhouette_dist_bwd_f32: null pointer (idx_v, idx_m, g_dist, g_verts, g_logs_t)");
-    const size_t R = (size_t)N * B, P = (size_t)S * S;
-    struct { const void *p; size_t n; } in[7] = {{verts, R * V * 12}, {logs_t, R * 12}, {pixels, (size_t)B * P * 4}, {count, (size_t)B * 4},
-                                                 {idx_v, R * V * 4}, {idx_m, R * P * 4}, {g_dist, R * 4}};
-    for (int i = 0; i < 7; ++i)
-        MHE_REQUIRE(disjoint(g_verts, R * V * 12, in[i].p, in[i].n) && disjoint(g_logs_t, R * 12, in[i].p, in[i].n),
-                    "mhe_silhouette_dist_bwd_f32: an output overlaps input %d", i);
-    MHE_REQUIRE(disjoint(g_verts, R * V * 12, g_logs_t, R * 12), "mhe_silhouette_dist_bwd_f32: g_verts and g_logs_t overlap");
-    hipLaunchKernelGGL(silhouette::dist_bwd_kernel, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, idx_v,
-                       idx_m, g_dist, g_verts, g_logs_t, B, V, S);
-    return check_launch("silhouette::dist_bwd_kernel");
+    return dist_bwd_call("mhe_silhouette_dist_bwd_f32", false, verts, logs_t, pixels, count, nullptr, idx_v, idx_m, g_dist, g_verts, g_logs_t, N, B, V, S,
+                         stream);
+}
+
+extern "C" int mhe_silhouette_dist_bwd_occ_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *count_all,
+                                               const int *idx_v, const int *idx_m, const float *g_dist, float *g_verts, float *g_logs_t, int N, int B, int V,
+                                               int S, void *stream) {
+    return dist_bwd_call("mhe_silhouette_dist_bwd_occ_f32", true, verts, logs_t, pixels, count, count_all, idx_v, idx_m, g_dist, g_verts, g_logs_t, N, B, V,
+                         S, stream);
 }
 
 extern "C" int mhe_silhouette_dist_grad_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const float *g_dist, float *dist,
                                             float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream) {
-    if (int st = silhouette_args("mhe_silhouette_dist_grad_f32", verts, logs_t, pixels, count, N, B, V, S)) return st;
-    MHE_REQUIRE(g_dist && g_verts && g_logs_t, "mhe_silhouette_dist_grad_f32: null pointer (g_dist, g_verts, g_logs_t)");
-    const size_t R = (size_t)N * B, P = (size_t)S * S;
-    struct { const void *p; size_t n; } in[5] = {{verts, R * V * 12}, {logs_t, R * 12}, {pixels, (size_t)B * P * 4}, {count, (size_t)B * 4}, {g_dist, R * 4}},
-                                        out[3] = {{dist, R * 4}, {g_verts, R * V * 12}, {g_logs_t, R * 12}};
-    for (int o = 0; o < 3; ++o) {
-        for (int i = 0; i < 5; ++i)
-            MHE_REQUIRE(disjoint(out[o].p, out[o].n, in[i].p, in[i].n), "mhe_silhouette_dist_grad_f32: output %d overlaps input %d", o, i);
-        for (int q = 0; q < o; ++q)
-            MHE_REQUIRE(disjoint(out[o].p, out[o].n, out[q].p, out[q].n), "mhe_silhouette_dist_grad_f32: outputs %d and %d overlap", q, o);
-    }
-    hipLaunchKernelGGL(silhouette::dist_grad_kernel, dim3((unsigned)R), dim3(silhouette::NT), 0, (hipStream_t)stream, verts, logs_t, pixels, count, g_dist,
-                       dist, g_verts, g_logs_t, B, V, S);
-    return check_launch("silhouette::dist_grad_kernel");
+    return dist_grad_call("mhe_silhouette_dist_grad_f32", false, verts, logs_t, pixels, count, nullptr, g_dist, dist, g_verts, g_logs_t, N, B, V, S, stream);
+}
+
+extern "C" int mhe_silhouette_dist_grad_occ_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *count_all,
+                                                const float *g_dist, float *dist, float *g_verts, float *g_logs_t, int N, int B, int V, int S,
+                                                void *stream) {
+    return dist_grad_call("mhe_silhouette_dist_grad_occ_f32", true, verts, logs_t, pixels, count, count_all, g_dist, dist, g_verts, g_logs_t, N, B, V, S,
+                          stream);
 }

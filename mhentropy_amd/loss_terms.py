@@ -1,29 +1,36 @@
-"""The optional terms of the hand loss for ONE call of it - get_loss(mods=, chamfer_w=, sil_w=) - as one object: MHEnt._reverse_kld and
+"""The optional terms of the hand loss for ONE call of it - get_loss(mods=, chamfer_w=, sil_w=, sil_occluder=) - as one object: MHEnt._reverse_kld and
 train.TrainStep build it, ask it for the loss pass, its reverse and the result dictionary, and TrainStep keeps it on its tape.  A new
 term is added here (and in the kernels), not in the layers between."""
 from . import ops
 
 
 class LossTerms:
-    def __init__(self, model, y, mods=None, chamfer_w=None, sil_w=None, B=None, who="get_loss", sharded=False, pixels=True):
+    def __init__(self, model, y, mods=None, chamfer_w=None, sil_w=None, B=None, who="get_loss", sharded=False, pixels=True, sil_occluder=None):
         """every host check of the call, before any launch: the likelihood bit set (mods: get_loss's names or the bits themselves), the
         Chamfer weight and operands (MHEnt.chamfer_operands), the silhouette weight and - pixels=True, the one launch here - the kept pixels
-        of y['hand_mask'] for B images (MHEnt.sil_operands).  sharded: the hypothesis-sharded step, which has no silhouette term."""
+        of y['hand_mask'] for B images (MHEnt.sil_operands) - with sil_occluder (None: the model's) those of y['object_mask'] behind them,
+        and sil_all, the length of both sections.  sharded: the hypothesis-sharded step, which has no silhouette term."""
         self.model, self.y = model, y
         self.bits = mods if isinstance(mods, int) else ops.mods_bits(mods)
         if self.bits & ops.MODS_XYZ and "pose3d" not in y:
             raise ValueError(f"{who}(mods=[..., 'xyz']) needs the 3D target y['pose3d'] (B, 63)")
         self.chamfer_w, self.chamfer = model.chamfer_operands(y, chamfer_w)
-        self.sil_w, self.sil = float(model.sil_w if sil_w is None else sil_w), None
+        self.sil_w, self.sil, self.sil_all = float(model.sil_w if sil_w is None else sil_w), None, None
+        self.sil_occluder = bool(model.sil_occluder if sil_occluder is None else sil_occluder) and self.sil_w > 0
         if sharded and self.sil_w > 0:
             raise NotImplementedError("hypothesis sharding with sil_w > 0: the masks of the other ranks' images are not gathered")
         if pixels:
-            self.sil_w, self.sil = model.sil_operands(y, self.sil_w, B)
+            self.sil_w, self.sil, *rest = model.sil_operands(y, self.sil_w, B, self.sil_occluder)
+            self.sil_all = rest[0] if rest else None
         self._pass = None
 
     def weights(self):
-        """the call's three arguments, checked and with the model's defaults filled in"""
-        return {"mods": self.bits, "chamfer_w": self.chamfer_w, "sil_w": self.sil_w}
+        """the call's arguments, checked and with the model's defaults filled in; 'sil_occluder' is carried when the occluder is on (the
+        silhouette term on, too): a call without it is the call it was before the argument existed"""
+        w = {"mods": self.bits, "chamfer_w": self.chamfer_w, "sil_w": self.sil_w}
+        if self.sil_occluder:
+            w["sil_occluder"] = True
+        return w
 
     def keys(self):
         """the keys of reduce()'s dictionary, in its order"""
@@ -63,7 +70,7 @@ class LossTerms:
         q_log_p, h, log_p = ops.elbo_reduce(o["log_p"], log_q, N, B)
         ch = ops.elbo_reduce(o["chamfer"], None, N, B)[0] if self.chamfer is not None else None
         # mesh of the loss pass' z, its distance without index tensors, mean over the hypotheses; the mesh is kept for the reverse
-        self.sil_verts, self.sil_logs_t, sl = self.model.silhouette_rows(o["z"], self.sil, N, B) if self.sil is not None else (None, None, None)
+        self.sil_verts, self.sil_logs_t, sl = self.model.silhouette_rows(o["z"], self.sil, N, B, self.sil_all) if self.sil is not None else (None, None, None)
         if share is not None:
             q_log_p, h, ch = share(q_log_p, h, ch)
             log_p = h + q_log_p

@@ -17,6 +17,8 @@ Extensions (all optional, defaults reproduce the reference):
   * `sil_w=` / the attribute `MHEnt.sil_w` (0.0): the weight of the silhouette term the reference only prepared for (`mask_sz=64`,
     hand/network.py:363; its renderer is commented out): log_p -= sil_w * silhouette, new key 'silhouette' (B,), the mean over the hypotheses
     of criteria.silhouette_dist of the mesh against y['hand_mask'] at grid size `MHEnt.sil_size` (64).
+  * `sil_occluder=` / the attribute `MHEnt.sil_occluder` (False): the silhouette term with y['object_mask'] as criteria.silhouette_dist's
+    occluder - the object the hand holds excuses the vertices behind it and attracts nothing.
 The `q_z_giv_i_model='glow'` branch (hand/network.py:342-344,736-742) runs on mhentropy_amd/glow.py's ConditionalGlow - a
 restatement of the published nflows algorithm, parity UNPINNED (the third-party class is absent from the reference tree).
 Dead reference branches (VAE prior, GT evidences) raise NotImplementedError.  The renderer (hand/network.py:528-558, whose third-party
@@ -130,6 +132,7 @@ class MHEnt(nn.Module):
         self.chamfer_w = 0.0                    # network.py:821-826: use_chamfer_loss = False as shipped; its w_chamfer is 10
         self.sil_w = 0.0                        # the silhouette term (no reference counterpart: its renderer is commented out)
         self.sil_size = 64                      # network.py:363: mask_sz
+        self.sil_occluder = False               # the silhouette term reads y['object_mask'] as its occluder
 
     # ---- pieces ---------------------------------------------------------------
     def _det(self, feat):
@@ -169,10 +172,12 @@ class MHEnt(nn.Module):
         scale, root, obj, count = chamfer_target_operands(y, who="get_loss(chamfer_w)")
         return w, (scale.float(), root.float(), obj.float(), count)
 
-    def sil_operands(self, y, sil_w=None, B=None):
+    def sil_operands(self, y, sil_w=None, B=None, sil_occluder=None):
         """(weight, (pixels, count) | None) of the silhouette term for the target y: sil_w None falls back to self.sil_w; a weight of 0 is
         the term off (None, nothing launched).  y['hand_mask'] (B, H, H) (B None: whatever the mask has) bool / uint8 / float32 with H a multiple of self.sil_size; the shape
-        checks are criteria.silhouette_dist's, on the host, before any launch; the kept-pixel list (ops.silhouette_pixels) is the one launch."""
+        checks are criteria.silhouette_dist's, on the host, before any launch; the kept-pixel list (ops.silhouette_pixels) is the one launch.
+        sil_occluder (None: self.sil_occluder) on and the weight > 0: y['object_mask'] (B, H, H) like the mask is the occluder, its kept pixels
+        follow the hand's in the list, and the result is (weight, (pixels, count), count_all) as ops.silhouette_pixels(occluder=...) has it."""
         w = float(self.sil_w if sil_w is None else sil_w)
         if not w >= 0.0:
             raise ValueError(f"get_loss: sil_w={w} (>= 0)")
@@ -185,20 +190,28 @@ class MHEnt(nn.Module):
         silhouette_mask_checks(mask, B, int(self.sil_size), who="get_loss(sil_w)")
         if mask.dtype not in (torch.bool, torch.uint8, torch.float32):
             raise ValueError(f"get_loss(sil_w): y['hand_mask'] must be bool, uint8 or float32, got {mask.dtype}")
-        return w, ops.silhouette_pixels(mask.contiguous(), int(self.sil_size))
+        if not (self.sil_occluder if sil_occluder is None else sil_occluder):
+            return w, ops.silhouette_pixels(mask.contiguous(), int(self.sil_size))
+        if "object_mask" not in y:
+            raise ValueError("get_loss(sil_w > 0, sil_occluder) needs the occluder target y['object_mask'] (B, H, H)")
+        from .criteria import silhouette_occluder_checks
+        occ = silhouette_occluder_checks(y["object_mask"], mask, who="get_loss(sil_occluder)")
+        pixels, count, count_all = ops.silhouette_pixels(mask.contiguous(), int(self.sil_size), occ)
+        return w, (pixels, count), count_all
 
-    def silhouette_rows(self, z, sil, N, B):
+    def silhouette_rows(self, z, sil, N, B, count_all=None):
         """the silhouette term's forward on the loss pass' z [N*B,61]: the normalised mesh (ops.mano_verts), its distance to the kept pixels
-        sil = (pixels, count) without index tensors, the mean over the hypotheses -> (verts [N*B,778,3], logs_t [N*B,3], silhouette [B])"""
+        sil = (pixels, count) - with count_all, the occluder section behind them too - without index tensors, the mean over the hypotheses
+        -> (verts [N*B,778,3], logs_t [N*B,3], silhouette [B])"""
         if sil[0].shape[0] != B:
             raise ValueError(f"get_loss(sil_w): y['hand_mask'] has {sil[0].shape[0]} images, the batch {B}")
         verts = ops.mano_verts(z, self.mano_dec.table_blob())
         logs_t = z[:, 58:61].contiguous()
-        dist, _ = ops.silhouette_dist(verts.view(N, B, 778, 3), logs_t.view(N, B, 3), *sil)
+        dist, _ = ops.silhouette_dist(verts.view(N, B, 778, 3), logs_t.view(N, B, 3), *sil, count_all=count_all)
         return verts, logs_t, ops.elbo_reduce(dist.view(N * B), None, N, B)[0]
 
     # ---- reference surface ------------------------------------------------------
-    def _reverse_kld(self, y, x, mods=None, return_dict=True, N=None, noise=None, chamfer_w=None, sil_w=None):
+    def _reverse_kld(self, y, x, mods=None, return_dict=True, N=None, noise=None, chamfer_w=None, sil_w=None, sil_occluder=None):
         """reference hand/network.py:760-831.  mods: ['uv'] (None; weak supervision), ['xyz'] or ['xyz', 'uv'] (3D supervision,
         hand/CrossModalHand.py:354: adds the Laplace likelihood of the normalised joints against y['pose3d'], network.py:620-643).
         chamfer_w (None: self.chamfer_w) > 0: the Chamfer term of network.py:821-826 for N hypotheses - out['chamfer'][b] = mean_n of
@@ -206,15 +219,17 @@ class MHEnt(nn.Module):
         log_p -= chamfer_w * chamfer; the other keys are not touched by it.
         sil_w (None: self.sil_w) > 0: the silhouette term - out['silhouette'][b] = mean_n of criteria.silhouette_dist of row n*B+b's normalised
         mesh (ops.mano_verts(z), the 'verts' of sample()) under logs_t = z[:, 58:61] against y['hand_mask'][b] at grid size self.sil_size, and
-        log_p -= sil_w * silhouette; the other keys are not touched by it.  Both terms may be on."""
+        log_p -= sil_w * silhouette; the other keys are not touched by it.  Both terms may be on.
+        sil_occluder (None: self.sil_occluder): the silhouette term takes y['object_mask'] as its occluder (criteria.silhouette_dist's)."""
         N = N or self.loss_N
         tr = getattr(self, "_trainer", None)
         if tr is not None and self.training and torch.is_grad_enabled():
             # a train.TrainStep is attached: the loss dict comes out as ONE autograd node whose backward is the
             # hand-written reverse pass, so the reference's `total_loss.backward()` works unchanged
             from .train import differentiable_get_loss
-            return differentiable_get_loss(tr, x, y, N=N, noise=noise, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
-        terms = LossTerms(self, y, mods, chamfer_w, sil_w, None if x is None else x.shape[0])      # every host check, then the kept-pixel launch
+            return differentiable_get_loss(tr, x, y, N=N, noise=noise, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w, sil_occluder=sil_occluder)
+        # every host check, then the kept-pixel launch
+        terms = LossTerms(self, y, mods, chamfer_w, sil_w, None if x is None else x.shape[0], sil_occluder=sil_occluder)
         _, feat, _ = self.feat_extractor(x)
         B = feat.shape[0]
         if isinstance(self.q_z_giv_i, ConditionalGlow):      # entropy from the sampling pass itself (network.py:781-783,798-799)

@@ -712,22 +712,40 @@ def chamfer_bwd(points, scale, root, obj, count, idx_p, idx_o, g_dist, unit=1000
 SILHOUETTE_MAX_SIZE, SILHOUETTE_MAX_VERTS = 64, 778          # MHE_SILHOUETTE_MAX_SIZE / _MAX_VERTS of include/mhe.h
 
 
-def silhouette_pixels(hand_mask, size=64):
+def silhouette_pixels(hand_mask, size=64, occluder=None):
     """kept pixels of every image's hand mask (include/mhe.h, mhe_silhouette_pixels): hand_mask [B,H,H] bool / uint8 (non-zero counts as 1) or
     float32 in [0,1], H a multiple of size -> pixels [B,size*size] int32, packed (i << 16) | j in row-major order and -1 past the count, and
-    count [B] int32, which stays on the device"""
+    count [B] int32, which stays on the device.  occluder [B,H,H] (the same types; mhe_silhouette_pixels_occ): its kept pixels that are not
+    the hand's follow the hand's in the list -> (pixels, count, count_all), count_all [B] int32 the length of both sections"""
     if not isinstance(hand_mask, torch.Tensor) or hand_mask.dim() != 3 or hand_mask.shape[1] != hand_mask.shape[2]:
         raise _lib.MheError("silhouette_pixels.hand_mask: expected a [B,H,H] tensor")
     B, H, S = hand_mask.shape[0], hand_mask.shape[1], int(size)
     if hand_mask.dtype not in (torch.bool, torch.uint8, torch.float32):
         raise _lib.MheError(f"silhouette_pixels.hand_mask: expected bool, uint8 or float32, got {hand_mask.dtype}")
     _chk(hand_mask, hand_mask.dtype, "silhouette_pixels.hand_mask")
+    if occluder is not None:
+        if not isinstance(occluder, torch.Tensor) or occluder.dtype not in (torch.bool, torch.uint8, torch.float32):
+            raise _lib.MheError(f"silhouette_pixels.occluder: expected a bool, uint8 or float32 tensor, got {getattr(occluder, 'dtype', type(occluder))}")
+        _chk(occluder, occluder.dtype, "silhouette_pixels.occluder", (B, H, H))
     if not 1 <= S <= SILHOUETTE_MAX_SIZE or B < 1 or H < S or H % S:
         raise ValueError(f"silhouette_pixels: B={B} H={H} size={S} (B >= 1, size in 1..{SILHOUETTE_MAX_SIZE}, H a multiple of size)")
     pixels = torch.empty(B, S * S, device=hand_mask.device, dtype=torch.int32)
     count = torch.empty(B, device=hand_mask.device, dtype=torch.int32)
-    launch("mhe_silhouette_pixels", hand_mask, int(hand_mask.dtype == torch.float32), pixels, count, B, H, S)
-    return pixels, count
+    if occluder is None:
+        launch("mhe_silhouette_pixels", hand_mask, int(hand_mask.dtype == torch.float32), pixels, count, B, H, S)
+        return pixels, count
+    count_all = torch.empty_like(count)
+    launch("mhe_silhouette_pixels_occ", hand_mask, int(hand_mask.dtype == torch.float32), occluder, int(occluder.dtype == torch.float32), pixels, count,
+           count_all, B, H, S)
+    return pixels, count, count_all
+
+
+def _silhouette_entry(name, count_all, B, who):
+    """the entry and the operand that follows count: (name, ()) without an occluder section, (name_occ, (count_all,)) with one"""
+    if count_all is None:
+        return f"mhe_silhouette_{name}_f32", ()
+    _chk(count_all, torch.int32, f"{who}.count_all", (B,))
+    return f"mhe_silhouette_{name}_occ_f32", (count_all,)
 
 
 def _silhouette_operands(verts, logs_t, pixels, count, who):
@@ -747,39 +765,44 @@ def _silhouette_operands(verts, logs_t, pixels, count, who):
     return N, B, V, S
 
 
-def silhouette_dist(verts, logs_t, pixels, count, want_idx=False):
+def silhouette_dist(verts, logs_t, pixels, count, want_idx=False, count_all=None):
     """silhouette distance of every hypothesis' projected vertices to its image's kept pixels (include/mhe.h, mhe_silhouette_dist_f32): verts
     [N,B,V,3], logs_t [N,B,3] = (log s, tx, ty), pixels / count of silhouette_pixels -> dist [N,B], parts [N,B,2] = (inside, cover);
-    want_idx: also the argmins idx_v [N,B,V] and idx_m [N,B,size*size] (int32) that silhouette_dist_bwd reads"""
+    want_idx: also the argmins idx_v [N,B,V] and idx_m [N,B,size*size] (int32) that silhouette_dist_bwd reads.  count_all [B] (the third
+    result of silhouette_pixels(occluder=...); mhe_silhouette_dist_occ_f32): the vertices' minima also run over the list's occluder section"""
     N, B, V, S = _silhouette_operands(verts, logs_t, pixels, count, "silhouette_dist")
     dev = verts.device
     dist = torch.empty(N, B, device=dev, dtype=torch.float32)
     parts = torch.empty(N, B, 2, device=dev, dtype=torch.float32)
     idx_v = torch.empty(N, B, V, device=dev, dtype=torch.int32) if want_idx else None
     idx_m = torch.empty(N, B, S * S, device=dev, dtype=torch.int32) if want_idx else None
-    launch("mhe_silhouette_dist_f32", verts, logs_t, pixels, count, dist, parts, idx_v, idx_m, N, B, V, S)
+    entry, occ = _silhouette_entry("dist", count_all, B, "silhouette_dist")
+    launch(entry, verts, logs_t, pixels, count, *occ, dist, parts, idx_v, idx_m, N, B, V, S)
     return (dist, parts, idx_v, idx_m) if want_idx else (dist, parts)
 
 
-def silhouette_dist_bwd(verts, logs_t, pixels, count, idx_v, idx_m, g_dist):
+def silhouette_dist_bwd(verts, logs_t, pixels, count, idx_v, idx_m, g_dist, count_all=None):
     """reverse of silhouette_dist's dist (mhe_silhouette_dist_bwd_f32): idx_v / idx_m of the forward call, g_dist [N,B] -> g_verts [N,B,V,3]
-    (its z column is zero), g_logs_t [N,B,3]"""
+    (its z column is zero), g_logs_t [N,B,3]; count_all: the forward call's"""
     N, B, V, S = _silhouette_operands(verts, logs_t, pixels, count, "silhouette_dist_bwd")
     _chk(idx_v, torch.int32, "silhouette_dist_bwd.idx_v", (N, B, V)); _chk(idx_m, torch.int32, "silhouette_dist_bwd.idx_m", (N, B, S * S))
     _chk(g_dist, torch.float32, "silhouette_dist_bwd.g_dist", (N, B))
     g_verts, g_logs_t = torch.empty_like(verts), torch.empty_like(logs_t)
-    launch("mhe_silhouette_dist_bwd_f32", verts, logs_t, pixels, count, idx_v, idx_m, g_dist, g_verts, g_logs_t, N, B, V, S)
+    entry, occ = _silhouette_entry("dist_bwd", count_all, B, "silhouette_dist_bwd")
+    launch(entry, verts, logs_t, pixels, count, *occ, idx_v, idx_m, g_dist, g_verts, g_logs_t, N, B, V, S)
     return g_verts, g_logs_t
 
 
-def silhouette_dist_grad(verts, logs_t, pixels, count, g_dist, want_dist=False):
+def silhouette_dist_grad(verts, logs_t, pixels, count, g_dist, want_dist=False, count_all=None):
     """silhouette_dist(want_idx=True) + silhouette_dist_bwd in one launch, without the two index tensors (mhe_silhouette_dist_grad_f32: the
-    argmins stay in registers and LDS): g_dist [N,B] -> (g_verts [N,B,V,3], g_logs_t [N,B,3]), with want_dist (dist [N,B], g_verts, g_logs_t)"""
+    argmins stay in registers and LDS): g_dist [N,B] -> (g_verts [N,B,V,3], g_logs_t [N,B,3]), with want_dist (dist [N,B], g_verts, g_logs_t);
+    count_all as in silhouette_dist (mhe_silhouette_dist_grad_occ_f32)"""
     N, B, V, S = _silhouette_operands(verts, logs_t, pixels, count, "silhouette_dist_grad")
     _chk(g_dist, torch.float32, "silhouette_dist_grad.g_dist", (N, B))
     dist = torch.empty(N, B, device=verts.device, dtype=torch.float32) if want_dist else None
     g_verts, g_logs_t = torch.empty_like(verts), torch.empty_like(logs_t)
-    launch("mhe_silhouette_dist_grad_f32", verts, logs_t, pixels, count, g_dist, dist, g_verts, g_logs_t, N, B, V, S)
+    entry, occ = _silhouette_entry("dist_grad", count_all, B, "silhouette_dist_grad")
+    launch(entry, verts, logs_t, pixels, count, *occ, g_dist, dist, g_verts, g_logs_t, N, B, V, S)
     return (dist, g_verts, g_logs_t) if want_dist else (g_verts, g_logs_t)
 
 

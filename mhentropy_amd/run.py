@@ -8,6 +8,7 @@ on synthetic batches (no dataset ships with this repository; the HO3D pipeline i
     python -m mhentropy_amd.run --mods uv,xyz ...        # 3D-supervised training (hand/CrossModalHand.py:354, mods = ['xyz', 'uv'])
     python -m mhentropy_amd.run --chamfer-w 10 ...       # with the hand-object Chamfer term (hand/network.py:821-826, w_chamfer = 10)
     python -m mhentropy_amd.run --sil-w 1 ...            # with the silhouette term (the mesh against the hand mask, MHEnt.get_loss(sil_w=...))
+    python -m mhentropy_amd.run --sil-w 1 --sil-occluder ...   # ... with the object's mask as the term's occluder (get_loss(sil_occluder=True))
     python -m mhentropy_amd.run --test-samples 200 --quant-samples 10 --quant kmeans ...      # metrics of 10 k-means modes of 200 hypotheses
 """
 import argparse
@@ -69,11 +70,17 @@ def main(argv=None):
                     help="weight of the silhouette term in the loss (MHEnt.get_loss(sil_w=...): the distance of every hypothesis' projected mesh "
                          "to the image's hand mask; 0 = off).  Synthetic masks around the target keypoints (synth.hand_masks) by default, the "
                          "pipeline's hand_mask under --input-pipeline")
+    ap.add_argument("--sil-occluder", action="store_true",
+                    help="the silhouette term takes the object's mask as its occluder (MHEnt.get_loss(sil_occluder=True): a vertex behind the "
+                         "object costs nothing, the object attracts nothing).  A synthetic disc or box over part of the hand mask, cut out of "
+                         "it (synth.object_masks), by default, the pipeline's object_mask under --input-pipeline; needs --sil-w > 0")
     args = ap.parse_args(argv)
     if args.chamfer_w < 0:
         raise SystemExit("--chamfer-w must be >= 0")
     if not args.sil_w >= 0:
         raise SystemExit("--sil-w must be >= 0")
+    if args.sil_occluder and not args.sil_w > 0:
+        raise SystemExit("--sil-occluder needs --sil-w > 0")
     if args.quant_samples < 0:
         raise SystemExit("--quant-samples must be >= 0")
     from . import ops
@@ -141,18 +148,21 @@ def main(argv=None):
                     yn.update(synth.object_targets(args.seed + 1000 * rank + step, args.batch, with_count=True))
                 if args.sil_w > 0:
                     yn["hand_mask"] = synth.hand_masks(args.seed + 1000 * rank + step, args.batch, crop_uv=yn["crop_uv"])
+                if args.sil_occluder:
+                    yn["hand_mask"], yn["object_mask"] = synth.object_masks(args.seed + 1000 * rank + step, yn["hand_mask"])
                 y = {k: torch.as_tensor(v).cuda() for k, v in yn.items()}
             model.training_step_start(step)
             if args.graph and not args.test_samples:
                 from .train import GraphedStep
                 yk = {k: y[k].contiguous() for k in ("crop_uv", "vis") + (("pose3d",) if "xyz" in mods else ()) +      # what the loss consumes
                       (("object_verts", "object_count", "scale", "original_pose3d") if args.chamfer_w > 0 else ()) +
-                      (("hand_mask",) if args.sil_w > 0 else ())}
+                      (("hand_mask",) if args.sil_w > 0 else ()) + (("object_mask",) if args.sil_occluder else ())}
                 if graphed is None or graphed_lr != trainer.lr:
                     # (re-)capture: GraphedStep's warm-up pass is one real step on this batch - it IS this iteration (replaying the
                     # same batch as well would apply two optimizer steps to it and advance Adam's count and the BatchNorm buffers twice)
                     sx, sy = x.clone(), {k: v.clone() for k, v in yk.items()}
-                    graphed, graphed_lr = GraphedStep(trainer, sx, sy, N=args.hyps, mods=mods, chamfer_w=args.chamfer_w, sil_w=args.sil_w), trainer.lr
+                    graphed, graphed_lr = GraphedStep(trainer, sx, sy, N=args.hyps, mods=mods, chamfer_w=args.chamfer_w, sil_w=args.sil_w,
+                                                       sil_occluder=args.sil_occluder), trainer.lr
                     out = graphed.warm_out
                 else:
                     sx.copy_(x)
@@ -161,7 +171,7 @@ def main(argv=None):
                     out = graphed.replay()
             else:
                 out = trainer.step(x, y, N=args.hyps, test_samples=args.test_samples, mods=mods, chamfer_w=args.chamfer_w, sil_w=args.sil_w,
-                                   test_quant=args.quant_samples, quant=args.quant)
+                                   test_quant=args.quant_samples, quant=args.quant, sil_occluder=args.sil_occluder)
             with torch.no_grad():
                 total, losses, metrics = criterion(dict(out), y)
             meters["loss"].update(float(total))

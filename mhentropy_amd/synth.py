@@ -202,6 +202,34 @@ def hand_masks(seed=0, B=2, H=64, crop_uv=None, image_size=256, with_image=True)
     return (d2 <= 0.08 ** 2).any(1)
 
 
+def object_masks(seed=0, hand_mask=None, B=2, H=64, **kw):
+    """Seeded occluders for the silhouette term (get_loss(sil_occluder=True), criteria.silhouette_dist(occluder=...)): a disc or a box, drawn
+    per image, laid over part of hand_mask (B, H, H) bool (None: hand_masks(seed, B, H, **kw)), with the pixels it covers REMOVED from the
+    hand mask, as an object in front of the hand removes them -> (hand_mask, object_mask), both (B, H, H) bool and disjoint.  The shape is
+    centred on a hand pixel and its half-size is drawn from 0.15 .. 0.3 of the hand's extent; one that would cover the whole hand is halved
+    until a hand pixel stays, so no image loses its hand."""
+    hand = np.array(hand_masks(seed, B, H, **kw) if hand_mask is None else hand_mask, bool)
+    B, H = hand.shape[:2]
+    rng = np.random.default_rng(seed + 4700)
+    ii, jj = np.mgrid[0:H, 0:H]
+    obj = np.zeros_like(hand)
+    for b in range(B):
+        i, j = np.nonzero(hand[b])
+        pick, disc, frac = rng.integers(0, max(len(i), 1)), rng.random() < 0.5, rng.uniform(0.15, 0.3)
+        if not len(i):
+            continue
+        r = max(1.0, frac * max(i.max() - i.min() + 1, j.max() - j.min() + 1))
+        while True:
+            di, dj = np.abs(ii - i[pick]), np.abs(jj - j[pick])
+            shape = (di * di + dj * dj <= r * r) if disc else ((di <= r) & (dj <= r))
+            if (hand[b] & ~shape).any() or r < 0.5:
+                break
+            r *= 0.5
+        if (hand[b] & ~shape).any():
+            obj[b] = shape
+    return hand & ~obj, obj
+
+
 def structured_images(seed=0, B=2, image_size=256):
     """Images with image-to-image structure (a smooth random field per image: random 4x4 / 16x16 colour patterns bilinearly enlarged, a
     per-image gain and offset, a little pixel noise), in [-1,1].  batch()'s default images are i.i.d. white noise: after global average pooling

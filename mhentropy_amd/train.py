@@ -727,7 +727,7 @@ class TrainStep:
         self._grad_ready(0)
 
     # ------------------------------------------------------------------ the step
-    def forward(self, x, y, noise=None, N=None, trunk_out=None, mods=None, chamfer_w=None, sil_w=None):
+    def forward(self, x, y, noise=None, N=None, trunk_out=None, mods=None, chamfer_w=None, sil_w=None, sil_occluder=None):
         """forward of MHEnt.get_loss (hand/network.py:760-831) keeping what the reverse pass needs.  Returns the get_loss dict.
         trunk_out (B, feat_dim) f32 (testing aid): stands in for the ResNet trunk's output, whose forward and reverse
         passes are then skipped - the reference's golden gradients are pinned from the trunk feature on.
@@ -736,11 +736,13 @@ class TrainStep:
         'original_pose3d' and, if present, 'object_count'; 0 launches what the step launched without the argument).
         sil_w: get_loss's weight of the silhouette term (None: the model's sil_w; > 0 reads y['hand_mask']; 0 launches what the step launched
         without the argument).  Between forward and reverse the term keeps z, the mesh (N*B x 778 x 3 f32) and the kept-pixel list; no index
-        tensor exists: the reverse re-evaluates both minima (ops.silhouette_dist_grad)."""
+        tensor exists: the reverse re-evaluates both minima (ops.silhouette_dist_grad).
+        sil_occluder: get_loss's (None: the model's sil_occluder); on, the term reads y['object_mask'] as its occluder and keeps the length of
+        the list's two sections next to the list."""
         m = self.model
         N = N or m.loss_N
         B = x.shape[0] if trunk_out is None else trunk_out.shape[0]
-        terms = LossTerms(m, y, mods, chamfer_w, sil_w, B, who="TrainStep.forward", sharded=self.shard_hypotheses)
+        terms = LossTerms(m, y, mods, chamfer_w, sil_w, B, who="TrainStep.forward", sharded=self.shard_hypotheses, sil_occluder=sil_occluder)
         self.arena.sync()     # someone else (torch.optim, load_state_dict) may have written the parameters
         f = self._trunk_forward(x.contiguous()) if trunk_out is None else trunk_out.contiguous()
         feat, feat_b = ops.linear(f, self.l1["w"], self.l1["b"], want_bf16=True) if self.flow_bf16 else (ops.linear(f, self.l1["w"], self.l1["b"]), None)
@@ -771,7 +773,7 @@ class TrainStep:
                 own = slice(hs.rank * B_own, (hs.rank + 1) * B_own)
                 return part[0, own].contiguous(), part[1, own].contiguous(), None if ch is None else part[2, own].contiguous()
         out = terms.reduce(o, log_q if m.entropy else None, N, B, share)
-        self.tape = {"f": f, "feat": feat, "hd": hd, "det": det, "th45": th45, "blob": blob, "terms": terms, "sil": terms.sil, "z": o.get("z"),
+        self.tape = {"f": f, "feat": feat, "hd": hd, "det": det, "th45": th45, "blob": blob, "terms": terms, "sil": terms.sil, "sil_all": terms.sil_all, "z": o.get("z"),
                      "sil_verts": terms.sil_verts, "sil_logs_t": terms.sil_logs_t, "N": N, "B": B, "trunk": trunk_out is None, "hs": hs, "B_own": B_own,
                      "N_all": N_all, "feat_own": feat_own}
         return out
@@ -821,9 +823,9 @@ class TrainStep:
             self.G.mul_(1.0 / self.world)
             self._G_averaged = True        # optimizer_step() must not divide by world a second time
 
-    def forward_backward(self, x, y, noise=None, N=None, trunk_out=None, mods=None, chamfer_w=None, sil_w=None):
+    def forward_backward(self, x, y, noise=None, N=None, trunk_out=None, mods=None, chamfer_w=None, sil_w=None, sil_occluder=None):
         """forward + reverse pass of total = mean_b(-log_p[b]); fills self.G.  Returns the get_loss dict + 'total'."""
-        out = self.forward(x, y, noise=noise, N=N, trunk_out=trunk_out, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
+        out = self.forward(x, y, noise=noise, N=N, trunk_out=trunk_out, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w, sil_occluder=sil_occluder)
         self.backward()
         out["total"] = -out["log_p"].mean()
         return out
@@ -843,7 +845,7 @@ class TrainStep:
         N, B = t["N"], t["B"]
         g_dist = self.arena.buf("g_sil_dist", (N, B))
         torch.mul(g_logp.view(1, B).expand(N, B), -t["terms"].sil_w / t["N_all"], out=g_dist)
-        g_verts, g_logs_t = ops.silhouette_dist_grad(t["sil_verts"].view(N, B, 778, 3), t["sil_logs_t"].view(N, B, 3), *t["sil"], g_dist)
+        g_verts, g_logs_t = ops.silhouette_dist_grad(t["sil_verts"].view(N, B, 778, 3), t["sil_logs_t"].view(N, B, 3), *t["sil"], g_dist, count_all=t["sil_all"])
         g_z = ops.mano_verts_bwd(t["z"], t["blob"], g_verts.view(N * B, 778, 3))
         ops.mano_z_grad_add(g_z, g_logs_t.view(N * B, 3), g45, gdet_rows)
 
@@ -876,15 +878,16 @@ class TrainStep:
         torch._foreach_add_([u.bn.num_batches_tracked for u in units], 1)
 
     def step(self, x, y, noise=None, N=None, test_samples=0, temp=0.8, double_bn_update=True, mods=None, chamfer_w=None, sil_w=None,
-             test_quant=0, quant="log_q"):
+             test_quant=0, quant="log_q", sil_occluder=None):
         """one iteration of the reference's training loop (hand/CrossModalHand.py:353-361,455-470).  test_samples > 0
         adds its per-iteration metrics pass `sample(N=[n,n], temp=0.8, mods={uv,xyz,verts})` to the returned dict,
         from the conditioning feature of THIS forward.  The reference runs the encoder a second time on the same
         batch in train mode for it: same feature, but the BatchNorm running statistics advance twice per iteration -
         double_bn_update=True (default) reproduces that on the buffers, so checkpoints / eval-mode results match a
-        reference-trained model.  mods, chamfer_w, sil_w: get_loss's likelihoods, Chamfer and silhouette weights, as in forward().
+        reference-trained model.  mods, chamfer_w, sil_w, sil_occluder: get_loss's likelihoods, Chamfer and silhouette weights and the
+        silhouette term's occluder switch, as in forward().
         test_quant (0: test_samples) and quant: the metrics pass is sample(N=[test_samples, test_quant], quant=quant)."""
-        out = self.forward_backward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
+        out = self.forward_backward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w, sil_occluder=sil_occluder)
         if test_samples:
             if double_bn_update and self.tape["trunk"]:
                 self.second_bn_update()
@@ -901,14 +904,15 @@ class GraphedStep:
     (RCCL, async_op: it runs on the communicator's stream under the next graph's kernels), the next graph starts; the last
     graph (norm, clip, Adam, operand re-pack) is launched after the waits.  Six graphs and four collectives per step."""
 
-    def __init__(self, ts, x, y, noise=None, N=None, test_samples=0, criterion=None, mods=None, chamfer_w=None, sil_w=None):
+    def __init__(self, ts, x, y, noise=None, N=None, test_samples=0, criterion=None, mods=None, chamfer_w=None, sil_w=None, sil_occluder=None):
         """test_samples / criterion: the reference's whole iteration (hand/CrossModalHand.py:349-361,452-470) in the graph - the
         metrics pass sample(N=[n,n], temp=0.8) from this forward's feature and `criterion(out, y)` (MHEntLoss: 14 metrics);
         self.out then carries 'criterion' = (total, losses, metrics).  mods: get_loss's likelihoods (TrainStep.forward); with 'xyz'
         the graphs read y['pose3d'] - a new target is copied into that static tensor like the rest of the batch.  chamfer_w > 0 (None: the
         model's): y['object_verts'], 'scale', 'original_pose3d' and 'object_count' are static inputs in the same way; the count's range is
         checked on the host by the warm-up step only (a capturing stream takes no host read: the kernels clamp it to 1..VO).  sil_w > 0
-        (None: the model's): y['hand_mask'] is a static input too; its kept-pixel list is rebuilt inside the graph on every replay"""
+        (None: the model's): y['hand_mask'] is a static input too; its kept-pixel list is rebuilt inside the graph on every replay.
+        sil_occluder (None: the model's): y['object_mask'] is a static input like the mask, and both sections of the list are rebuilt"""
         if ts.shard_hypotheses:
             raise NotImplementedError("GraphedStep: the hypothesis-sharded forward has collectives inside the forward pass")
         self.ts, self.graphs, self.actions = ts, [], []
@@ -918,7 +922,7 @@ class GraphedStep:
         _step = ts.step
 
         def step(x, y, noise=None, N=None):
-            out = _step(x, y, noise=noise, N=N, test_samples=test_samples, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
+            out = _step(x, y, noise=noise, N=N, test_samples=test_samples, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w, sil_occluder=sil_occluder)
             if criterion is not None:
                 with torch.no_grad():
                     out["criterion"] = criterion(dict(out), y)
@@ -975,8 +979,8 @@ class GraphedStep:
 class _LossFn(torch.autograd.Function):
     """MHEnt.get_loss as one autograd node: forward = TrainStep.forward, backward = TrainStep.backward(d loss / d log_p)."""
     @staticmethod
-    def forward(ctx, trainer, x, y, N, noise, mods, chamfer_w, sil_w, *params):
-        out = trainer.forward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w)
+    def forward(ctx, trainer, x, y, N, noise, mods, chamfer_w, sil_w, sil_occluder, *params):
+        out = trainer.forward(x, y, noise=noise, N=N, mods=mods, chamfer_w=chamfer_w, sil_w=sil_w, sil_occluder=sil_occluder)
         ctx.trainer, ctx.keys = trainer, list(out)
         vals = tuple(out[k] for k in ctx.keys)
         ctx.mark_non_differentiable(*[v for k, v in zip(ctx.keys, vals) if k != "log_p"])
@@ -991,7 +995,9 @@ class _LossFn(torch.autograd.Function):
         return (None,) * (len(ctx.needs_input_grad) - len(params)) + tuple(tr.grad_of(p) for p in params)     # one per input of forward
 
 
-def differentiable_get_loss(trainer, x, y, N=None, noise=None, mods=None, chamfer_w=None, sil_w=None):
-    terms = LossTerms(trainer.model, y, mods, chamfer_w, sil_w, pixels=False)     # (forward checks the mask and lists its pixels, before any other launch)
-    vals = _LossFn.apply(trainer, x, y, N, noise, *terms.weights().values(), *trainer.arena.params)
+def differentiable_get_loss(trainer, x, y, N=None, noise=None, mods=None, chamfer_w=None, sil_w=None, sil_occluder=None):
+    # (forward checks the mask and lists its pixels, before any other launch)
+    terms = LossTerms(trainer.model, y, mods, chamfer_w, sil_w, pixels=False, sil_occluder=sil_occluder)
+    w = terms.weights()
+    vals = _LossFn.apply(trainer, x, y, N, noise, w["mods"], w["chamfer_w"], w["sil_w"], w.get("sil_occluder", False), *trainer.arena.params)
     return dict(zip(terms.keys(), vals))
