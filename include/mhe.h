@@ -1046,6 +1046,24 @@ int mhe_chamfer_f32(const float *points, const float *scale, const float *root, 
 int mhe_chamfer_bwd_f32(const float *points, const float *scale, const float *root, const float *obj, const int *obj_count, const int *idx_p,
                         const int *idx_o, const float *g_dist, float *g_points, int N, int B, int P, int VO, float unit, void *stream);
 
+/* Hand mesh evaluation (csrc/mesh_eval.hip): vertex-to-vertex error and precision / recall / F-score of every hypothesis' mesh against its image's
+ * ground-truth mesh, the FreiHAND / HO3D protocol, without the (N B, V, V) distance tensor.  Rows are sample-major, r = n B + b:
+ *   p_v = pred[r][v] (scale[b] unit),  g_v = target[b][v] (scale[b] unit)
+ *   err[r] = (1/V) sum_v |p_v - g_v|                                   (by correspondence)
+ *   d1_v = min_w |p_v - g_w|,  d2_w = min_v |p_v - g_w|
+ *   precision[t][r] = #{v: d1_v < thr[t]} / V,  recall[t][r] = #{w: d2_w < thr[t]} / V,  f[t][r] = 2 P R / (P + R), 0 when P + R = 0
+ * The comparison is the strict < of the FreiHAND / HO3D evaluation code: a vertex exactly thr away is not counted.  What is compared is the
+ * DISTANCE, sqrtf of the least squared distance (the minima are taken of squared distances, one square root per minimum), with thr as given.
+ * mhe_mesh_eval_f32: pred [N,B,V,3], target [B,V,3], scale [B], thr = T thresholds in HOST memory, in the output's unit (unit = 1000: mm)
+ *   -> err [N,B], prf [3,T,N,B] = (precision, recall, f).  1 <= V <= MHE_CHAMFER_MAX_POINTS, 1 <= T <= MHE_MESH_EVAL_MAX_THRESHOLDS, N B < 2^31.
+ *   A workgroup keeps its image's target mesh in LDS for all the hypotheses it walks and stages each hypothesis next to it; N is split over
+ *   enough workgroups to fill the chip at any B.  f32, fixed summation order, integer counts, no atomics: two calls give the same bits.  No
+ *   allocation, no workspace.  Non-finite coordinates are not rejected and their row's result is unspecified (other rows are not disturbed).
+ *   MHE_ERR_ARG before any launch for a null pointer, a shape out of range, a NaN threshold or unit, or outputs that overlap inputs or each other. */
+#define MHE_MESH_EVAL_MAX_THRESHOLDS 4
+int mhe_mesh_eval_f32(const float *pred, const float *target, const float *scale, const float *thr, float *err, float *prf, int N, int B, int V, int T,
+                      float unit, void *stream);
+
 /* Silhouette and depth of a triangle mesh under the 2D head's orthographic camera (csrc/render.hip; the call chain of the reference's
  * ManoLayer.render, hand/ManoLayer.py:62-105, whose third-party rasteriser `neural_renderer` is commented out there and absent here: parity
  * with it is UNPINNED, the contract below is this project's own and is what the tests pin).  R rows (hypotheses), forward only.

@@ -4,7 +4,8 @@ block runs in one HIP kernel (csrc/metrics.hip), the Procrustes alignment of the
 evaluation in csrc/procrustes.hip.  chamfer_dist (hand/criteria.py:18-39) and the selection
 it was written for (chamfer_select) run on csrc/chamfer.hip; silhouette_iou scores the hypotheses' meshes against the image's hand mask
 on csrc/render.hip; silhouette_dist, the differentiable distance of the projected mesh to that mask, and silhouette_select run on
-csrc/silhouette.hip; kmeans_select, which summarises the hypotheses by the representatives of Q k-means modes, runs on csrc/kmeans.hip."""
+csrc/silhouette.hip; kmeans_select, which summarises the hypotheses by the representatives of Q k-means modes, runs on csrc/kmeans.hip;
+mesh_eval, the HO3D mesh protocol (vertex error, F-score, best of n) against target['verts'], and mesh_select run on csrc/mesh_eval.hip."""
 import torch
 from torch import nn
 
@@ -134,6 +135,105 @@ def chamfer_select(output, target, Q=1, points="xyz"):
     with torch.no_grad():
         dist = chamfer_dist(src.detach().reshape(N, B, -1, 3), target)
     return _cut(output, dist, Q, "chamfer")
+
+
+MESH_UNIT = 1000.0             # normalised -> mm, as CHAMFER_UNIT
+
+
+def _mesh_operands(who, output, target, thresholds=(5.0,), ns=None):
+    """the checks of mesh_eval that need no device -> (verts (N, B, V, 3) view-shaped, target verts (B, V, 3), scale (B,), thresholds, ns | None)"""
+    if "verts" not in output:
+        raise ValueError(f"{who}: output has no 'verts'")
+    for k in ("verts", "scale"):
+        if k not in target:
+            raise ValueError(f"{who}: target has no {k!r}")
+    pv, tv, scale = output["verts"], target["verts"], target["scale"]
+    if not isinstance(pv, torch.Tensor) or pv.dim() not in (3, 4) or (pv.dim() == 4 and pv.shape[-1] != 3) or pv.shape[2:].numel() % 3:
+        raise ValueError(f"{who}: output['verts'] must be (N, B, V*3) or (N, B, V, 3), got {tuple(getattr(pv, 'shape', ()))}")
+    N, B, V = pv.shape[0], pv.shape[1], pv.shape[2:].numel() // 3
+    if not isinstance(tv, torch.Tensor) or tv.dim() not in (2, 3) or (tv.dim() == 3 and tv.shape[-1] != 3) or tv.shape[1:].numel() % 3:
+        raise ValueError(f"{who}: target['verts'] must be (B, V*3) or (B, V, 3), got {tuple(getattr(tv, 'shape', ()))}")
+    if tv.shape[0] != B:
+        raise ValueError(f"{who}: output['verts'] has B={B} images, target['verts'] {tv.shape[0]}")
+    if tv.shape[1:].numel() // 3 != V:
+        raise ValueError(f"{who}: output['verts'] has V={V} vertices, target['verts'] {tv.shape[1:].numel() // 3}")
+    if not 1 <= V <= ops.MESH_EVAL_MAX_VERTS:
+        raise ValueError(f"{who}: output['verts'] has V={V} vertices per hypothesis (1..{ops.MESH_EVAL_MAX_VERTS})")
+    if not 1 <= N or not 1 <= B:
+        raise ValueError(f"{who}: output['verts'] is empty, {tuple(pv.shape)}")
+    if not isinstance(scale, torch.Tensor) or tuple(scale.shape) != (B,):
+        raise ValueError(f"{who}: target['scale'] must be (B,) = ({B},), got {tuple(getattr(scale, 'shape', ()))}")
+    try:
+        thr = tuple(float(t) for t in thresholds)
+    except TypeError:
+        raise ValueError(f"{who}: thresholds must be 1 to {ops.MESH_EVAL_MAX_THRESHOLDS} positive numbers, got {thresholds!r}") from None
+    if not 1 <= len(thr) <= ops.MESH_EVAL_MAX_THRESHOLDS:
+        raise ValueError(f"{who}: thresholds holds {len(thr)} numbers (1..{ops.MESH_EVAL_MAX_THRESHOLDS})")
+    if any(not t > 0 for t in thr):
+        raise ValueError(f"{who}: thresholds must be positive, got {thr!r}")
+    if ns is not None:
+        ns = (ns,) if isinstance(ns, int) else tuple(ns)
+        if not 1 <= len(ns) <= 8 or any(not isinstance(n, int) or isinstance(n, bool) for n in ns):
+            raise ValueError(f"{who}: ns must hold 1 to 8 integers, got {ns!r}")
+        if any(not 1 <= n <= N for n in ns) or any(b <= a for a, b in zip(ns, ns[1:])):
+            raise ValueError(f"{who}: ns must be strictly increasing within 1..N={N}, got {ns!r}")
+    return pv.detach().reshape(N, B, V, 3), tv.detach().reshape(B, V, 3), scale.detach(), thr, ns
+
+
+def _min_first_n(err, ns):
+    """err (B', N) f32 contiguous -> (values, index), each (B', len(ns)): the least of the first ns[i] entries of a row and the lowest n that
+    attains it (mhe_min_of_n_f32)"""
+    import ctypes as C
+    Bp, N = err.shape
+    val = torch.empty(Bp, len(ns), device=err.device, dtype=torch.float32)
+    idx = torch.empty(Bp, len(ns), device=err.device, dtype=torch.int32)
+    ops.launch("mhe_min_of_n_f32", err, val, idx, Bp, N, C.cast((C.c_int * len(ns))(*ns), C.c_void_p), len(ns))
+    return val, idx
+
+
+def mesh_eval(output, target, thresholds=(5.0, 15.0), aligned=False, ns=None):
+    """The HO3D / FreiHAND mesh protocol for every hypothesis of a sample() output: output['verts'] (N, B, V*3) or (N, B, V, 3) against the
+    image's ground-truth mesh target['verts'] (B, V*3) or (B, V, 3), both normalised; with p_v = verts * target['scale'] * 1000 (mm) and g_w the
+    target's vertices scaled alike,
+        mesh_err  (N, B)     mean over v of |p_v - g_v|, the vertex-to-vertex error by correspondence, in mm
+        precision (T, N, B)  share of the predicted vertices whose nearest target vertex is closer than thresholds[t] (mm; strictly)
+        recall    (T, N, B)  share of the target vertices whose nearest predicted vertex is closer than thresholds[t]
+        f_score   (T, N, B)  2 P R / (P + R), 0 when both are 0
+    aligned=True: every hypothesis' mesh is first Procrustes-aligned with scale to its target (ops.procrustes_align, the alignment of
+    MHEntLoss(aligned=True)) and the aligned mesh is evaluated; output['verts'] is not replaced.
+    ns=[n1, ...] (strictly increasing, within 1..N): best of the first n hypotheses - adds mesh_err_min and mesh_err_index (len(ns), B), the
+    least mesh_err among hypotheses 0 .. n-1 and the lowest n attaining it (int64), and f_score_max (T, len(ns), B).
+    No gradient.  Runs on csrc/mesh_eval.hip (no (N B, V, V) tensor exists); HIP tensors only (MheError otherwise).  ValueError, before
+    anything touches the device, for a missing 'verts' on either side, B or V that disagree, V outside 1..778, no thresholds or more than 4,
+    a threshold that is not positive, ns outside 1..N."""
+    return _mesh_eval("mesh_eval", output, target, thresholds, aligned, ns)
+
+
+def _mesh_eval(who, output, target, thresholds, aligned, ns):
+    pv, tv, scale, thr, ns = _mesh_operands(who, output, target, thresholds, ns)
+    with torch.no_grad():
+        pv, tv, scale = pv.float().contiguous(), tv.float().contiguous(), scale.float().contiguous()
+        if aligned:
+            pv = ops.procrustes_align(pv, tv)
+        err, prf = ops.mesh_eval(pv, tv, scale, thr, MESH_UNIT)
+        res = {"mesh_err": err, "precision": prf[0], "recall": prf[1], "f_score": prf[2]}
+        if ns is not None:
+            N, B = err.shape
+            val, idx = _min_first_n(err.t().contiguous(), ns)
+            res["mesh_err_min"], res["mesh_err_index"] = val.t().contiguous(), idx.t().long()
+            fmax, _ = _min_first_n(prf[2].permute(0, 2, 1).neg().reshape(-1, N), ns)          # max F = -min(-F)
+            res["f_score_max"] = fmax.neg().view(len(thr), B, len(ns)).permute(0, 2, 1).contiguous()
+    return res
+
+
+def mesh_select(output, target, Q=1, aligned=False):
+    """chamfer_select with the ground truth: keep, per image, the Q hypotheses of a sample() output whose mesh has the least mesh_err (mesh_eval;
+    aligned as there), least first, ties to the lower n - the oracle selection that best-of-n tables are made from.  Every (N, B, ...) tensor of
+    `output` is cut to (Q, B, ...); 'faces' and 'image' pass through.  Added: 'mesh_err' (Q, B), in mm, and 'mesh_err_index' (Q, B) int64."""
+    if "verts" not in output:
+        raise ValueError("mesh_select: output has no 'verts'")
+    _select_shape("mesh_select", "verts", output["verts"], Q)
+    return _cut(output, _mesh_eval("mesh_select", output, target, (5.0,), aligned, None)["mesh_err"], Q, "mesh_err")
 
 
 def silhouette_mask_checks(hand_mask, B, size, who="silhouette_dist"):

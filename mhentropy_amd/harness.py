@@ -152,6 +152,24 @@ def mhent_cfgs_from_config(cfg, tables=None, compute_dtype=torch.float32):
     return special, common
 
 
+MESH_SCALARS = tuple(k + s for s in ("", "_best") for k in ("mesh_err", "mesh_err_pa", "f5", "f15", "f5_pa", "f15_pa"))
+
+
+def mesh_scalars(out, y):
+    """the HO3D mesh protocol of one metrics pass (run --mesh-metrics): criteria.mesh_eval of out['verts'] against y['verts'] at 5 and 15 mm, plain
+    and Procrustes-aligned (_pa), with ns = [1, N] -> {name: float} for MESH_SCALARS: the mean over hypotheses and images of the vertex error
+    (mm) and of the two F-scores, and under `_best` the mean over images of the best of the N hypotheses (least error, largest F-score)."""
+    from .criteria import mesh_eval
+    N = out["verts"].shape[0]
+    res = {}
+    for sfx, aligned in (("", False), ("_pa", True)):
+        m = mesh_eval(out, y, thresholds=(5.0, 15.0), aligned=aligned, ns=sorted({1, N}))
+        res["mesh_err" + sfx], res["mesh_err" + sfx + "_best"] = m["mesh_err"].mean(), m["mesh_err_min"][-1].mean()
+        for t, name in enumerate(("f5", "f15")):
+            res[name + sfx], res[name + sfx + "_best"] = m["f_score"][t].mean(), m["f_score_max"][t, -1].mean()
+    return {k: float(res[k]) for k in MESH_SCALARS}
+
+
 class ScalarLog:
     """the scalars the reference sends to TensorBoard (hand/CrossModalHand.py:486-564), under its tags: `loss_it/*`, `metric_it/*`,
     `loss_avg/loss_total`, `metric_train|eval/eval_3d_rgb` (x1000), `param/{beta,theta}_norm`.  Written as JSON lines, and to a
@@ -184,6 +202,11 @@ class ScalarLog:
         for name, key in (("theta", "th_norm"), ("beta", "bt_norm")):
             if key in out:
                 self.add_scalar(f"param/{name}_norm", out[key].mean(), step)
+
+    def mesh(self, step, scalars):
+        """the mesh metrics of one iteration (mesh_scalars), under `metric_it/<name>` like the other per-iteration metrics"""
+        for k, v in scalars.items():
+            self.add_scalar(f"metric_it/{k}", v, step)
 
     def epoch(self, step, loss_avg, eval_3d_avg, train=True):
         """hand/CrossModalHand.py:557-564"""

@@ -709,7 +709,29 @@ def chamfer_bwd(points, scale, root, obj, count, idx_p, idx_o, g_dist, unit=1000
     return g_points
 
 
-SILHOUETTE_MAX_SIZE, SILHOUETTE_MAX_VERTS = 64, 778          # MHE_SILHOUETTE_MAX_SIZE / _MAX_VERTS of include/mhe.h
+MESH_EVAL_MAX_VERTS, MESH_EVAL_MAX_THRESHOLDS = 778, 4         # MHE_CHAMFER_MAX_POINTS / MHE_MESH_EVAL_MAX_THRESHOLDS of include/mhe.h
+
+
+def mesh_eval(pred, target, scale, thresholds, unit=1000.0):
+    """hand mesh evaluation (include/mhe.h, mhe_mesh_eval_f32): pred [N,B,V,3], target [B,V,3], scale [B], thresholds = 1 to 4 numbers in the
+    output's unit (unit 1000: mm) -> err [N,B], the mean vertex-to-vertex distance by correspondence, and prf [3,T,N,B] = (precision, recall,
+    F-score) of the two vertex sets at every threshold (nearest distance strictly below it)"""
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 4 or pred.shape[-1] != 3:
+        raise _lib.MheError("mesh_eval.pred: expected an [N,B,V,3] tensor")
+    N, B, V = pred.shape[:3]
+    _chk(pred, torch.float32, "mesh_eval.pred"); _chk(target, torch.float32, "mesh_eval.target", (B, V, 3)); _chk(scale, torch.float32, "mesh_eval.scale", (B,))
+    thr = [float(t) for t in thresholds]
+    T = len(thr)
+    if not 1 <= T <= MESH_EVAL_MAX_THRESHOLDS:
+        raise _lib.MheError(f"mesh_eval.thresholds: {T} thresholds (1..{MESH_EVAL_MAX_THRESHOLDS})")
+    err = torch.empty(N, B, device=pred.device, dtype=torch.float32)
+    prf = torch.empty(3, T, N, B, device=pred.device, dtype=torch.float32)
+    arr = (C.c_float * T)(*thr)
+    launch("mhe_mesh_eval_f32", pred, target, scale, C.cast(arr, C.c_void_p), err, prf, N, B, V, T, float(unit))
+    return err, prf
+
+
+SILHOUETTE_MAX_SIZE, SILHOUETTE_MAX_VERTS = 64, 778         # MHE_SILHOUETTE_MAX_SIZE / _MAX_VERTS of include/mhe.h
 
 
 def silhouette_pixels(hand_mask, size=64, occluder=None):

@@ -10,6 +10,7 @@ on synthetic batches (no dataset ships with this repository; the HO3D pipeline i
     python -m mhentropy_amd.run --sil-w 1 ...            # with the silhouette term (the mesh against the hand mask, MHEnt.get_loss(sil_w=...))
     python -m mhentropy_amd.run --sil-w 1 --sil-occluder ...   # ... with the object's mask as the term's occluder (get_loss(sil_occluder=True))
     python -m mhentropy_amd.run --test-samples 200 --quant-samples 10 --quant kmeans ...      # metrics of 10 k-means modes of 200 hypotheses
+    python -m mhentropy_amd.run --test-samples 200 --mesh-metrics ...       # HO3D mesh protocol: vertex error, F@5 / F@15 mm, aligned, best of N
 """
 import argparse
 import json
@@ -74,6 +75,11 @@ def main(argv=None):
                     help="the silhouette term takes the object's mask as its occluder (MHEnt.get_loss(sil_occluder=True): a vertex behind the "
                          "object costs nothing, the object attracts nothing).  A synthetic disc or box over part of the hand mask, cut out of "
                          "it (synth.object_masks), by default, the pipeline's object_mask under --input-pipeline; needs --sil-w > 0")
+    ap.add_argument("--mesh-metrics", action="store_true",
+                    help="evaluate the meshes of the --test-samples metrics pass by the HO3D mesh protocol (criteria.mesh_eval: vertex error in mm "
+                         "and F-score at 5 and 15 mm, plain and Procrustes-aligned, mean and best of N) and report them as mesh_err, mesh_err_pa, "
+                         "f5, f15, f5_pa, f15_pa and *_best (the scalars log: metric_it/<name>).  The target mesh is the mesh of a seeded "
+                         "ground-truth pose (synth.mesh_pose) by default, the pipeline's verts under --input-pipeline; needs --test-samples > 0")
     args = ap.parse_args(argv)
     if args.chamfer_w < 0:
         raise SystemExit("--chamfer-w must be >= 0")
@@ -94,6 +100,8 @@ def main(argv=None):
         args.test_samples = cfg.training.get("test_samples", args.test_samples)
     if args.quant_samples > args.test_samples:
         raise SystemExit(f"--quant-samples {args.quant_samples} is more than the {args.test_samples} hypotheses of --test-samples")
+    if args.mesh_metrics and not args.test_samples > 0:
+        raise SystemExit("--mesh-metrics needs --test-samples > 0 (the meshes come from the metrics pass)")
 
     rank, local_rank, world, dist = mdist.init()
     if not torch.cuda.is_available():
@@ -120,6 +128,8 @@ def main(argv=None):
     trainer = TrainStep(model, lr=args.lr, max_norm=1.0, dist=dist)
     criterion = MHEntLoss(aligned=args.aligned)
     meters = {"loss": harness.AverageMeter(), "epe3d": harness.AverageMeter(), "epe2d": harness.AverageMeter()}
+    if args.mesh_metrics:
+        meters.update({k: harness.AverageMeter() for k in harness.MESH_SCALARS})
     step, log = 0, []
     graphed, graphed_lr, sx, sy = None, None, None, None
     if args.input_pipeline:
@@ -151,6 +161,9 @@ def main(argv=None):
                 if args.sil_occluder:
                     yn["hand_mask"], yn["object_mask"] = synth.object_masks(args.seed + 1000 * rank + step, yn["hand_mask"])
                 y = {k: torch.as_tensor(v).cuda() for k, v in yn.items()}
+                if args.mesh_metrics:
+                    with torch.no_grad():          # the mesh of the seeded ground-truth pose, normalised like the hypotheses' meshes
+                        y["verts"] = model.mano_dec.verts(torch.as_tensor(synth.mesh_pose(args.seed + 1000 * rank + step, args.batch)).cuda())
             model.training_step_start(step)
             if args.graph and not args.test_samples:
                 from .train import GraphedStep
@@ -178,6 +191,12 @@ def main(argv=None):
             it_losses.append(float(total))
             if scalars is not None:
                 scalars.iteration(step, losses, metrics, out)
+            if args.mesh_metrics:
+                ms = harness.mesh_scalars(out, y)
+                for k, v in ms.items():
+                    meters[k].update(v)
+                if scalars is not None:
+                    scalars.mesh(step, ms)
             if args.test_samples:
                 meters["epe3d"].update(float(metrics["eucLoss_3d_rgb_sample"].mean()))
                 meters["epe2d"].update(float(metrics["eucLoss_2d_rgb_sample"].mean()))

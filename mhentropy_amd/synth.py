@@ -185,6 +185,17 @@ def object_targets(seed=0, B=2, VO=256, with_count=False):
     return y
 
 
+def mesh_pose(seed=0, B=2):
+    """Seeded ground-truth hand poses of B images for the mesh metrics (criteria.mesh_eval): z (B, 61) = 48 pose coefficients (global rotation
+    and the 45 PCA coefficients, the spread a trained flow samples with), 10 shape coefficients and a zero camera, the row layout of
+    ManoLayer.verts - whose mesh of these rows is the batch's target['verts']."""
+    rng = np.random.default_rng(seed + 5300)
+    z = np.zeros((B, 61), np.float32)
+    z[:, :48] = rng.normal(0.0, 0.5, (B, 48))
+    z[:, 48:58] = rng.normal(0.0, 0.5, (B, 10))
+    return z
+
+
 def hand_masks(seed=0, B=2, H=64, crop_uv=None, image_size=256, with_image=True):
     """Seeded hand masks (B, H, H) bool for the silhouette term (get_loss(sil_w=...), criteria.silhouette_dist), taken from the same seed's
     batch() target so that the mask lies where the hand is (a random blob would only drag the camera): the union of the discs of radius 0.08,
