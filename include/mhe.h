@@ -1157,6 +1157,45 @@ int mhe_silhouette_dist_bwd_occ_f32(const float *verts, const float *logs_t, con
 int mhe_silhouette_dist_grad_occ_f32(const float *verts, const float *logs_t, const int *pixels, const int *count, const int *count_all,
                                      const float *g_dist, float *dist, float *g_verts, float *g_logs_t, int N, int B, int V, int S, void *stream);
 
+/* Depth agreement of the hand mesh with the depth image, and its reverse (csrc/depth_dist.hip; the reference has no counterpart - the contract
+ * below is this project's own).  Normalised image coordinates and rasteriser of mhe_render_mesh_f32 without anti-aliasing: sample (row i, col j)
+ * of the S x S grid sits at ((2j+1)/S - 1, (2i+1)/S - 1), the camera is p = exp(log s) v_xy + t, a vertex is projected in f64 and rounded once
+ * to f32 sample units, edge functions and the depth plane (clamped to the face's range) are f64; a face with an index outside [0,V) is skipped,
+ * never read, a face of zero projected area covers nothing.  Rows are sample-major, r = n B + b, row r uses image b = r % B.
+ * mhe_depth_dist_f32: verts [R,V,3], faces [F,3] int32, logs_t [R,3] = (log s, tx, ty), zscale [B] (metres per normalised unit), obs [B,S,S]
+ *   (metres; a value <= 0 or non-finite is "no observation"), root_z [B] or NULL, trunc > 0 -> dist [R]; optional parts [R,3] = (overlap,
+ *   offset, inliers), face_img [R,S,S] int32, resid_img [R,S,S].
+ *     R(p)  = the f32 depth v_z zscale[b] of the nearest covering face at sample p, the lowest face index among equal f32 depths; C = the
+ *             covered samples, f(p) the winning face; O = the observed samples; P = C n O
+ *     off   = root_z[b], or with root_z NULL the mean over P of obs - R (0 when P is empty)
+ *     e(p)  = R(p) + off - obs(p) on P
+ *     dist  = (sum_P min(|e|, trunc) + trunc |O \ C|) / |O|, in [0, trunc]; 0 when O is empty
+ *     parts = (|P| / |O| or 0 when O is empty, off, share of P with |e| < trunc or 0 when P is empty)
+ *     face_img = f(p), -1 outside C;  resid_img = e(p) rounded to f32, NaN outside P
+ *   A row with a non-finite projected vertex, zscale or root_z: dist and parts NaN, face_img -1, resid_img NaN; other rows are not disturbed.
+ * mhe_depth_dist_bwd_f32: the same operands, vf_start [V+1] and vf_list [3F] int32 (the vertex -> face table: entries vf_start[v] ..
+ *   vf_start[v+1]-1 of vf_list are (face << 2) | corner for every corner of a face that is vertex v, ascending; the rest of the list is -1;
+ *   ops.face_adjacency builds it), g_dist [R] -> g_verts [R,V,3], g_logs_t [R,3].  It rasterises again; coverage and face assignment are held
+ *   fixed.  With s(p) = sign(e) [|e| < trunc] on P, the weight of a sample is g(p) = g_dist[r] s(p) / |O| with root_z and
+ *   g_dist[r] (s(p) - mean_P s) / |O| without (the offset moves with the mesh); with w_k(p) the barycentric weights of f(p) = (a, b, c) and
+ *   (gx, gy) its depth-plane slopes per sample,
+ *     dR/dz_k = w_k zscale,  dR/dX_k = -gx w_k,  dR/dY_k = -gy w_k;   X = (s v_x + t_x) S/2 + S/2 - 1/2:  dX/dv_x = s S/2, dX/dt_x = S/2,
+ *     dX/dlog s = s v_x S/2, and Y alike.  The clamp of the depth plane is ignored.
+ *   Zeros for a row whose P is empty and for a NaN row.  An entry of the table outside its range contributes nothing and is never an address.
+ * Both: one workgroup per row, 61.3 KiB of LDS (two workgroups per CU); the z-image is a 64-bit integer minimum in LDS, every sum is f64 in a
+ *   fixed order, no floating-point atomics, no allocation, no workspace, no host read: two calls give the same bits, a row's bits do not depend
+ *   on the other rows, and the calls can be captured into a HIP graph.  MHE_ERR_ARG before any launch for a null pointer (the optional ones
+ *   excepted), N, B < 1 or N B >= 2^31, V, F or S outside the limits below, trunc not positive and finite, or outputs that overlap inputs or
+ *   each other. */
+#define MHE_DEPTH_MAX_SIZE 64
+#define MHE_DEPTH_MAX_VERTS 1024
+#define MHE_DEPTH_MAX_FACES 2048
+int mhe_depth_dist_f32(const float *verts, const int *faces, const float *logs_t, const float *zscale, const float *obs, const float *root_z,
+                       float trunc, float *dist, float *parts, int *face_img, float *resid_img, int N, int B, int V, int F, int S, void *stream);
+int mhe_depth_dist_bwd_f32(const float *verts, const int *faces, const float *logs_t, const float *zscale, const float *obs, const float *root_z,
+                           float trunc, const int *vf_start, const int *vf_list, const float *g_dist, float *g_verts, float *g_logs_t, int N, int B,
+                           int V, int F, int S, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

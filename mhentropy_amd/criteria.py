@@ -350,6 +350,124 @@ def silhouette_select(output, target, Q=1, size=64, occluder=False):
     return _cut(output, dist, Q, "silhouette")
 
 
+def _depth_operands(who, verts, logs_t, faces, depth, hand_mask, scale, root_z, size, trunc):
+    """the checks of depth_dist that need no device -> (verts [N,B,V,3], logs_t [N,B,3], faces [F,3] int32, depth, hand_mask, scale [B],
+    root_z [B] | None)"""
+    if not isinstance(verts, torch.Tensor) or verts.dim() not in (3, 4) or (verts.dim() == 4 and verts.shape[-1] != 3) or verts[0, 0].numel() % 3:
+        raise ValueError(f"{who}: verts must be (N, B, V*3) or (N, B, V, 3), got {tuple(getattr(verts, 'shape', ()))}")
+    N, B = verts.shape[:2]
+    V = verts[0, 0].numel() // 3
+    if not 1 <= V <= ops.DEPTH_MAX_VERTS:
+        raise ValueError(f"{who}: V={V} vertices per hypothesis (1..{ops.DEPTH_MAX_VERTS})")
+    if not isinstance(logs_t, torch.Tensor) or tuple(logs_t.shape) != (N, B, 3):
+        raise ValueError(f"{who}: logs_t must be (N, B, 3) = ({N}, {B}, 3), got {tuple(getattr(logs_t, 'shape', ()))}")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.is_floating_point() or \
+            not 1 <= faces.shape[0] <= ops.DEPTH_MAX_FACES:
+        raise ValueError(f"{who}: faces must be an integer (F, 3) tensor with F in 1..{ops.DEPTH_MAX_FACES}, got "
+                         f"{tuple(getattr(faces, 'shape', ()))} {getattr(faces, 'dtype', None)}")
+    if not isinstance(size, int) or not 1 <= size <= ops.DEPTH_MAX_SIZE:
+        raise ValueError(f"{who}: size={size!r} (1..{ops.DEPTH_MAX_SIZE})")
+    for name, img in (("depth", depth), ("hand_mask", hand_mask)):
+        if not isinstance(img, torch.Tensor) or img.dim() != 3 or img.shape[0] != B or img.shape[1] != img.shape[2]:
+            raise ValueError(f"{who}: {name} must be (B, H, H) with B={B}, got {tuple(getattr(img, 'shape', ()))}")
+    if tuple(hand_mask.shape) != tuple(depth.shape):
+        raise ValueError(f"{who}: hand_mask is {tuple(hand_mask.shape)}, depth {tuple(depth.shape)}")
+    H = depth.shape[1]
+    if H < size or H % size:
+        raise ValueError(f"{who}: depth is {H} x {H}, not a multiple of size={size}")
+    if not isinstance(scale, torch.Tensor) or tuple(scale.shape) != (B,):
+        raise ValueError(f"{who}: scale must be (B,) = ({B},), got {tuple(getattr(scale, 'shape', ()))}")
+    if root_z is not None and (not isinstance(root_z, torch.Tensor) or tuple(root_z.shape) != (B,)):
+        raise ValueError(f"{who}: root_z must be (B,) = ({B},) or None, got {tuple(getattr(root_z, 'shape', ()))}")
+    if isinstance(trunc, bool) or not isinstance(trunc, (int, float)) or not 0 < trunc < float("inf"):
+        raise ValueError(f"{who}: trunc={trunc!r} (a positive, finite number)")
+    if faces.dtype != torch.int32:          # (sample()'s output['faces'] is int64: converted once per tensor and kept beside it, with its adjacency)
+        kept = getattr(faces, "_mhe_i32", None)
+        if kept is None or kept[0] != faces._version:
+            kept = (faces._version, faces.to(torch.int32).contiguous())
+            faces._mhe_i32 = kept
+        faces = kept[1]
+    return (verts.reshape(N, B, V, 3).float().contiguous(), logs_t.float().contiguous(), faces.contiguous(), depth, hand_mask,
+            scale.detach().float().contiguous(), None if root_z is None else root_z.detach().float().contiguous())
+
+
+class _Depth(torch.autograd.Function):
+    """(dist, parts) of ops.depth_dist; the gradient of dist reaches verts and logs_t (parts is returned for reading only).  Only the inputs are
+    saved: the reverse rasterises again."""
+    @staticmethod
+    def forward(ctx, verts, logs_t, faces, zscale, obs, root_z, trunc, adjacency):
+        dist, parts = ops.depth_dist(verts, faces, logs_t, zscale, obs, root_z, trunc)
+        ctx.save_for_backward(verts, logs_t, faces, zscale, obs, *(() if root_z is None else (root_z,)), *adjacency)
+        ctx.trunc, ctx.root = trunc, root_z is not None
+        ctx.mark_non_differentiable(parts)
+        return dist, parts
+
+    @staticmethod
+    def backward(ctx, g_dist, _g_parts):
+        saved = ctx.saved_tensors
+        verts, logs_t, faces, zscale, obs = saved[:5]
+        root_z = saved[5] if ctx.root else None
+        g_verts, g_logs_t = ops.depth_dist_bwd(verts, faces, logs_t, zscale, obs, root_z, ctx.trunc, g_dist.contiguous(), adjacency=tuple(saved[-2:]))
+        return g_verts, g_logs_t, None, None, None, None, None, None
+
+
+def depth_dist(verts, logs_t, faces, depth, hand_mask, scale, root_z=None, size=64, trunc=0.05, parts=False):
+    """Depth agreement of every hypothesis' mesh with its image's depth crop: verts (N, B, V*3) or (N, B, V, 3) and logs_t (N, B, 3) =
+    (log s, tx, ty) of a sample() output, faces (F, 3) (ManoLayer's `mano_layer.faces_i32`; an int64 tensor is converted once and the copy kept on it), depth
+    (B, H, H) in metres, 0 where the sensor saw nothing, and hand_mask (B, H, H) (the input pipeline's target['depth'] and target['hand_mask']),
+    scale (B,) metres per normalised unit (target['scale']) -> (N, B) f32, in metres; with parts=True (dist, overlap, offset, inliers).
+    In the normalised image coordinates of silhouette_iou, one sample per pixel of the size x size grid (H a multiple of size):
+        R(p)   the mesh rendered under p = exp(log s) v_xy + t with depth v_z scale[b]: nearest covering face, lowest face index among equals
+        obs    ops.depth_obs: depth sampled at each block's centre, valid where the hand mask's box mean is >= 0.5 and the sample is finite and > 0
+        off    root_z[b] (target['pose3d_root'][:, 2]) - or, with root_z=None, the mean of obs - R over the compared samples, fitted per
+               hypothesis: no ground truth is needed, so this is the mode for selection at test time
+        dist   (sum over the compared samples of min(|R + off - obs|, trunc) + trunc x the observed samples the mesh does not cover) / the observed
+               samples: a truncated L1 over every observed hand pixel, in [0, trunc]
+        overlap = compared / observed samples, offset = off, inliers = the share of the compared samples with |R + off - obs| < trunc
+    An image with no observed sample gives 0 and a zero gradient, a row with a non-finite projected vertex, scale or root_z NaN and a zero
+    gradient.  Differentiable with respect to verts and logs_t with coverage and face assignment held fixed (truncated and uncovered samples
+    contribute nothing; with the fitted offset the weights are centred, because the offset moves with the mesh); depth, hand_mask, scale and
+    root_z get no gradient, the parts are returned detached.  Runs on csrc/depth_dist.hip: one number per hypothesis leaves the kernel, no
+    image tensor exists; forward and reverse are bit-reproducible; nothing is read on the host once ops.face_adjacency(faces) has been built
+    (the first call with a faces tensor), so the call can be captured into a HIP graph.  HIP tensors only (MheError otherwise); ValueError for
+    a bad rank or shape, H not a multiple of size, V, F or size outside 1..1024 / 1..2048 / 1..64, trunc not positive - before any launch."""
+    v, lt, f, depth, hand_mask, zs, rz = _depth_operands("depth_dist", verts, logs_t, faces, depth, hand_mask, scale, root_z, size, trunc)
+    if not (v.is_cuda and f.is_cuda):
+        raise ops._lib.MheError("depth_dist: expected CUDA/HIP tensors (the hot path has no CPU fallback)")
+    with torch.no_grad():
+        obs = ops.depth_obs(depth, hand_mask, size)
+        adjacency = ops.face_adjacency(f, v.shape[2])
+    dist, pt = _Depth.apply(v, lt, f, zs, obs, rz, float(trunc), adjacency)
+    return (dist, pt[..., 0], pt[..., 1], pt[..., 2]) if parts else dist
+
+
+def depth_select(output, target, Q=1, size=64, trunc=0.05, root=False):
+    """chamfer_select with depth_dist: keep, per image, the Q hypotheses of a sample() output whose mesh (output['verts'] under
+    output['logs_t'], triangulated by output['faces']) agrees best with target['depth'] on target['hand_mask'] (scale from target['scale']),
+    best first, ties to the lower n.  root=False fits the depth offset per hypothesis (no ground truth), root=True reads
+    target['pose3d_root'][:, 2].  Every (N, B, ...) tensor of `output` is cut to (Q, B, ...); 'faces' and 'image' pass through.  Added:
+    'depth_dist' (Q, B), the distances in metres, and 'depth_index' (Q, B) int64."""
+    for k in ("verts", "logs_t", "faces"):
+        if k not in output:
+            raise ValueError(f"depth_select: output has no {k!r}")
+    for k in ("depth", "hand_mask", "scale") + (("pose3d_root",) if root else ()):
+        if k not in target:
+            raise ValueError(f"depth_select{'(root=True)' if k == 'pose3d_root' else ''}: target has no {k!r}")
+    N, B = _select_shape("depth_select", "verts", output["verts"], Q)
+    root_z = None
+    if root:
+        pr = target["pose3d_root"]
+        if not isinstance(pr, torch.Tensor) or tuple(pr.shape) != (B, 3):
+            raise ValueError(f"depth_select: target['pose3d_root'] must be (B, 3) = ({B}, 3), got {tuple(getattr(pr, 'shape', ()))}")
+        root_z = pr[:, 2]
+    with torch.no_grad():
+        dist = depth_dist(output["verts"].detach(), output["logs_t"].detach(), output["faces"], target["depth"], target["hand_mask"], target["scale"],
+                          root_z=root_z, size=size, trunc=trunc)
+    out = _cut(output, dist, Q, "depth_dist")
+    out["depth_index"] = out.pop("depth_dist_index")
+    return out
+
+
 def kmeans_select(output, Q, points="xyz", iters=10, score=None):
     """Summarise a sample() output by Q distinct, weighted hypotheses per image (the n-quantised-best-of-M protocol): the N hypotheses are
     clustered by k-means on output[points] ('xyz', the joints, or 'verts', the mesh) and each cluster is kept as its member nearest the

@@ -170,6 +170,23 @@ def mesh_scalars(out, y):
     return {k: float(res[k]) for k in MESH_SCALARS}
 
 
+DEPTH_SCALARS = ("depth_dist", "depth_dist_best", "depth_mpjpe")
+
+
+def depth_scalars(out, y, size=64, trunc=0.05):
+    """the depth agreement of one metrics pass (run --depth-metrics): criteria.depth_dist of out['verts'] under out['logs_t'] against y['depth'] on
+    y['hand_mask'], the offset fitted per hypothesis (no ground truth) -> {name: float} for DEPTH_SCALARS: the mean over images of the
+    distance (metres) of the top hypothesis (n = 0) and of the best of the N, and the MPJPE (mm, out['xyz'] against y['pose3d'] scaled by
+    y['scale']) of the hypothesis the depth selects - what criteria.depth_select(Q=1) keeps."""
+    from .criteria import _rank, depth_dist
+    d = depth_dist(out["verts"].detach(), out["logs_t"].detach(), out["faces"], y["depth"], y["hand_mask"], y["scale"], size=size, trunc=trunc)
+    val, order = _rank(d)
+    B = d.shape[1]
+    picked = out["xyz"][order[0], torch.arange(B, device=d.device)].reshape(B, -1, 3)
+    err = (picked - y["pose3d"].reshape(B, -1, 3)).norm(dim=-1).mean(1) * y["scale"] * 1000.0
+    return {"depth_dist": float(d[0].mean()), "depth_dist_best": float(val[0].mean()), "depth_mpjpe": float(err.mean())}
+
+
 class ScalarLog:
     """the scalars the reference sends to TensorBoard (hand/CrossModalHand.py:486-564), under its tags: `loss_it/*`, `metric_it/*`,
     `loss_avg/loss_total`, `metric_train|eval/eval_3d_rgb` (x1000), `param/{beta,theta}_norm`.  Written as JSON lines, and to a

@@ -885,6 +885,107 @@ def render_mesh(verts, faces, scale, trans, zscale=None, size=64, anti_aliasing=
     return {k: v for k, v in o.items() if v is not None}
 
 
+DEPTH_MAX_SIZE, DEPTH_MAX_VERTS, DEPTH_MAX_FACES = 64, 1024, 2048         # MHE_DEPTH_MAX_SIZE / _MAX_VERTS / _MAX_FACES of include/mhe.h
+
+
+def depth_obs(depth, hand_mask, size=64):
+    """the observation image of depth_dist: depth [B,H,H] (metres, 0 where the sensor saw nothing) and hand_mask [B,H,H] (bool, uint8 or float
+    in [0,1]), H a multiple of size -> obs [B,size,size] f32.  With k = H / size, sample (i, j) is depth[b, i k + k//2, j k + k//2] (one sample,
+    never a mean: depth is not averaged across a discontinuity) where the box mean of the mask over the k x k block is >= 0.5 and the sample is
+    finite and > 0, and 0 elsewhere.  torch ops only, nothing is read back; works on any device."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or depth.shape[1] != depth.shape[2]:
+        raise ValueError(f"depth_obs: depth must be (B, H, H), got {tuple(getattr(depth, 'shape', ()))}")
+    if not isinstance(hand_mask, torch.Tensor) or tuple(hand_mask.shape) != tuple(depth.shape):
+        raise ValueError(f"depth_obs: hand_mask must be (B, H, H) = {tuple(depth.shape)} like depth, got {tuple(getattr(hand_mask, 'shape', ()))}")
+    B, H, S = depth.shape[0], depth.shape[1], size
+    if not isinstance(S, int) or not 1 <= S <= DEPTH_MAX_SIZE:
+        raise ValueError(f"depth_obs: size={S!r} (1..{DEPTH_MAX_SIZE})")
+    if H < S or H % S:
+        raise ValueError(f"depth_obs: depth is {H} x {H}, not a multiple of size={S}")
+    k = H // S
+    sample = depth[:, k // 2::k, k // 2::k].float()
+    kept = hand_mask.view(B, S, k, S, k).to(torch.float64).sum((2, 4)) >= 0.5 * k * k
+    valid = kept & torch.isfinite(sample) & (sample > 0)
+    return torch.where(valid, sample, torch.zeros_like(sample)).contiguous()
+
+
+def face_adjacency(faces, V=None):
+    """the vertex -> face table mhe_depth_dist_bwd_f32 reads, built once per faces tensor on the host (and per in-place change of it; one host
+    read, so the first call must not fall into a stream capture) and kept on the tensor: faces [F,3] int32 -> (vf_start [V+1], vf_list [3F]) int32
+    on the faces' device.  Entries vf_start[v] .. vf_start[v+1]-1 of vf_list are (face << 2) | corner for every corner that is vertex v, ascending;
+    a face with an index outside [0,V) has no entry (the kernels skip it); the tail of the list is -1.  V: the vertex count, the highest index
+    + 1 when not given."""
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[-1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"face_adjacency: faces must be an (F, 3) int32 tensor, got {tuple(getattr(faces, 'shape', ()))} {getattr(faces, 'dtype', None)}")
+    cache = getattr(faces, "_mhe_adjacency", None)
+    if cache is None or cache[0] != faces._version:
+        cache = (faces._version, {})
+        faces._mhe_adjacency = cache
+    if V is None:
+        V = max(int(faces.max()) + 1, 1)
+    if V not in cache[1]:
+        f = faces.detach().cpu().numpy().astype(np.int64)
+        ok = ((f >= 0) & (f < V)).all(1)
+        ent = (np.arange(f.shape[0])[:, None] * 4 + np.arange(3)[None, :])[ok].reshape(-1)
+        vert = f[ok].reshape(-1)
+        order = np.argsort(vert, kind="stable")          # entries ascend already: a stable sort by vertex keeps them so
+        start = np.concatenate([[0], np.cumsum(np.bincount(vert, minlength=V))]).astype(np.int32)
+        lst = np.full(3 * f.shape[0], -1, np.int32)
+        lst[:ent.size] = ent[order]
+        cache[1][V] = (torch.as_tensor(start).to(faces.device), torch.as_tensor(lst).to(faces.device))
+    return cache[1][V]
+
+
+def _depth_operands(who, verts, faces, logs_t, zscale, obs, root_z, trunc):
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 4 or verts.shape[-1] != 3:
+        raise _lib.MheError(f"{who}.verts: expected an [N,B,V,3] tensor")
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[-1] != 3:
+        raise _lib.MheError(f"{who}.faces: expected an [F,3] tensor")
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[1] != obs.shape[2]:
+        raise _lib.MheError(f"{who}.obs: expected a [B,size,size] tensor")
+    N, B, V = verts.shape[:3]
+    F, S = faces.shape[0], obs.shape[1]
+    if N < 1 or B < 1 or not 1 <= V <= DEPTH_MAX_VERTS or not 1 <= F <= DEPTH_MAX_FACES or not 1 <= S <= DEPTH_MAX_SIZE:
+        raise ValueError(f"{who}: N={N} B={B} V={V} F={F} size={S} (N, B >= 1, V in 1..{DEPTH_MAX_VERTS}, F in 1..{DEPTH_MAX_FACES}, "
+                         f"size in 1..{DEPTH_MAX_SIZE})")
+    if not float(trunc) > 0 or float(trunc) == float("inf"):
+        raise ValueError(f"{who}: trunc={trunc!r} (positive and finite)")
+    _chk(verts, torch.float32, f"{who}.verts"); _chk(faces, torch.int32, f"{who}.faces"); _chk(logs_t, torch.float32, f"{who}.logs_t", (N, B, 3))
+    _chk(zscale, torch.float32, f"{who}.zscale", (B,)); _chk(obs, torch.float32, f"{who}.obs", (B, S, S))
+    if root_z is not None:
+        _chk(root_z, torch.float32, f"{who}.root_z", (B,))
+    return N, B, V, F, S
+
+
+def depth_dist(verts, faces, logs_t, zscale, obs, root_z=None, trunc=0.05, want_images=False):
+    """depth agreement of every hypothesis' rendered mesh with its image's observed depth (include/mhe.h, mhe_depth_dist_f32, whose comment is the
+    contract): verts [N,B,V,3], faces [F,3] int32, logs_t [N,B,3] = (log s, tx, ty), zscale [B] (metres per normalised unit), obs [B,size,size]
+    of depth_obs, root_z [B] or None (the offset is then fitted per hypothesis) -> dist [N,B] in metres, parts [N,B,3] = (overlap, offset,
+    inliers); want_images: also face_img [N,B,size,size] int32 (-1 where nothing covers) and resid_img [N,B,size,size] (NaN outside the
+    compared set), which exist for tests and debugging - the product path writes no image."""
+    N, B, V, F, S = _depth_operands("depth_dist", verts, faces, logs_t, zscale, obs, root_z, trunc)
+    dev = verts.device
+    dist = torch.empty(N, B, device=dev, dtype=torch.float32)
+    parts = torch.empty(N, B, 3, device=dev, dtype=torch.float32)
+    face_img = torch.empty(N, B, S, S, device=dev, dtype=torch.int32) if want_images else None
+    resid_img = torch.empty(N, B, S, S, device=dev, dtype=torch.float32) if want_images else None
+    launch("mhe_depth_dist_f32", verts, faces, logs_t, zscale, obs, root_z, float(trunc), dist, parts, face_img, resid_img, N, B, V, F, S)
+    return (dist, parts, face_img, resid_img) if want_images else (dist, parts)
+
+
+def depth_dist_bwd(verts, faces, logs_t, zscale, obs, root_z, trunc, g_dist, adjacency=None):
+    """reverse of depth_dist's dist (mhe_depth_dist_bwd_f32): the forward call's operands, g_dist [N,B] -> g_verts [N,B,V,3], g_logs_t [N,B,3].
+    It rasterises again - nothing of the forward call is kept - and is bit-reproducible.  adjacency: face_adjacency(faces, V), looked up (and
+    built on first use) when not given."""
+    N, B, V, F, S = _depth_operands("depth_dist_bwd", verts, faces, logs_t, zscale, obs, root_z, trunc)
+    _chk(g_dist, torch.float32, "depth_dist_bwd.g_dist", (N, B))
+    vf_start, vf_list = face_adjacency(faces, V) if adjacency is None else adjacency
+    _chk(vf_start, torch.int32, "depth_dist_bwd.vf_start", (V + 1,)); _chk(vf_list, torch.int32, "depth_dist_bwd.vf_list", (3 * F,))
+    g_verts, g_logs_t = torch.empty_like(verts), torch.empty_like(logs_t)
+    launch("mhe_depth_dist_bwd_f32", verts, faces, logs_t, zscale, obs, root_z, float(trunc), vf_start, vf_list, g_dist, g_verts, g_logs_t, N, B, V, F, S)
+    return g_verts, g_logs_t
+
+
 def conv2d_nhwc(x, w, KH, KW, stride, pad, in_scale=None, in_shift=None, relu_in=False, out_scale=None,
                 out_shift=None, residual=None, relu_out=False, stats=None, out=None, mask=None, bn=None, tile=0, res_half=False, xcat=None,
                 mask_bits=None):

@@ -11,6 +11,7 @@ on synthetic batches (no dataset ships with this repository; the HO3D pipeline i
     python -m mhentropy_amd.run --sil-w 1 --sil-occluder ...   # ... with the object's mask as the term's occluder (get_loss(sil_occluder=True))
     python -m mhentropy_amd.run --test-samples 200 --quant-samples 10 --quant kmeans ...      # metrics of 10 k-means modes of 200 hypotheses
     python -m mhentropy_amd.run --test-samples 200 --mesh-metrics ...       # HO3D mesh protocol: vertex error, F@5 / F@15 mm, aligned, best of N
+    python -m mhentropy_amd.run --test-samples 200 --depth-metrics ...      # depth agreement with the depth crop: top hypothesis, best of N, MPJPE of the pick
 """
 import argparse
 import json
@@ -80,6 +81,12 @@ def main(argv=None):
                          "and F-score at 5 and 15 mm, plain and Procrustes-aligned, mean and best of N) and report them as mesh_err, mesh_err_pa, "
                          "f5, f15, f5_pa, f15_pa and *_best (the scalars log: metric_it/<name>).  The target mesh is the mesh of a seeded "
                          "ground-truth pose (synth.mesh_pose) by default, the pipeline's verts under --input-pipeline; needs --test-samples > 0")
+    ap.add_argument("--depth-metrics", action="store_true",
+                    help="score the meshes of the --test-samples metrics pass against the depth crop (criteria.depth_dist, offset fitted per "
+                         "hypothesis) and report depth_dist (the top hypothesis, metres), depth_dist_best (best of N) and depth_mpjpe (the MPJPE "
+                         "in mm of the hypothesis the depth selects, next to epe3d) (the scalars log: metric_it/<name>).  The depth crop is "
+                         "rendered from the mesh of a seeded ground-truth pose (synth.depth_images) by default, the pipeline's depth and "
+                         "hand_mask under --input-pipeline; needs --test-samples > 0")
     args = ap.parse_args(argv)
     if args.chamfer_w < 0:
         raise SystemExit("--chamfer-w must be >= 0")
@@ -102,6 +109,8 @@ def main(argv=None):
         raise SystemExit(f"--quant-samples {args.quant_samples} is more than the {args.test_samples} hypotheses of --test-samples")
     if args.mesh_metrics and not args.test_samples > 0:
         raise SystemExit("--mesh-metrics needs --test-samples > 0 (the meshes come from the metrics pass)")
+    if args.depth_metrics and not args.test_samples > 0:
+        raise SystemExit("--depth-metrics needs --test-samples > 0 (the meshes come from the metrics pass)")
 
     rank, local_rank, world, dist = mdist.init()
     if not torch.cuda.is_available():
@@ -130,6 +139,8 @@ def main(argv=None):
     meters = {"loss": harness.AverageMeter(), "epe3d": harness.AverageMeter(), "epe2d": harness.AverageMeter()}
     if args.mesh_metrics:
         meters.update({k: harness.AverageMeter() for k in harness.MESH_SCALARS})
+    if args.depth_metrics:
+        meters.update({k: harness.AverageMeter() for k in harness.DEPTH_SCALARS})
     step, log = 0, []
     graphed, graphed_lr, sx, sy = None, None, None, None
     if args.input_pipeline:
@@ -161,9 +172,13 @@ def main(argv=None):
                 if args.sil_occluder:
                     yn["hand_mask"], yn["object_mask"] = synth.object_masks(args.seed + 1000 * rank + step, yn["hand_mask"])
                 y = {k: torch.as_tensor(v).cuda() for k, v in yn.items()}
-                if args.mesh_metrics:
+                if args.mesh_metrics or args.depth_metrics:
                     with torch.no_grad():          # the mesh of the seeded ground-truth pose, normalised like the hypotheses' meshes
                         y["verts"] = model.mano_dec.verts(torch.as_tensor(synth.mesh_pose(args.seed + 1000 * rank + step, args.batch)).cuda())
+                if args.depth_metrics:
+                    with torch.no_grad():          # ... and its depth crop under the target camera
+                        y.update(synth.depth_images(y, model.mano_dec.mano_layer.faces_i32, args.seed + 1000 * rank + step,
+                                                    scale=y["scale"] if args.chamfer_w > 0 else None))          # (the object targets' bone length)
             model.training_step_start(step)
             if args.graph and not args.test_samples:
                 from .train import GraphedStep
@@ -197,6 +212,13 @@ def main(argv=None):
                     meters[k].update(v)
                 if scalars is not None:
                     scalars.mesh(step, ms)
+            if args.depth_metrics:
+                with torch.no_grad():
+                    ds = harness.depth_scalars(out, y)
+                for k, v in ds.items():
+                    meters[k].update(v)
+                if scalars is not None:
+                    scalars.mesh(step, ds)
             if args.test_samples:
                 meters["epe3d"].update(float(metrics["eucLoss_3d_rgb_sample"].mean()))
                 meters["epe2d"].update(float(metrics["eucLoss_2d_rgb_sample"].mean()))

@@ -196,6 +196,30 @@ def mesh_pose(seed=0, B=2):
     return z
 
 
+def depth_images(target, faces, seed=0, H=64, scale=None):
+    """A depth crop and its hand mask for the depth criterion (criteria.depth_dist, run --depth-metrics) when no input pipeline decodes one: the
+    batch's target mesh target['verts'] (B, 778*3) or (B, 778, 3), normalised, rendered by ops.render_mesh (one sample per pixel) under the
+    target camera target['st'] = (s, tx, ty) with depth v_z scale, plus a seeded root depth of 0.4 .. 0.7 m -> {'depth': (B, H, H) metres, 0
+    where the mesh does not cover, 'hand_mask': (B, H, H) bool, 'pose3d_root': (B, 3), 'scale': (B,)} on the target's device (HIP tensors).
+    scale (B,): the bone length in m to use; None draws one of 0.025 .. 0.04 as object_targets() does - the returned 'scale' replaces
+    batch()'s (drawn there for the metrics, 0.5 .. 1.5, with which the mesh would span metres and reach behind the camera)."""
+    import torch
+    from . import ops
+    verts, st = target["verts"], target["st"].float()
+    B = st.shape[0]
+    rng = np.random.default_rng(seed + 5900)
+    root = torch.zeros(B, 3, device=st.device)
+    root[:, 2] = torch.as_tensor(rng.uniform(0.4, 0.7, B).astype(np.float32)).to(st.device)
+    if scale is None:
+        scale = torch.as_tensor(rng.uniform(0.025, 0.04, B).astype(np.float32)).to(st.device)
+    scale = scale.float().contiguous()
+    r = ops.render_mesh(verts.reshape(B, -1, 3).float().contiguous(), faces, st[:, 0].contiguous(), st[:, 1:].contiguous(),
+                        zscale=(scale * 1000.0).contiguous(), size=H, anti_aliasing=False, far=0.0, want=("mask", "depth"))
+    mask = r["mask"] > 0
+    return {"depth": torch.where(mask, r["depth"] + root[:, 2, None, None], torch.zeros_like(r["depth"])), "hand_mask": mask, "pose3d_root": root,
+            "scale": scale}
+
+
 def hand_masks(seed=0, B=2, H=64, crop_uv=None, image_size=256, with_image=True):
     """Seeded hand masks (B, H, H) bool for the silhouette term (get_loss(sil_w=...), criteria.silhouette_dist), taken from the same seed's
     batch() target so that the mask lies where the hand is (a random blob would only drag the camera): the union of the discs of radius 0.08,
