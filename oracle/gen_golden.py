@@ -366,11 +366,16 @@ HO3D_CASES = [(0, (0, 0), False), (0, (0, 0), True), (1, (250, -180), False), (1
               (3, (120, 60), True)]
 
 
-def gen_ho3d():
-    """row f4: the reference's `Generate_ho3d_uv.__getitem__` (hand/dataloader/ho3d_dataloader.py:272-459) on synthetic decoded
-    samples.  The module is imported from a scratch directory holding the (empty) dataset directories its import-time checks look
-    for; its file readers are pointed at the synthetic arrays, and the OpenCV / torchvision calls it makes are served by the
-    restatements of oracle/ho3d_ref.py (those primitives stay unpinned; the reference's own logic around them is what is pinned)."""
+_HO3D_REF = []
+
+
+def _ho3d_reference():
+    """the reference's HO3D dataloader module, set up once: imported from a scratch directory holding the (empty) dataset
+    directories its import-time checks look for; its file readers are pointed at the decoded arrays of cur["s"], and the OpenCV /
+    torchvision calls it makes are served by the restatements of oracle/ho3d_ref.py (those primitives stay unpinned; the
+    reference's own logic around them is what is pinned).  Returns (module, cur, run) with run(sample, aug) -> (image, target)."""
+    if _HO3D_REF:
+        return _HO3D_REF[0]
     import tempfile
     from oracle import ho3d_ref
     scratch = tempfile.mkdtemp(prefix="ho3d_ref_")
@@ -410,16 +415,28 @@ def gen_ho3d():
     hd.imageio.imread = lambda fn: cur["s"]["seg"] if fn.endswith(".png") else cur["s"]["image"]
     hd.read_depth_img = lambda *a: ho3d_ref.decode_depth(cur["s"]["depth_png"])
     hd.read_annotation = lambda *a: {"objName": "obj", "objRot": cur["s"]["obj_rot"], "objTrans": cur["s"]["obj_trans"], "camMat": cur["s"]["cam"]}
-    for ci, (seed, off, aug) in enumerate(HO3D_CASES):
-        smp = synth.ho3d_sample(seed, off)
+
+    def run(smp, aug):
         cur["s"] = smp
         ds = object.__new__(hd.Generate_ho3d_uv)
         ds.train_file, ds.baseDir, ds.model = np.array(["SEQ/0000"]), "", "train"
         ds.handJoints3D, ds.handMesh = smp["joints3d"][None], smp["mesh"][None]
         ds.objmesh_all = {"obj": {"v": smp["obj_verts"], "vn": smp["obj_verts"]}}
         ds.dpda, ds.aug, ds.joint_idx = "HO3D", aug, "RHD"
+        return ds[0]
+    _HO3D_REF.append((hd, cur, run))
+    return _HO3D_REF[0]
+
+
+def gen_ho3d():
+    """row f4: the reference's `Generate_ho3d_uv.__getitem__` (hand/dataloader/ho3d_dataloader.py:272-459) on synthetic decoded
+    samples (set-up: _ho3d_reference)."""
+    from oracle import ho3d_ref
+    _, _, run = _ho3d_reference()
+    for ci, (seed, off, aug) in enumerate(HO3D_CASES):
+        smp = synth.ho3d_sample(seed, off)
         np.random.seed(100 + seed)
-        img, tgt = ds[0]
+        img, tgt = run(smp, aug)
         prm = synth.ho3d_aug_params(100 + seed) if aug else None
         oimg, ot = ho3d_ref.getitem(smp, prm)
         _close(f"ho3d[{ci}] image", torch.as_tensor(oimg), img, 0, 0)
@@ -436,6 +453,44 @@ def gen_ho3d():
                    depth_sub=tgt["depth"].numpy()[::4, ::4], depth_sum=np.float64(tgt["depth"].numpy().astype(np.float64).sum()),
                    verts_sum=np.float64(tgt["verts"].numpy().astype(np.float64).sum()))
         np.savez_compressed(os.path.join(GOLD, f"ho3d_{ci}.npz"), **out)
+
+
+HO3D_EDGE_KEYS = ("crop_uv", "vis", "crop_center", "crop_size", "st", "scale", "pose3d")
+
+
+def gen_ho3d_edges():
+    """the reference's `__getitem__` on the designed edge cases tests/ho3d_edge_ref.py:GOLDEN (fuse_bbox quirks, rint ties, the
+    boundaries of both visibility passes).  Only the small targets are stored (tests/golden/ho3d_edge_<name>.npz, a few KB each);
+    the sample itself is rebuilt from the case name.  For an augmented case the reference's np.random draws are served, in its
+    order (three colour factors, scale, rand(1) = angle / 2 pi, two normals), from the case's designed parameters."""
+    from oracle import ho3d_ref
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ho3d_edge_ref as edge
+    print("[ho3d edges]")
+    _, _, run = _ho3d_reference()
+    for name, augmented in edge.GOLDEN:
+        smp, a = edge.build(name)
+        prm = edge.aug_dict(a) if augmented else None
+        saved = np.random.uniform, np.random.rand, np.random.normal
+        if augmented:
+            uni, nrm = [prm["pn"], prm["scale"]], [prm["tx"], prm["ty"]]
+            np.random.uniform = lambda *a_, **k_: uni.pop(0)
+            np.random.rand = lambda *a_: np.array([prm["angle"] / (2 * np.pi)])
+            np.random.normal = lambda *a_, **k_: nrm.pop(0)
+            assert 2 * np.pi * (prm["angle"] / (2 * np.pi)) == prm["angle"], "the angle must survive the reference's 2 pi * rand"
+        np.random.seed(7)
+        try:
+            img, tgt = run(smp, augmented)
+        finally:
+            np.random.uniform, np.random.rand, np.random.normal = saved
+        oimg, ot = ho3d_ref.getitem(smp, prm)
+        _close(f"ho3d edge {name} image", torch.as_tensor(oimg), img, 0, 0)
+        for k in HO3D_EDGE_KEYS + ("depth", "original_pose3d", "verts", "pose3d_root", "rot_mat_inv", "_rot_mat", "uvd"):
+            _close(f"ho3d edge {name} {k}", torch.as_tensor(ot[k]), tgt[k].reshape(ot[k].shape), 2e-6, 1e-7)
+        for k in ("hand_mask", "object_mask"):
+            assert np.array_equal(ot[k], tgt[k].numpy()), k
+        assert np.array_equal(ot["vis"], tgt["vis"].numpy()) and np.array_equal(ot["crop_center"], tgt["crop_center"].numpy()), name
+        np.savez_compressed(os.path.join(GOLD, f"ho3d_edge_{name}.npz"), aug=int(augmented), **{k: np.asarray(tgt[k]) for k in HO3D_EDGE_KEYS})
 
 
 def gen_index_tables():
@@ -496,6 +551,7 @@ def main():
     gen_priors(network, tables)
     gen_rot6d()
     gen_ho3d()
+    gen_ho3d_edges()
     print("golden fixtures written to", GOLD)
 
 
