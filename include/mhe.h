@@ -1064,6 +1064,30 @@ int mhe_chamfer_bwd_f32(const float *points, const float *scale, const float *ro
 int mhe_mesh_eval_f32(const float *pred, const float *target, const float *scale, const float *thr, float *err, float *prf, int N, int B, int V, int T,
                       float unit, void *stream);
 
+/* 3D PCK curve, its area and the mean error of every hypothesis' points (joints or mesh vertices) against its image's ground truth
+ * (csrc/pck.hip), the other two numbers of the FreiHAND / HO3D leaderboards.  The official evaluation code is not available to this project:
+ * parity with it is UNPINNED, the contract below is this project's own and is what the tests pin.  Rows are sample-major, r = n B + b:
+ *   su = scale[b] unit,  p = pred[r] su,  g = target[b] su,  d_p = |p - g| in f32,  a point p of image b is valid when valid[b][p] != 0
+ *   hits[r][i] = #{valid p: d_p <= thr[i]}                 the comparison is inclusive: a point exactly thr[i] away counts.  Exact integers.
+ *   err[r]     = (1/n_valid) sum over the valid p of d_p   f32, summed in a fixed order
+ *   auc[r]     = sum_{i<T-1} (thr[i+1] - thr[i]) (hits[i] + hits[i+1]) / (2 n_valid (thr[T-1] - thr[0]))
+ *                the trapezoid rule over the trapezoid of the constant 1, evaluated in f64 from the f32 thresholds and rounded once to f32
+ * mhe_pck_curve_f32: pred [N,B,P,3], target [B,P,3], scale [B], valid [B,P] bytes or NULL (all valid), thr = T thresholds in DEVICE memory,
+ *   strictly ascending, in the output's unit (unit = 1000: mm) -> hits [N,B,T] int32 or NULL, auc [N,B], err [N,B].
+ *   1 <= P <= MHE_PCK_MAX_POINTS, 2 <= T <= MHE_PCK_MAX_THRESHOLDS, N B < 2^31.
+ *   A row whose image has no valid point: hits 0, auc and err NaN.  A non-finite distance hits nothing and makes its row's err NaN; other
+ *   rows are not disturbed.  The table is read as given (nothing on the host reads it, so the call can be captured into a HIP graph): for a
+ *   table that is not ascending the result is unspecified, but every access stays in bounds.
+ *   A workgroup keeps its image's scaled target, valid mask and the thresholds in LDS for all the hypotheses it walks; N is split over enough
+ *   workgroups to fill the chip at any B.  A distance's bin is found by binary search in the f32 table itself (what T comparisons would give),
+ *   bins are counted by integer LDS adds, a prefix sum gives hits.  No float atomics, fixed summation order: two calls give the same bits.
+ *   No allocation, no workspace.  MHE_ERR_ARG before any launch for a null pointer (other than valid and hits), a shape out of range, a NaN
+ *   unit, thr in host memory, or outputs that overlap inputs or each other. */
+#define MHE_PCK_MAX_POINTS 778
+#define MHE_PCK_MAX_THRESHOLDS 256
+int mhe_pck_curve_f32(const float *pred, const float *target, const float *scale, const unsigned char *valid, const float *thr, float unit, int *hits,
+                      float *auc, float *err, int N, int B, int P, int T, void *stream);
+
 /* Silhouette and depth of a triangle mesh under the 2D head's orthographic camera (csrc/render.hip; the call chain of the reference's
  * ManoLayer.render, hand/ManoLayer.py:62-105, whose third-party rasteriser `neural_renderer` is commented out there and absent here: parity
  * with it is UNPINNED, the contract below is this project's own and is what the tests pin).  R rows (hypotheses), forward only.

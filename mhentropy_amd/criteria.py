@@ -5,7 +5,8 @@ evaluation in csrc/procrustes.hip.  chamfer_dist (hand/criteria.py:18-39) and th
 it was written for (chamfer_select) run on csrc/chamfer.hip; silhouette_iou scores the hypotheses' meshes against the image's hand mask
 on csrc/render.hip; silhouette_dist, the differentiable distance of the projected mesh to that mask, and silhouette_select run on
 csrc/silhouette.hip; kmeans_select, which summarises the hypotheses by the representatives of Q k-means modes, runs on csrc/kmeans.hip;
-mesh_eval, the HO3D mesh protocol (vertex error, F-score, best of n) against target['verts'], and mesh_select run on csrc/mesh_eval.hip."""
+mesh_eval, the HO3D mesh protocol (vertex error, F-score, best of n) against target['verts'], and mesh_select run on csrc/mesh_eval.hip;
+pck_auc, the 3D PCK curve and its area (AUC) of the joints or of the mesh, and pck_select run on csrc/pck.hip."""
 import torch
 from torch import nn
 
@@ -172,11 +173,7 @@ def _mesh_operands(who, output, target, thresholds=(5.0,), ns=None):
     if any(not t > 0 for t in thr):
         raise ValueError(f"{who}: thresholds must be positive, got {thr!r}")
     if ns is not None:
-        ns = (ns,) if isinstance(ns, int) else tuple(ns)
-        if not 1 <= len(ns) <= 8 or any(not isinstance(n, int) or isinstance(n, bool) for n in ns):
-            raise ValueError(f"{who}: ns must hold 1 to 8 integers, got {ns!r}")
-        if any(not 1 <= n <= N for n in ns) or any(b <= a for a, b in zip(ns, ns[1:])):
-            raise ValueError(f"{who}: ns must be strictly increasing within 1..N={N}, got {ns!r}")
+        ns = _check_ns(who, ns, N)
     return pv.detach().reshape(N, B, V, 3), tv.detach().reshape(B, V, 3), scale.detach(), thr, ns
 
 
@@ -234,6 +231,123 @@ def mesh_select(output, target, Q=1, aligned=False):
         raise ValueError("mesh_select: output has no 'verts'")
     _select_shape("mesh_select", "verts", output["verts"], Q)
     return _cut(output, _mesh_eval("mesh_select", output, target, (5.0,), aligned, None)["mesh_err"], Q, "mesh_err")
+
+
+PCK_TARGET = {"xyz": "pose3d", "verts": "verts"}          # the target's key for output[points]
+
+
+def _check_ns(who, ns, N):
+    ns = (ns,) if isinstance(ns, int) else tuple(ns)
+    if not 1 <= len(ns) <= 8 or any(not isinstance(n, int) or isinstance(n, bool) for n in ns):
+        raise ValueError(f"{who}: ns must hold 1 to 8 integers, got {ns!r}")
+    if any(not 1 <= n <= N for n in ns) or any(b <= a for a, b in zip(ns, ns[1:])):
+        raise ValueError(f"{who}: ns must be strictly increasing within 1..N={N}, got {ns!r}")
+    return ns
+
+
+def _pck_operands(who, output, target, points, vmin, vmax, steps, ns, valid):
+    """the checks of pck_auc that need no device -> (points (N, B, P, 3) view-shaped, target points (B, P, 3), scale (B,), thresholds (T,) f32
+    numpy, ns | None, valid (B, P) | None)"""
+    import numpy as np
+    if points not in PCK_TARGET:
+        raise ValueError(f"{who}: points={points!r} (xyz or verts)")
+    tkey = PCK_TARGET[points]
+    if points not in output:
+        raise ValueError(f"{who}: output has no {points!r}")
+    for k in (tkey, "scale"):
+        if k not in target:
+            raise ValueError(f"{who}: target has no {k!r}")
+    pv, tv, scale = output[points], target[tkey], target["scale"]
+    if not isinstance(pv, torch.Tensor) or pv.dim() not in (3, 4) or (pv.dim() == 4 and pv.shape[-1] != 3) or pv.shape[2:].numel() % 3:
+        raise ValueError(f"{who}: output[{points!r}] must be (N, B, P*3) or (N, B, P, 3), got {tuple(getattr(pv, 'shape', ()))}")
+    N, B, P = pv.shape[0], pv.shape[1], pv.shape[2:].numel() // 3
+    if not isinstance(tv, torch.Tensor) or tv.dim() not in (2, 3) or (tv.dim() == 3 and tv.shape[-1] != 3) or tv.shape[1:].numel() % 3:
+        raise ValueError(f"{who}: target[{tkey!r}] must be (B, P*3) or (B, P, 3), got {tuple(getattr(tv, 'shape', ()))}")
+    if tv.shape[0] != B:
+        raise ValueError(f"{who}: output[{points!r}] has B={B} images, target[{tkey!r}] {tv.shape[0]}")
+    if tv.shape[1:].numel() // 3 != P:
+        raise ValueError(f"{who}: output[{points!r}] has P={P} points, target[{tkey!r}] {tv.shape[1:].numel() // 3}")
+    if not 1 <= P <= ops.PCK_MAX_POINTS:
+        raise ValueError(f"{who}: output[{points!r}] has P={P} points per hypothesis (1..{ops.PCK_MAX_POINTS})")
+    if not 1 <= N or not 1 <= B:
+        raise ValueError(f"{who}: output[{points!r}] is empty, {tuple(pv.shape)}")
+    if not isinstance(scale, torch.Tensor) or tuple(scale.shape) != (B,):
+        raise ValueError(f"{who}: target['scale'] must be (B,) = ({B},), got {tuple(getattr(scale, 'shape', ()))}")
+    if isinstance(steps, bool) or not isinstance(steps, int) or not 2 <= steps <= ops.PCK_MAX_THRESHOLDS:
+        raise ValueError(f"{who}: steps={steps!r} (an integer in 2..{ops.PCK_MAX_THRESHOLDS})")
+    try:
+        vmin, vmax = float(vmin), float(vmax)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: vmin={vmin!r}, vmax={vmax!r} must be numbers") from None
+    if not (np.isfinite(vmin) and np.isfinite(vmax)) or not vmax > vmin:
+        raise ValueError(f"{who}: vmin={vmin!r}, vmax={vmax!r} must be finite with vmax > vmin")
+    thr = np.linspace(vmin, vmax, steps).astype(np.float32)          # f64, rounded once
+    if not np.isfinite(thr).all() or not (np.diff(thr) > 0).all():
+        raise ValueError(f"{who}: {steps} steps from vmin={vmin!r} to vmax={vmax!r} are not strictly ascending in float32")
+    if ns is not None:
+        ns = _check_ns(who, ns, N)
+    if valid is not None and (not isinstance(valid, torch.Tensor) or tuple(valid.shape) != (B, P) or valid.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError(f"{who}: valid must be a (B, P) = ({B}, {P}) bool or uint8 tensor, got {tuple(getattr(valid, 'shape', ()))} "
+                         f"{getattr(valid, 'dtype', type(valid))}")
+    return pv.detach().reshape(N, B, P, 3), tv.detach().reshape(B, P, 3), scale.detach(), thr, ns, valid
+
+
+def pck_auc(output, target, points="xyz", vmin=0.0, vmax=50.0, steps=100, aligned=False, ns=None, valid=None, curve=False):
+    """The 3D PCK curve of every hypothesis of a sample() output and the area under it (the AUC of the HO3D / FreiHAND leaderboards):
+    points='xyz': the joints output['xyz'] (N, B, 63) against target['pose3d'] (B, 63); points='verts': output['verts'] (N, B, V*3) or
+    (N, B, V, 3) against target['verts'].  Both sides are scaled by target['scale'] * 1000 (mm), d_p is the distance of point p to its ground
+    truth, and with thresholds = np.linspace(vmin, vmax, steps) (computed in f64, rounded to f32; mm)
+        hits (N, B, T) int32   the valid points with d_p <= thresholds[i] (inclusive); PCK = hits / n_valid          (curve=True only)
+        auc  (N, B)            trapezoid area under the PCK curve over the trapezoid of the constant 1: in [0, 1]
+        err  (N, B)            mean of d_p over the valid points, in mm
+        thresholds (T,)        the f32 table, on the device
+        n_valid (B,) int32     the valid points of every image                                                     (curve=True only)
+    The integer hits and n_valid of several batches can be added into a pooled curve without rounding (harness.PckPool).
+    valid (B, P) bool or uint8: the points that count; an image with none gives hits 0 and auc = err = NaN.
+    aligned=True: every hypothesis is first Procrustes-aligned with scale to its target (ops.procrustes_align, as mesh_eval); the output's
+    tensor is not replaced.  ns=[n1, ...] (strictly increasing, within 1..N): adds auc_max and auc_index (len(ns), B), the largest auc among
+    hypotheses 0 .. n-1 and the lowest n attaining it (int64).
+    No gradient.  Runs on csrc/pck.hip (no per-point distance is written); HIP tensors only (MheError otherwise).  ValueError, before anything
+    touches the device, for a missing key, B or P that disagree, P outside 1..778, steps outside 2..256, vmin or vmax non-finite or
+    vmax <= vmin, ns outside 1..N or not increasing, a valid of the wrong shape or dtype."""
+    return _pck_auc("pck_auc", output, target, points, vmin, vmax, steps, aligned, ns, valid, curve)
+
+
+def _pck_auc(who, output, target, points, vmin, vmax, steps, aligned, ns, valid, curve):
+    pv, tv, scale, thr, ns, valid = _pck_operands(who, output, target, points, vmin, vmax, steps, ns, valid)
+    with torch.no_grad():
+        pv, tv, scale = pv.float().contiguous(), tv.float().contiguous(), scale.float().contiguous()
+        if not pv.is_cuda:
+            raise ops._lib.MheError(f"{who}: expected CUDA/HIP tensors (the hot path has no CPU fallback)")
+        if valid is not None:
+            valid = valid.contiguous()
+        if aligned:
+            pv = ops.procrustes_align(pv, tv)
+        table = ops.pck_thresholds(thr, pv.device)
+        hits, auc, err = ops.pck_curve(pv, tv, scale, table, valid, MESH_UNIT, want_hits=curve)
+        res = {"auc": auc, "err": err, "thresholds": table}
+        if curve:
+            B, P = tv.shape[:2]
+            res["hits"] = hits
+            res["n_valid"] = torch.full((B,), P, device=pv.device, dtype=torch.int32) if valid is None else (valid != 0).sum(1, dtype=torch.int32)
+        if ns is not None:
+            val, idx = _min_first_n(auc.neg().t().contiguous(), ns)          # max auc = -min(-auc)
+            res["auc_max"], res["auc_index"] = val.neg().t().contiguous(), idx.t().long()
+    return res
+
+
+def pck_select(output, target, Q=1, points="xyz", aligned=False):
+    """mesh_select ranked on the AUC: keep, per image, the Q hypotheses of a sample() output of largest auc (pck_auc with its default
+    thresholds; points and aligned as there), largest first, ties to the lower n.  Every (N, B, ...) tensor of `output` is cut to (Q, B, ...);
+    'faces' and 'image' pass through.  Added: 'auc' (Q, B) and 'auc_index' (Q, B) int64."""
+    if points not in PCK_TARGET:
+        raise ValueError(f"pck_select: points={points!r} (xyz or verts)")
+    if points not in output:
+        raise ValueError(f"pck_select: output has no {points!r}")
+    _select_shape("pck_select", points, output[points], Q)
+    out = _cut(output, _pck_auc("pck_select", output, target, points, 0.0, 50.0, 100, aligned, None, None, False)["auc"].neg(), Q, "auc")
+    out["auc"] = out["auc"].neg()
+    return out
 
 
 def silhouette_mask_checks(hand_mask, B, size, who="silhouette_dist"):

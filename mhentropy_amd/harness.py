@@ -170,6 +170,68 @@ def mesh_scalars(out, y):
     return {k: float(res[k]) for k in MESH_SCALARS}
 
 
+PCK_SCALARS = tuple(k + s for s in ("", "_best") for k in ("auc_j", "auc_j_pa", "auc_v", "auc_v_pa"))
+
+
+def pck_scalars(out, y, pool=None):
+    """the AUC half of the HO3D / FreiHAND protocol of one metrics pass (run --pck-metrics): criteria.pck_auc (0..50 mm, 100 thresholds) of the
+    joints out['xyz'] against y['pose3d'] (auc_j) and of the mesh out['verts'] against y['verts'] (auc_v), plain and Procrustes-aligned (_pa)
+    -> {name: float} for PCK_SCALARS: the mean over hypotheses and images, and under `_best` the mean over images of the best of the N
+    hypotheses.  pool: a {name: PckPool} dict with the four plain names - every pass's curve of hypothesis 0 is added to it."""
+    from .criteria import pck_auc
+    res = {}
+    for name, points in (("auc_j", "xyz"), ("auc_v", "verts")):
+        N = out[points].shape[0]
+        for sfx, aligned in (("", False), ("_pa", True)):
+            m = pck_auc(out, y, points=points, aligned=aligned, ns=[N], curve=pool is not None)
+            res[name + sfx], res[name + sfx + "_best"] = m["auc"].mean(), m["auc_max"][-1].mean()
+            if pool is not None:
+                pool[name + sfx].add(m["hits"], m["n_valid"], m["thresholds"])
+    return {k: float(res[k]) for k in PCK_SCALARS}
+
+
+class PckPool:
+    """The pooled PCK curve of an evaluation run: the integer hits of hypothesis 0 and the valid points of every batch (criteria.pck_auc with
+    curve=True) are added in int64 on the device, so the dataset's curve is exact whatever the batch sizes and masks were - a mean of per-batch
+    AUCs is not.  Nothing is read on the host before curve() / auc()."""
+    def __init__(self):
+        self.hits = self.n_valid = self.thresholds = None
+        self.other_tables = []          # threshold tensors of later calls that are not the first call's object: compared on the host in curve()
+
+    def add(self, hits, n_valid, thresholds):
+        """hits (N, B, T) int32, n_valid (B,) int32, thresholds (T,) of one call.  Every call must bring the same thresholds: another length is
+        refused here, other values of the same length in curve(), where the host reads anyway"""
+        h, n = hits[0].sum(0, dtype=torch.int64), n_valid.sum(dtype=torch.int64)
+        if self.hits is None:
+            self.hits, self.n_valid, self.thresholds = h, n, thresholds
+            return
+        if h.shape != self.hits.shape or thresholds.shape != self.thresholds.shape:
+            raise ValueError(f"PckPool.add: {h.shape[0]} thresholds, the pool holds {self.hits.shape[0]}")
+        if thresholds is not self.thresholds and all(thresholds is not t for t in self.other_tables):
+            self.other_tables.append(thresholds)
+        self.hits, self.n_valid = self.hits + h, self.n_valid + n
+
+    def curve(self):
+        """-> (thresholds (T,) float32, hits (T,) int64, n_valid int) as numpy / int; ValueError if the calls did not share one table"""
+        if self.hits is None:
+            raise ValueError("PckPool: nothing was added")
+        thr = self.thresholds.cpu().numpy()
+        for t in self.other_tables:
+            if not (t.cpu().numpy() == thr).all():
+                raise ValueError("PckPool: the calls were made with different thresholds; their hits cannot be pooled")
+        self.other_tables = []
+        return thr, self.hits.cpu().numpy(), int(self.n_valid)
+
+    def auc(self):
+        """the area under the pooled curve by mhe_pck_curve_f32's rule, in f64: NaN when no point was valid"""
+        import numpy as np
+        thr, hits, n = self.curve()
+        if n == 0:
+            return float("nan")
+        t = thr.astype(np.float64)
+        return float((np.diff(t) * (hits[:-1] + hits[1:])).sum() / (2.0 * n * (t[-1] - t[0])))
+
+
 DEPTH_SCALARS = ("depth_dist", "depth_dist_best", "depth_mpjpe")
 
 
@@ -224,6 +286,8 @@ class ScalarLog:
         """the mesh metrics of one iteration (mesh_scalars), under `metric_it/<name>` like the other per-iteration metrics"""
         for k, v in scalars.items():
             self.add_scalar(f"metric_it/{k}", v, step)
+
+    named = mesh          # any {name: float} of one iteration (pck_scalars): the same tags
 
     def epoch(self, step, loss_avg, eval_3d_avg, train=True):
         """hand/CrossModalHand.py:557-564"""

@@ -731,6 +731,61 @@ def mesh_eval(pred, target, scale, thresholds, unit=1000.0):
     return err, prf
 
 
+PCK_MAX_POINTS, PCK_MAX_THRESHOLDS = 778, 256         # MHE_PCK_MAX_POINTS / MHE_PCK_MAX_THRESHOLDS of include/mhe.h
+_PCK_TABLES = {}          # (f32 bytes of the thresholds, device) -> the uploaded table
+
+
+def pck_thresholds(values, device):
+    """a Python sequence of thresholds -> the device f32 table [T] mhe_pck_curve_f32 reads: checked here for 2..256 finite values that are
+    strictly ascending as f32, uploaded once per (values, device) and kept.  The first call with a new sequence copies from the host: make it
+    before a HIP graph is captured, not inside the capture (a later call with the same values only looks the table up).  The tables (1 KB at
+    most each) are kept for the life of the process, like the grow-only workspaces: a captured graph may have baked a table's address in, so
+    none is ever dropped - pass a device tensor of your own where the values change from call to call."""
+    try:
+        thr = np.asarray([float(t) for t in values], np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        raise _lib.MheError(f"pck_curve.thresholds: expected a device tensor or a sequence of numbers, got {values!r}") from None
+    if not 2 <= thr.size <= PCK_MAX_THRESHOLDS:
+        raise _lib.MheError(f"pck_curve.thresholds: {thr.size} thresholds (2..{PCK_MAX_THRESHOLDS})")
+    if not np.isfinite(thr).all() or not (np.diff(thr) > 0).all():
+        raise _lib.MheError("pck_curve.thresholds: must be finite and strictly ascending as float32")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.MheError("pck_curve.thresholds: expected a CUDA/HIP device (the hot path has no CPU fallback)")
+    key = (thr.tobytes(), device.index if device.index is not None else torch.cuda.current_device())
+    table = _PCK_TABLES.get(key)
+    if table is None:
+        table = _PCK_TABLES[key] = torch.from_numpy(thr).to(device)
+    return table
+
+
+def pck_curve(pred, target, scale, thresholds, valid=None, unit=1000.0, want_hits=True):
+    """3D PCK curve (include/mhe.h, mhe_pck_curve_f32): pred [N,B,P,3], target [B,P,3], scale [B], thresholds = a device f32 tensor [T], taken as
+    given (strictly ascending is the caller's word: nothing is read on the host), or a Python sequence (pck_thresholds), in the output's unit
+    (unit 1000: mm); valid [B,P] bool / uint8 or None (all points) -> (hits [N,B,T] int32, the valid points within each threshold (inclusive),
+    or None without want_hits; auc [N,B], the normalised trapezoid area under hits / n_valid; err [N,B], the mean distance over the valid points)"""
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 4 or pred.shape[-1] != 3:
+        raise _lib.MheError("pck_curve.pred: expected an [N,B,P,3] tensor")
+    N, B, P = pred.shape[:3]
+    _chk(pred, torch.float32, "pck_curve.pred"); _chk(target, torch.float32, "pck_curve.target", (B, P, 3)); _chk(scale, torch.float32, "pck_curve.scale", (B,))
+    if isinstance(thresholds, torch.Tensor):
+        _chk(thresholds, torch.float32, "pck_curve.thresholds")
+        if thresholds.dim() != 1 or not 2 <= thresholds.shape[0] <= PCK_MAX_THRESHOLDS:
+            raise _lib.MheError(f"pck_curve.thresholds: expected a [T] tensor with T in 2..{PCK_MAX_THRESHOLDS}, got {tuple(thresholds.shape)}")
+    else:
+        thresholds = pck_thresholds(thresholds, pred.device)
+    T = thresholds.shape[0]
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8):
+            raise _lib.MheError(f"pck_curve.valid: expected a bool or uint8 tensor, got {getattr(valid, 'dtype', type(valid))}")
+        _chk(valid, valid.dtype, "pck_curve.valid", (B, P))
+    hits = torch.empty(N, B, T, device=pred.device, dtype=torch.int32) if want_hits else None
+    auc = torch.empty(N, B, device=pred.device, dtype=torch.float32)
+    err = torch.empty(N, B, device=pred.device, dtype=torch.float32)
+    launch("mhe_pck_curve_f32", pred, target, scale, valid, thresholds, float(unit), hits, auc, err, N, B, P, T)
+    return hits, auc, err
+
+
 SILHOUETTE_MAX_SIZE, SILHOUETTE_MAX_VERTS = 64, 778         # MHE_SILHOUETTE_MAX_SIZE / _MAX_VERTS of include/mhe.h
 
 

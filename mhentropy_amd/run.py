@@ -11,6 +11,7 @@ on synthetic batches (no dataset ships with this repository; the HO3D pipeline i
     python -m mhentropy_amd.run --sil-w 1 --sil-occluder ...   # ... with the object's mask as the term's occluder (get_loss(sil_occluder=True))
     python -m mhentropy_amd.run --test-samples 200 --quant-samples 10 --quant kmeans ...      # metrics of 10 k-means modes of 200 hypotheses
     python -m mhentropy_amd.run --test-samples 200 --mesh-metrics ...       # HO3D mesh protocol: vertex error, F@5 / F@15 mm, aligned, best of N
+    python -m mhentropy_amd.run --test-samples 200 --pck-metrics ...        # AUC of the 3D PCK curve 0..50 mm, joints and mesh, aligned, best of N
     python -m mhentropy_amd.run --test-samples 200 --depth-metrics ...      # depth agreement with the depth crop: top hypothesis, best of N, MPJPE of the pick
 """
 import argparse
@@ -81,6 +82,13 @@ def main(argv=None):
                          "and F-score at 5 and 15 mm, plain and Procrustes-aligned, mean and best of N) and report them as mesh_err, mesh_err_pa, "
                          "f5, f15, f5_pa, f15_pa and *_best (the scalars log: metric_it/<name>).  The target mesh is the mesh of a seeded "
                          "ground-truth pose (synth.mesh_pose) by default, the pipeline's verts under --input-pipeline; needs --test-samples > 0")
+    ap.add_argument("--pck-metrics", action="store_true",
+                    help="evaluate the joints and meshes of the --test-samples metrics pass by the area under the 3D PCK curve from 0 to 50 mm "
+                         "(criteria.pck_auc, 100 thresholds, plain and Procrustes-aligned, mean and best of N) and report them as auc_j, "
+                         "auc_j_pa, auc_v, auc_v_pa and *_best (the scalars log: metric_it/<name>); the run's pooled AUC of the top hypothesis "
+                         "(harness.PckPool: integer hits added over all iterations) is printed at the end.  The target mesh as for "
+                         "--mesh-metrics: a seeded ground-truth pose by default, the pipeline's verts under --input-pipeline; needs "
+                         "--test-samples > 0")
     ap.add_argument("--depth-metrics", action="store_true",
                     help="score the meshes of the --test-samples metrics pass against the depth crop (criteria.depth_dist, offset fitted per "
                          "hypothesis) and report depth_dist (the top hypothesis, metres), depth_dist_best (best of N) and depth_mpjpe (the MPJPE "
@@ -109,6 +117,8 @@ def main(argv=None):
         raise SystemExit(f"--quant-samples {args.quant_samples} is more than the {args.test_samples} hypotheses of --test-samples")
     if args.mesh_metrics and not args.test_samples > 0:
         raise SystemExit("--mesh-metrics needs --test-samples > 0 (the meshes come from the metrics pass)")
+    if args.pck_metrics and not args.test_samples > 0:
+        raise SystemExit("--pck-metrics needs --test-samples > 0 (the joints and meshes come from the metrics pass)")
     if args.depth_metrics and not args.test_samples > 0:
         raise SystemExit("--depth-metrics needs --test-samples > 0 (the meshes come from the metrics pass)")
 
@@ -141,6 +151,10 @@ def main(argv=None):
         meters.update({k: harness.AverageMeter() for k in harness.MESH_SCALARS})
     if args.depth_metrics:
         meters.update({k: harness.AverageMeter() for k in harness.DEPTH_SCALARS})
+    pck_pool = None
+    if args.pck_metrics:
+        meters.update({k: harness.AverageMeter() for k in harness.PCK_SCALARS})
+        pck_pool = {k: harness.PckPool() for k in harness.PCK_SCALARS[:4]}
     step, log = 0, []
     graphed, graphed_lr, sx, sy = None, None, None, None
     if args.input_pipeline:
@@ -172,7 +186,7 @@ def main(argv=None):
                 if args.sil_occluder:
                     yn["hand_mask"], yn["object_mask"] = synth.object_masks(args.seed + 1000 * rank + step, yn["hand_mask"])
                 y = {k: torch.as_tensor(v).cuda() for k, v in yn.items()}
-                if args.mesh_metrics or args.depth_metrics:
+                if args.mesh_metrics or args.depth_metrics or args.pck_metrics:
                     with torch.no_grad():          # the mesh of the seeded ground-truth pose, normalised like the hypotheses' meshes
                         y["verts"] = model.mano_dec.verts(torch.as_tensor(synth.mesh_pose(args.seed + 1000 * rank + step, args.batch)).cuda())
                 if args.depth_metrics:
@@ -212,6 +226,12 @@ def main(argv=None):
                     meters[k].update(v)
                 if scalars is not None:
                     scalars.mesh(step, ms)
+            if args.pck_metrics:
+                ps = harness.pck_scalars(out, y, pool=pck_pool)
+                for k, v in ps.items():
+                    meters[k].update(v)
+                if scalars is not None:
+                    scalars.named(step, ps)
             if args.depth_metrics:
                 with torch.no_grad():
                     ds = harness.depth_scalars(out, y)
@@ -232,6 +252,8 @@ def main(argv=None):
             scalars.epoch(step, rec["loss"], rec["epe3d"])
         if rank == 0:
             print(json.dumps(rec), flush=True)
+    if pck_pool is not None and rank == 0:          # this rank's pooled curves of the top hypothesis over every iteration of the run
+        print(json.dumps({"pck_pooled_auc": {k: round(p.auc(), 6) for k, p in pck_pool.items()}}), flush=True)
     if scalars is not None:
         scalars.close()
     if args.save and rank == 0:
@@ -239,6 +261,7 @@ def main(argv=None):
     if dist is not None:
         dist.destroy_process_group()
     main.last_trainer = trainer           # (tests: optimizer step count, parameters)
+    main.last_pck_pool = pck_pool         # (tests: the pooled curves)
     return log
 
 
